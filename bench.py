@@ -26,14 +26,17 @@ WORLD_SIZE that contradicts --gpus is an error.  Inputs (13-D room features, wei
       its time is throughput, not the critical path of its longest room.  ``fixed_work_best``: the same R jobs with the number of
       slots per GPU chosen by a short sweep (rooms/s is not a property of 68 slots).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the steady leg computed as .npy files (dump_steady_outputs).
 """
 import argparse
+import atexit
 import ctypes
 import json
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 import time
 import zlib
 
@@ -97,10 +100,17 @@ def parse():
     ap.add_argument('--one-rank-collective', type=int, default=1,
                     help='--gpus 1: 1 = a one-rank RCCL process group is brought up and the fixed-work leg\'s label gather goes through its all_gather '
                          '(the nccl branch of learn_region_grow_amd/dist.py executed on the device); 0 = the single-rank short cut')
-    ap.add_argument('--cache', default=os.environ.get('LRG_CACHE', '/tmp/lrg_cache'))
+    ap.add_argument('--cache', default=os.environ.get('LRG_CACHE'),
+                    help='directory of the generated room sets (.npz, keyed by their generation arguments); default: a temporary directory of '
+                         'this run, shared with the runs it starts and removed when it exits (nothing is written into the source tree)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the steady leg computed as DIR/<name>.npy (float32 / float64, at most 64 MB): see dump_steady_outputs')
     ap.add_argument('--named-configs', type=int, default=1, help='1: the ScanNet-shaped (8 rooms in flight) and KITTI-shaped (8 scenes in flight) configurations as short runs of their own, reported as named_configs')
     ap.add_argument('--p0-rooms', type=int, default=4, help='rooms of the preprocessing (P0) side measurement (0 = skip)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def _hoisted_numpy_net(weights):
@@ -450,10 +460,83 @@ class _Leg:
             g._release_graph()
 
 
+DUMP_BYTES_MAX = 64 * 1024 * 1024
+
+
+def dump_steady_outputs(out_dir, leg, fill, slot_of=None):
+    """--dump-outputs: what a caller of the steady leg receives for its rooms -- final labels (1-NN filled; cluster labels before the
+    fill-in), regions per room -- as float32 / float64 .npy files, the same bits from run to run for the same arguments.
+      free-running launches: a launch has a time budget, so which rooms one step finishes depends on timing; the labels a room ends with
+          do not (its random stream is keyed by the room).  The rooms are the jobs that took the slots when the leg began (job order,
+          as many as fit in DUMP_BYTES_MAX): after the timed steps the launches go on, outside the clock, until each of them has finished.
+      lock-step iterations: the state of every in-flight room after the last timed iteration (the rooms restart in place when they finish).
+    Files: labels (filled; only with fill-in), cluster_labels, room_points, room_keys (random-stream key), room_regions."""
+    import torch
+    if leg.free:
+        gr = leg.gr
+        per_room = [(gr, r) for r in range(min(gr.n_groups, gr.n_rooms))]
+    else:
+        per_room = [(g, r) for g in leg.growers for r in range(g.n_rooms)]
+        per_room = [per_room[i] for i in np.argsort(slot_of, kind='stable')]      # (slot_of: the slot of each lane's rooms, lane by lane)
+    bytes_per_point = 4 * (2 if fill else 1)
+    total, keep = 0, []
+    for g, r in per_room:
+        total += bytes_per_point * int(g.room_n[r]) + 3 * 8
+        if total > DUMP_BYTES_MAX:
+            break
+        keep.append((g, r))
+    if leg.free:
+        sample = [r for _, r in keep]
+        with torch.cuda.stream(leg.stream):
+            while True:
+                rr = gr._read_rooms()
+                if all(rr[r].done for r in sample):
+                    break
+                if gr.rooms_finished >= gr.n_rooms:
+                    raise SystemExit('bench.py: every room job reported finished, yet rooms %s are not' % [r for r in sample if not rr[r].done])
+                gr.free_run_step(fill=fill)
+            if fill:
+                # a room the launch filled in itself has its fill_sync word set; every other one gets the fill-in the loop gives finished rooms
+                flags = gr.a_fill_sync[:, 3].cpu().numpy() if getattr(gr, 'fill_in_launch', False) else None
+                gr.fill_many([r for r in sample if flags is None or flags[r] != 1])
+                gr.wait_fills()
+    torch.cuda.synchronize()
+    room_info = {}
+    for g in {id(g): g for g, _ in keep}.values():
+        room_info[id(g)] = (g.d_label.cpu().numpy(), g.d_filled.cpu().numpy() if fill else None, g._read_rooms())
+    cols = {'cluster_labels': [], 'labels': [], 'room_points': [], 'room_keys': [], 'room_regions': []}
+    for g, r in keep:
+        lab, filled, rr = room_info[id(g)]
+        o, n = int(g.room_off[r]), int(g.room_n[r])
+        cols['cluster_labels'].append(lab[o:o + n])
+        if fill:
+            cols['labels'].append(filled[o:o + n])
+        cols['room_points'].append(n)
+        cols['room_keys'].append(int(rr[r].room_id))
+        cols['room_regions'].append(int(rr[r].n_regions))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, v in cols.items():
+        if name in ('cluster_labels', 'labels'):
+            if not v:
+                continue
+            a = np.concatenate(v)
+            assert int(np.abs(a).max(initial=0)) < 1 << 24      # (label ids are exact in float32)
+            a = a.astype(np.float32)
+        else:
+            a = np.asarray(v, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        written[name] = list(a.shape)
+    return {'dir': os.path.abspath(out_dir), 'rooms': len(keep), 'arrays': written}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         _respawn_under_torchrun(args)
+    if not args.cache:
+        args.cache = tempfile.mkdtemp(prefix='lrg_cache_')
+        atexit.register(shutil.rmtree, args.cache, True)
     # The contract is ONE JSON line on stdout.  Native libraries write there too (RCCL prints a version banner through C stdio when a communicator is
     # created, flushed at exit -- after the line): everything but the line goes to stderr; the line is written to the real stdout at the end.
     sys.stdout.flush()
@@ -635,6 +718,9 @@ def main():
     inst_steps, rooms_cycled, seeds = lrg_dist.allreduce_sum([float(s1[2] - s0[2]) - voided_steps, float(s1[1] - s0[1]), float(s1[0] - s0[0])], device=coll_dev)
     if int(s1[3]):
         raise SystemExit('bench.py: lrg_grow_async gave up on a hand-over (%d): the numbers would be invalid' % int(s1[3]))
+    dumped = None
+    if args.dump_outputs and rank == 0:      # (outside the clock; the counters above are read)
+        dumped = dump_steady_outputs(args.dump_outputs, leg, bool(args.fill), None if leg.free else [i for p in parts for i in p])
 
     # ------------------------------------------------------------------------------------------------------------------
     # roofline of the kernel the timed loop runs.  Free-running: lrg_grow_async_kernel IS the loop -- its launches were timed with HIP
@@ -917,6 +1003,8 @@ def main():
         mean_n = float(np.mean([len(r['points']) for r in base]))
         out['p2_box_query'] = {'points_per_room_mean': mean_n, 'algorithmic_bytes_per_instance_step': 14.0 * mean_n,
                                'GBps': 14.0 * mean_n * out['value'] / 1e9, 'frac_of_hbm_peak': 14.0 * mean_n * out['value'] / 1e9 / 8000.0}
+        if dumped:
+            out['dumped_outputs'] = dumped
         if iterations:
             out['ms_per_iteration'] = 1e3 * elapsed / iterations
             out['config']['iterations_per_step'] = args.iters_per_step

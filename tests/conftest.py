@@ -25,6 +25,12 @@ def hip_lib():
 
 
 @pytest.fixture(scope='session')
+def workload_cache(tmp_path_factory):
+    """Directory for the generated workload sets (learn_region_grow_amd.workloads caches them as .npz): one per test session."""
+    return str(tmp_path_factory.mktemp('lrg_cache'))
+
+
+@pytest.fixture(scope='session')
 def cuda_device(hip_lib):
     import torch
     if not torch.cuda.is_available():

@@ -15,6 +15,8 @@ NumPy stand-in in tf_numpy_standin.py (this repo's code).  What is executed from
   *_trained_*.npz the same two scripts under the weights this repository trained (learn_region_grow_amd/weights): realistic
                   dynamics -- tens of labelled regions per room, all three stop reasons, restarts whose winner is not restart 0
   stage_*.npz     the whole of stage_data.py (``--area 5``): the staged training tuples it writes to data/staged_area5.h5
+  grouping_ref_cpu.npz  the reference's C++ grouping functions (tf_ops/grouping/test/*.cpp, compiled into oracle/_ref by
+                  oracle/Makefile) on the inputs of tests/test_oracle_units.py
 
 Only data (inputs, expected outputs) is stored; weights are regenerated from their seed by
 learn_region_grow_amd.synthetic.make_synthetic_weights and pinned by a SHA-256 digest.
@@ -170,8 +172,17 @@ def golden_stage(raw_room, tag):
           % (tag, len(g['points']), len(out['count']), len(out['points']), len(out['neighbor_points']), len(out['steps'])))
 
 
+def golden_grouping():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle_units as t
+    assert t.HAVE_REF, 'oracle/_ref not built (make -C oracle where the reference exists)'
+    out = t.reference_grouping_outputs(*t.grouping_inputs())
+    np.savez_compressed(os.path.join(HERE, 'grouping_ref_cpu.npz'), **out)
+    print('grouping_ref_cpu: %s' % ', '.join('%s %s' % (k, v.shape) for k, v in sorted(out.items())))
+
+
 def main():
-    which = sys.argv[1:] or ['net', 'greedy', 'restart', 'beam', 'trained', 'stage']
+    which = sys.argv[1:] or ['net', 'greedy', 'restart', 'beam', 'trained', 'stage', 'grouping']
     if 'net' in which:
         golden_lrgnet(0, 13, 32, 32, 2, seed=11)
         golden_lrgnet(None, 13, 24, 40, 1, seed=12)     # LITE=None as test_region_grow.py passes it; Ni != Nn
@@ -209,6 +220,8 @@ def main():
         room = synthetic.generate_room_points(800, seed=105).astype(np.float32)
         run_reference_script('test_beam_search.py', ['--area', '5', '--scoring', 'np'], room, 'beam_room105',
                              init_globals={'range': lambda *a: list(builtins.range(*a))})
+    if 'grouping' in which:
+        golden_grouping()
 
 
 if __name__ == '__main__':

@@ -81,6 +81,33 @@ def test_bench_line(cuda_device, tmp_path, mode, lanes, graph):
         assert cb['rooms_per_sec'] == cb['measured_small_rooms']['rooms_per_sec_box'] and not cb['rooms_per_sec_extrapolated']
 
 
+@pytest.mark.parametrize('mode', ['free', 'lockstep'])
+def test_bench_dump_outputs_repeat(cuda_device, tmp_path, mode):
+    """--dump-outputs DIR: float32 / float64 arrays of what the steady leg computed, within 64 MB, the same bits from run to run
+    (free-running launches: the final labels of the rooms that took the slots first; lock-step: every room's state after the last step)."""
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ('dump%d' % k)
+        r, lines = run_bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--iters-per-step', '16', '--step-ms', '2', '--rooms', '6', '--mode', mode,
+                              '--fixed-rooms', '0', '--best-slots', '', '--steady-slots', '', '--named-configs', '0', '--cpu-seconds', '0', '--p0-rooms', '0',
+                              '--one-room-ks', '', '--cache', str(tmp_path / 'cache'), '--dump-outputs', str(out)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads(lines[0])
+        assert d['steps'] == 3 and d['ms_per_step'] > 0 and d['dumped_outputs']['rooms'] == 6
+        files = sorted(os.listdir(out))
+        assert files == ['cluster_labels.npy', 'labels.npy', 'room_keys.npy', 'room_points.npy', 'room_regions.npy']
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 * 1024 * 1024
+        dumps.append({f[:-len('.npy')]: np.load(out / f) for f in files})
+    a, b = dumps
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64), f
+        np.testing.assert_array_equal(a[f], b[f], err_msg=f)
+    n = a['room_points'].astype(int)
+    assert len(n) == 6 and len(a['labels']) == n.sum() and len(a['cluster_labels']) == n.sum()
+    if mode == 'free':      # finished rooms: every point labeled after the fill-in
+        assert a['labels'].min() > 0 and (a['room_regions'] > 0).all()
+
+
 def test_bench_line_with_restarts_counts_rows_per_slot(cuda_device, tmp_path):
     """test_random_restart.py's loop, 4 restarts per seed batched per launch: rows_evaluated_fraction is per SLOT (rooms x restarts), so it stays <= 1
     (round 5 divided by the rooms: 2.65 in the 16-restart record)."""

@@ -14,7 +14,6 @@ from test_gpu_fullsize import check_invariants, zero_net
 
 pytestmark = pytest.mark.gpu
 WEIGHT_KW = dict(seed=0, gain=2.0, bias_std=0.2, add_bias_shift=0.0, rmv_bias_shift=-3.0)
-CACHE = '/tmp/lrg_cache'
 
 
 @pytest.fixture(scope='module')
@@ -59,11 +58,11 @@ def test_sixteen_restarts_batched_match_the_oracle(net):
         np.testing.assert_array_equal(res.filled_label, want.filled_label)
 
 
-def test_sixteen_restarts_full_configuration(net):
+def test_sixteen_restarts_full_configuration(net, workload_cache):
     """The configuration as benchmarked: the 68-room Area-5-shaped set, 16 restarts per seed batched, 1088 slots in flight.
     Ground-truth masks: every room passes the invariants; two Area-5-size rooms equal the oracle's restart loop exactly."""
     from learn_region_grow_amd.grow import LanedRegionGrower
-    rooms = workloads.area5_rooms(68, seed_base=1000, cache_dir=CACHE)
+    rooms = workloads.area5_rooms(68, seed_base=1000, cache_dir=workload_cache)
     lg = LanedRegionGrower(net, rooms_in_flight=68, rng='counter', seed=17, policy='gt', restarts=16)
     assert sum(g.S for g in lg.growers) == 68 * 16
     got = lg.run(rooms)
@@ -80,11 +79,11 @@ def test_sixteen_restarts_full_configuration(net):
 
 
 # ---- configs[2]: ScanNet shape ---------------------------------------------------------------------------------------------
-def test_scannet_shaped_rooms(net):
+def test_scannet_shaped_rooms(net, workload_cache):
     """workloads.scannet_rooms(8), all eight in flight (one per GPU in the named case; here one GPU holds them): ground-truth
     masks exactly equal to the oracle, the Bernoulli policy through the invariants + independence from what else is in flight."""
     from learn_region_grow_amd.grow import LanedRegionGrower, RegionGrower
-    rooms = workloads.scannet_rooms(8, seed_base=7000, cache_dir=CACHE)
+    rooms = workloads.scannet_rooms(8, seed_base=7000, cache_dir=workload_cache)
     got = LanedRegionGrower(net, rooms_in_flight=8, lanes=2, rng='counter', seed=23, policy='gt').run(rooms)
     for room, res in zip(rooms, got):
         want = grow_ref.grow_room(room['points'], room['obj_id'], room['order'], None, rng_ref.CounterStream(23, room['room_id']),
@@ -102,13 +101,13 @@ def test_scannet_shaped_rooms(net):
 
 # ---- configs[1]: the benchmark configuration --------------------------------------------------------------------------------
 @pytest.mark.parametrize('mode', ['free-run', 'lock-step'])
-def test_benchmark_configuration_labels(net, mode):
+def test_benchmark_configuration_labels(net, mode, workload_cache):
     """68 Area-5-shaped rooms in flight, as bench.py runs them -- free-running launches (one lane), or lock-step iterations over the
     automatic number of lanes with HIP-graph replays: every room passes the invariants; the labels of eight rooms -- the 45 k-point
     one, the smallest, the median and five more -- equal single-room oracle runs."""
     import torch
     from learn_region_grow_amd.grow import LanedRegionGrower
-    rooms = workloads.area5_rooms(68, seed_base=1000, cache_dir=CACHE)
+    rooms = workloads.area5_rooms(68, seed_base=1000, cache_dir=workload_cache)
     from learn_region_grow_amd.grow import auto_lanes
     if mode == 'free-run':
         lg = LanedRegionGrower(net, rooms_in_flight=68, lanes=None, rng='counter', seed=0, policy='gt')
@@ -159,7 +158,7 @@ def test_restarts_scoring_ml_matches_the_oracle(net):
 
 
 @pytest.mark.parametrize('mode,policy', [('lock-step', 'gt'), ('lock-step', 'net'), ('free-run', 'net')])
-def test_benchmark_configuration_with_a_busy_chip(net, mode, policy):
+def test_benchmark_configuration_with_a_busy_chip(net, mode, policy, workload_cache):
     """Slots must not depend on when their workgroups start.  The front kernel allocates the packed rows of an iteration from
     row 0 again, so a slot whose workgroup starts late -- here: while a second stream keeps every CU busy with dense LrgNet
     evaluations -- would find last iteration's rows overwritten if it still looked for them there (it did, up to ABI 3: with two
@@ -170,7 +169,7 @@ def test_benchmark_configuration_with_a_busy_chip(net, mode, policy):
     import threading
     import torch
     from learn_region_grow_amd.grow import LanedRegionGrower
-    rooms = workloads.area5_rooms(68, seed_base=1000, cache_dir=CACHE)
+    rooms = workloads.area5_rooms(68, seed_base=1000, cache_dir=workload_cache)
     kw = dict(rooms_in_flight=68, rng='counter', seed=0, policy=policy)
     quiet = LanedRegionGrower(net, lanes=1, free_run=False, **kw).run(rooms)      # (lock-step, one lane: every formulation gives the same bits)
     dev = net.device
@@ -232,7 +231,7 @@ def test_voxel_grid_and_channel_major_copy_change_nothing(net, monkeypatch):
 
 # ---- configs[1] exactly as bench.py builds it, against the oracle ------------------------------------------------------------
 @pytest.mark.parametrize('mode', ['free-run', 'lock-step'])
-def test_benchmark_configuration_as_benchmarked_matches_the_oracle(cuda_device, mode):
+def test_benchmark_configuration_as_benchmarked_matches_the_oracle(cuda_device, mode, workload_cache):
     """What bench.py times -- the weights trained by this repository (synthetic.load_trained_weights), the reference's Bernoulli
     policy (test_region_grow.py:266-267), 68 rooms in flight, free-running launches (default) or three lock-step lanes with graph
     replays of four iterations -- against single-room oracle runs evaluating the same GPU network: the 45 k-point room, the
@@ -245,7 +244,7 @@ def test_benchmark_configuration_as_benchmarked_matches_the_oracle(cuda_device, 
     weights = synthetic.load_trained_weights()
     net1 = LrgNetHIP(1, 1, 512, 512, 13, 0, device=cuda_device).load_weights(weights)
     net8 = LrgNetHIP(8, 1, 512, 512, 13, 0, device=cuda_device).load_weights(weights)
-    rooms = workloads.area5_rooms(68, seed_base=1000, cache_dir=CACHE)
+    rooms = workloads.area5_rooms(68, seed_base=1000, cache_dir=workload_cache)
     by_size = [int(i) for i in np.argsort([len(r['points']) for r in rooms])]
     assert len(rooms[by_size[-1]]['points']) > 40000
     picks = [by_size[-1], by_size[len(by_size) // 2], by_size[0]] + by_size[9:60:20]

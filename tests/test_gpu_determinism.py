@@ -20,7 +20,6 @@ import pytest
 from learn_region_grow_amd import synthetic, workloads
 
 pytestmark = pytest.mark.gpu
-CACHE = '/tmp/lrg_cache'
 REPEATS = 8
 
 
@@ -31,8 +30,8 @@ def net(cuda_device):
 
 
 @pytest.fixture(scope='module')
-def rooms():
-    return workloads.area5_rooms(68, seed_base=1000, cache_dir=CACHE)
+def rooms(workload_cache):
+    return workloads.area5_rooms(68, seed_base=1000, cache_dir=workload_cache)
 
 
 def crc_of(results):

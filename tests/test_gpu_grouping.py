@@ -186,14 +186,14 @@ def test_nn1_fill_tiled(cuda_device, hip_lib, F, n, frac):
     assert hip_lib.lrg_nn1_fill_ws(_ptr(dP), n, F, _ptr(dlab), _ptr(out), _ptr(ws), 16, _stream_ptr()) <= -1000
 
 
-def test_nn1_fill_tiled_on_a_room(cuda_device, hip_lib):
+def test_nn1_fill_tiled_on_a_room(cuda_device, hip_lib, workload_cache):
     """Points in object order, as rooms come (the pruned pairs of lrg_nn1_fill_ws: most chunks are farther from a query in xyz than its
     best so far): the result is that of the exhaustive one-workgroup-per-point search, ties included (duplicated rows), with whole
     objects unlabeled and a stretch of points without any labeled neighbour nearby."""
     import torch
     from learn_region_grow_amd import _lib, workloads
     from learn_region_grow_amd.lrgnet import _ptr, _stream_ptr
-    room = workloads.area5_rooms(3, seed_base=1000, cache_dir='/tmp/lrg_cache')[2]
+    room = workloads.area5_rooms(3, seed_base=1000, cache_dir=workload_cache)[2]
     P = np.ascontiguousarray(room['points'][:40000], dtype=np.float32)
     n, F = P.shape
     rs = np.random.RandomState(11)

@@ -9,6 +9,8 @@ import pytest
 
 from oracle import grouping_ref as G, grow_ref, rng_ref
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+
 HAVE_REF = G.ref_lib('query_ball_point') is not None and G.ref_lib('selection_sort') is not None
 
 
@@ -64,26 +66,43 @@ def test_legacy_stream_is_the_reference_call_sequence():
     assert np.array_equal(a.uniform(512), b.random_sample(512))
 
 
-@pytest.mark.skipif(not HAVE_REF, reason='oracle/_ref not built (needs /root/reference at build time)')
-def test_grouping_oracle_equals_reference_cpu_functions():
+def grouping_inputs():
+    """The inputs of the grouping comparison (tests/golden/make_golden.py stores the reference's outputs on them)."""
     rs = np.random.RandomState(0)
     x1 = rs.rand(3, 200, 3).astype(np.float32)
     x2 = rs.rand(3, 50, 3).astype(np.float32)
-    i0, c0 = G.query_ball_point(0.2, 16, x1, x2)
-    i1, _ = G.query_ball_point(0.2, 16, x1, x2, use_reference=True)
-    np.testing.assert_array_equal(i0, i1)
-    assert c0.min() == 0 and c0.max() <= 16
     pts = rs.rand(3, 200, 7).astype(np.float32)
-    np.testing.assert_array_equal(G.group_point(pts, i0), G.group_point(pts, i0, use_reference=True))
     go = rs.rand(3, 50, 16, 7).astype(np.float32)
-    np.testing.assert_array_equal(G.group_point_grad(go, i0, 200), G.group_point_grad(go, i0, 200, use_reference=True))
     d = rs.rand(2, 5, 40).astype(np.float32)
     d[0, 0, 5] = d[0, 0, 9] = d[0, 0].min() - 1     # ties: first minimum must win
+    return x1, x2, pts, go, d
+
+
+def reference_grouping_outputs(x1, x2, pts, go, d):
+    """The reference's own CPU functions (oracle/_ref) on grouping_inputs()."""
+    idx, _ = G.query_ball_point(0.2, 16, x1, x2, use_reference=True)
     with quiet_stdout():
-        ri, ro = G.selection_sort(7, d, use_reference=True)
+        si, so = G.selection_sort(7, d, use_reference=True)
+    return dict(query_ball_point=idx, group_point=G.group_point(pts, idx, use_reference=True),
+                group_point_grad=G.group_point_grad(go, idx, 200, use_reference=True), selection_sort_idx=si, selection_sort_out=so)
+
+
+def test_grouping_oracle_equals_reference_cpu_functions():
+    """The C oracle against the reference's own C++ functions: their outputs as stored in tests/golden/grouping_ref_cpu.npz and,
+    where oracle/_ref was built, as computed now."""
+    x1, x2, pts, go, d = grouping_inputs()
+    i0, c0 = G.query_ball_point(0.2, 16, x1, x2)
+    assert c0.min() == 0 and c0.max() <= 16
     mi, mo = G.selection_sort(7, d)
-    np.testing.assert_array_equal(ri, mi)
-    np.testing.assert_array_equal(ro, mo)
+    mine = dict(query_ball_point=i0, group_point=G.group_point(pts, i0), group_point_grad=G.group_point_grad(go, i0, 200),
+                selection_sort_idx=mi, selection_sort_out=mo)
+    wants = [dict(np.load(os.path.join(GOLDEN, 'grouping_ref_cpu.npz')))]
+    if HAVE_REF:
+        wants.append(reference_grouping_outputs(x1, x2, pts, go, d))
+    for want in wants:
+        assert sorted(want) == sorted(mine)
+        for k in mine:
+            np.testing.assert_array_equal(mine[k], want[k], err_msg=k)
 
 
 def test_selection_sort_known_answer():
