@@ -641,6 +641,40 @@ int lrg_knn_topk(int b, int n, int m, int c, int k, const float *xyz1, const flo
 int lrg_pairwise_sqdist(int b, int n, int m, int c, const float *xyz1, const float *xyz2, float *dist, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * tf_ops/sampling and tf_ops/3d_interpolation replacements.  Argument order of the reference launchers
+ * (tf_ops/sampling/tf_sampling_g.cu:194-212, tf_ops/3d_interpolation/tf_interpolate.cpp:60,107,131) plus a trailing stream;
+ * extern "C"; int return.  No entry point allocates: workspaces come from the caller.
+ * ---------------------------------------------------------------------------------------------- */
+/* farthestpointsamplingLauncher (kernel tf_sampling_g.cu:105-170): inp [b,n,3] -> out [b,m] int32.  out[b,0] = 0; each step
+ * picks the point of largest running minimum squared distance (fp32, no FMA, minima start at 1e38f).  Tie rule (the
+ * reference's 512-thread stride scan with strict > and its left-keeping tree): among equal maxima the smallest
+ * (k mod 512, k) wins; with m > n, once every minimum is 0, index 0 repeats.  n <= 16384 runs from registers and temp may be
+ * NULL; larger n needs temp = b*n floats of device memory (LRG_EINVAL - 3 without it).  m <= 0 writes nothing. */
+int lrg_farthest_point_sample(int b, int n, int m, const float *inp, float *temp, int *out, void *stream);
+/* gatherpointLauncher (:172-181): out [b,m,3] = inp [b,n,3] rows at idx [b,m]; an index outside [0,n) gathers zeros. */
+int lrg_gather_point(int b, int n, int m, const float *inp, const int *idx, float *out, void *stream);
+/* scatteraddpointLauncher (:183-192): inp_g [b,n,3] += out_g [b,m,3] at idx, fp32 atomics; inp_g zeroed by the caller. */
+int lrg_scatter_add_point(int b, int n, int m, const float *out_g, const int *idx, float *inp_g, void *stream);
+/* probsampleLauncher (:198-201): temp [b,n] = inclusive cumsum of inp_p [b,n] (summation order: csrc/lrg_sampling.hip), then
+ * out [b,m] = the smallest j with temp[j] >= inp_r[b,m] * temp[n-1] by the reference's binary search (:90-104). */
+int lrg_prob_sample(int b, int n, int m, const float *inp_p, const float *inp_r, float *temp, int *out, void *stream);
+/* threenn_cpu (tf_interpolate.cpp:60-104), bit for bit: xyz1 [b,n,3] unknown, xyz2 [b,m,3] known -> dist [b,n,3] squared
+ * distances, idx [b,n,3]; the first index wins ties; with m < 3 the missing slots keep idx 0 and dist inf ((float)1e40). */
+int lrg_three_nn(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist, int *idx, void *stream);
+/* threeinterpolate_cpu (:107-128), bit for bit: out [b,n,c] = (p[i1] w1 + p[i2] w2) + p[i3] w3, points [b,m,c], idx and
+ * weight [b,n,3]; an index outside [0,m) contributes 0. */
+int lrg_three_interpolate(int b, int m, int c, int n, const float *points, const int *idx, const float *weight, float *out, void *stream);
+/* threeinterpolate_grad_cpu (:131-155): grad_points [b,m,c] += grad_out [b,n,c] * w at idx, fp32 atomics; grad_points zeroed
+ * by the caller (as lrg_group_point_grad). */
+int lrg_three_interpolate_grad(int b, int n, int c, int m, const float *grad_out, const int *idx, const float *weight,
+                               float *grad_points, void *stream);
+/* The interpolation that opens pointnet_fp_module (train_pointnet.py:145-150) in ONE launch: three_nn, then
+ * inv_i = 1/max(d_i, 1e-10f) (correctly rounded), norm = (inv_0 + inv_1) + inv_2, w_i = inv_i / norm, then three_interpolate of
+ * points [b,m,c] into out [b,n,c].  dist, idx, weight [b,n,3] are optional outputs (NULL: not written).  m >= 1. */
+int lrg_three_nn_interpolate(int b, int n, int m, int c, const float *xyz1, const float *xyz2, const float *points, float *dist,
+                             int *idx, float *weight, float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training side: the pieces of the backward pass and of AdamOptimizer
  * (learn_region_grow_util.py:165-189) that the forward entry points do not cover.  The step is sequenced by the host
  * mirror (learn_region_grow_amd/train.py: LrgNetTrainer.train_step = sess.run([net.train_op, net.loss, ...]) at

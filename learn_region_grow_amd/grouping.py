@@ -121,3 +121,13 @@ def knn_point(k, xyz1, xyz2, fused=None):
                'lrg_pairwise_sqdist')
     outi, out = select_top_k(k, dist)
     return out[:, :, :k].contiguous(), outi[:, :, :k].contiguous()
+
+
+def sample_and_group(npoint, radius, nsample, xyz, points):
+    """train_pointnet.py:113-123: farthest_point_sample + gather_point -> new_xyz (b,npoint,3), then query_ball_group with the
+    centre subtracted and the concat.  -> (new_xyz, new_points (b,npoint,nsample,3+c), idx (b,npoint,nsample), grouped_xyz)."""
+    from .sampling import farthest_point_sample, gather_point
+    new_xyz = gather_point(xyz, farthest_point_sample(npoint, xyz))
+    idx, _, grouped_xyz, grouped_points = query_ball_group(radius, nsample, xyz, new_xyz, points, subtract_center=True)
+    new_points = torch.cat([grouped_xyz, grouped_points], dim=-1) if points is not None else grouped_xyz
+    return new_xyz, new_points, idx, grouped_xyz
