@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Command-line driver with the job of the reference's ``benchmarks.py`` for its classical region-growing baselines:
+modes ``normal``, ``curvature``, ``color``, ``feature`` and ``smoothness`` on the GPU, the reference's per-room timing and
+metric lines and its aggregate line, optional PLY export.
+
+    python baselines.py --area 5 --mode smoothness          # data/s3dis_area5.h5 (benchmarks.py:187-190)
+    python baselines.py --h5 rooms.h5 --mode normal --threshold 0.995 --save out/
+
+The rooms of a file go to the GPU in batches (--batch-rooms per lrg_baseline_segment call); features are computed per room
+(device equalisation and covariances, host numpy.linalg.svd: learn_region_grow_amd.baselines.room_features).  The timing line
+of a room is its feature time plus its share, by equalised points, of its batch's segmentation time.  The other modes of
+benchmarks.py (edge, fpfh, pointnet, pointnet2) are not ported.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.abspath(__file__))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+
+def parse(argv=None):
+    from learn_region_grow_amd.baselines import MODES
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--mode', default='normal', choices=MODES)
+    ap.add_argument('--area', default='1,2,3,4,5,6,scannet', help="comma list of areas: 'scannet', 's3dis', 'kitti_train', ... or an S3DIS area number")
+    ap.add_argument('--h5', default=None, help='room file (overrides --area for the data; the area still names the lines)')
+    ap.add_argument('--data-dir', default='data')
+    ap.add_argument('--threshold', type=float, default=None, help="overrides the mode's first threshold (benchmarks.py:119)")
+    ap.add_argument('--resolution', type=float, default=0.1)
+    ap.add_argument('--save', nargs='?', const='', default=None, help='write <dir>/<n>.ply per room (default dir: data/results/<mode>)')
+    ap.add_argument('--room-names', default=None, help='one room name per line, in file order (data/<area>_room_name.txt)')
+    ap.add_argument('--max-rooms', type=int, default=0)
+    ap.add_argument('--batch-rooms', type=int, default=68, help='rooms per segmentation call')
+    ap.add_argument('--device', default=None, help='default: cuda:0')
+    return ap.parse_args(argv)
+
+
+def area_file(args, area):
+    if args.h5:
+        return args.h5
+    if area in ('scannet', 's3dis', 'kitti_train', 'kitti_val', 'kitti_small'):
+        return os.path.join(args.data_dir, '%s.h5' % area)
+    return os.path.join(args.data_dir, 's3dis_area%s.h5' % area)
+
+
+def main(argv=None):
+    args = parse(argv)
+    from learn_region_grow_amd import baselines, io, metrics
+    areas = args.area.split(',')
+    t = list(baselines.default_thresholds(args.mode, areas[0]))
+    if args.threshold is not None:
+        t[0] = args.threshold
+    print('Using threshold', t[0], 'resolution', args.resolution)
+    need_normals = args.mode != 'color'
+    ms = []
+    save_id = 0
+    for area in areas:
+        rooms, obj_ids, _ = io.loadFromH5(area_file(args, area))
+        if args.max_rooms:
+            rooms = rooms[:args.max_rooms]
+        names = None
+        name_file = args.room_names or os.path.join(args.data_dir, '%s_room_name.txt' % area)
+        if os.path.exists(name_file):
+            names = open(name_file).read().split('\n')
+        for b0 in range(0, len(rooms), max(1, args.batch_rooms)):
+            batch = range(b0, min(len(rooms), b0 + max(1, args.batch_rooms)))
+            feats, ftime = [], []
+            for r in batch:
+                t0 = time.time()
+                feats.append(baselines.room_features(rooms[r], resolution=args.resolution, need_normals=need_normals, device=args.device))
+                ftime.append(time.time() - t0)
+            t0 = time.time()
+            labels = baselines.segment(feats, args.mode, resolution=args.resolution, device=args.device, thresholds=t)
+            seg = time.time() - t0
+            total = max(1, sum(len(f['points']) for f in feats))
+            for j, r in enumerate(batch):
+                f, lab = feats[j], labels[j].astype(np.int64)
+                print('%s %d points: %.2fs' % (names[r] if names is not None and r < len(names) else '', len(rooms[r]),
+                                               ftime[j] + seg * len(f['points']) / total))
+                m = metrics.room_metrics(obj_ids[r][f['equalized_idx']], lab)
+                ms.append(m)
+                print(metrics.room_line(area, r, m))
+                if args.save is not None:
+                    out_dir = args.save or os.path.join(args.data_dir, 'results', args.mode)
+                    os.makedirs(out_dir, exist_ok=True)
+                    pts = np.array(rooms[r][:, :6], dtype=np.float64)
+                    colors = io.label_colors(int(m['cluster_label2'].max()) + 1)
+                    pts[:, 3:6] = colors[m['cluster_label2'], :][f['unequalized_idx']]
+                    io.savePLY(os.path.join(out_dir, ('scannet%d.ply' if area == 'scannet' else '%d.ply') % save_id), pts)
+                    save_id += 1
+    if ms:
+        print(metrics.aggregate_line(ms))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -675,6 +675,35 @@ int lrg_three_nn_interpolate(int b, int n, int m, int c, const float *xyz1, cons
                              int *idx, float *weight, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * benchmarks.py region-growing baselines (benchmarks.py:127-142 thresholds, :251-378 edges on the 26-neighbour voxel graph,
+ * :380-416 components and numbering).  extern "C"; int return; no entry point allocates.  DESIGN.md §3.8.
+ * ---------------------------------------------------------------------------------------------- */
+#define LRG_BASELINE_NORMAL 0          /* normals[k].dot(normals[i]) > t1, as fma(a2,b2, fma(a1,b1, a0*b0)) in float64     */
+#define LRG_BASELINE_CURVATURE 1       /* |curvatures[k] - curvatures[i]| < t1 in float64                                   */
+#define LRG_BASELINE_COLOR 2           /* (d0^2 + d1^2) + d2^2 < (float)t1 in float32, d = rgb[k] - rgb[i]                 */
+#define LRG_BASELINE_FEATURE 3         /* normal with t1 AND curvature with t2 AND color with (float)t3                     */
+#define LRG_BASELINE_SMOOTHNESS 4      /* the normal edges; regions numbered and sized as the reference's DFS (:380-405)     */
+#define LRG_BASELINE_MAX_MIN_CLUSTER 64
+/* Workspace of lrg_baseline_segment: 0 when an argument is out of range (1 <= min_cluster_size <= 64). */
+size_t lrg_baseline_workspace_bytes(int n_points, int n_rooms, int min_cluster_size);
+/* A batch of equalised rooms in one fixed sequence of launches.  room_start [n_rooms + 1] is HOST memory: room r owns points
+ * room_start[r] .. room_start[r+1]-1, room_start[0] = 0, n = room_start[n_rooms] (LRG_EINVAL - 73 if it is not non-decreasing).
+ * Device pointers: pts [n, ld] float32 (xyz, rgb in columns 0-5),
+ * normals [n, 3] and
+ * curvatures [n] float64, rank [n] int32 = the point's position in numpy.argsort(curvatures) of its room (smoothness only).
+ * normals, curvatures and rank may be NULL when the mode does not read them (LRG_EINVAL - 74 when it does).
+ * labels [n] int32: 0 = no cluster, else the room's cluster id (1, 2, ... in the reference's order); n_clusters [n_rooms].
+ * A component is kept when it has more than min_cluster_size points; for smoothness, when the reference's DFS pops more than
+ * min_cluster_size times (duplicates included).  Errors found on the device go to lrg_baseline_status. */
+int lrg_baseline_segment(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode,
+                         const double *normals, const double *curvatures, const int32_t *rank, double t1, double t2, double t3,
+                         int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream);
+/* Error bits of the last lrg_baseline_segment on this workspace (synchronises the stream): 1 a voxel outside the 21-bit window,
+ * 2 two points of one room in one voxel (the room is not equalised), 4 a rank outside [0, room size), 8 a replay stack
+ * overflow (not reachable by the bound of DESIGN.md §3.8).  Labels are not valid when it is non-zero. */
+int lrg_baseline_status(const void *ws, int n_points, int n_rooms, int min_cluster_size, int32_t *host_status, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training side: the pieces of the backward pass and of AdamOptimizer
  * (learn_region_grow_util.py:165-189) that the forward entry points do not cover.  The step is sequenced by the host
  * mirror (learn_region_grow_amd/train.py: LrgNetTrainer.train_step = sess.run([net.train_op, net.loss, ...]) at

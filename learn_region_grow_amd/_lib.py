@@ -10,7 +10,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
-SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip']
+SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
+           'lrg_baselines.hip']
 
 LRG_ABI_VERSION = 10      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
@@ -254,6 +255,11 @@ _SIGS = {
     'lrg_three_interpolate': (ctypes.c_int, [ctypes.c_int] * 4 + [_fp, _fp, _fp, _fp, _fp]),
     'lrg_three_interpolate_grad': (ctypes.c_int, [ctypes.c_int] * 4 + [_fp, _fp, _fp, _fp, _fp]),
     'lrg_three_nn_interpolate': (ctypes.c_int, [ctypes.c_int] * 4 + [_fp] * 8),
+    'lrg_baseline_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3),
+    'lrg_baseline_segment': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_float, ctypes.c_int, _fp, _fp, _fp,
+                                            ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, _fp, ctypes.c_size_t,
+                                            _fp, _fp, _fp]),
+    'lrg_baseline_status': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp]),
     'lrg_gemm_f32': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int,
                                     _fp, ctypes.c_int, _fp, _fp, ctypes.c_int, _fp]),
     'lrg_ce_grad': (ctypes.c_int, [_fp, _fp, ctypes.c_long, ctypes.c_float, ctypes.c_float, _fp, _fp, _fp]),

@@ -1,0 +1,427 @@
+// The classical region-growing baselines of benchmarks.py (modes normal, curvature, color, feature, smoothness) for gfx950.
+//
+// Every mode puts edges on the 26-neighbour voxel graph of an equalised room with a per-mode predicate (benchmarks.py:251-378)
+// and labels the connected components of more than min_cluster_size points (:380-416).  Here a batch of rooms goes through a
+// fixed sequence of launches, one thread per point in each:
+//   init     hash slots empty, parent[i] = i, counters cleared, the room of every point (binary search in room_start)
+//   insert   voxel key -> the room's own linear-probe segment (lrg_pack_voxel / lrg_fmix64); a key met twice is an error
+//   union    26 lookups, the predicate, then a lock-free union of i and j for the neighbours j < i (every predicate is
+//            symmetric, so each edge is handled once).  The larger root is linked under the smaller by CAS, so the root
+//            of a component is its minimum index whatever the order of the unions.
+//   count    every point's root (path halving), component sizes, and for smoothness the minimum (rank, index) of each
+//   keep     one lane per component root: the keep decision (size > min_cluster_size; for smoothness a component of
+//            2 .. min_cluster_size points replays the reference's DFS, whose pop count counts duplicates) and flag[key] = 1,
+//            key = the root's position in its room (networkx's order) or the smallest rank (smoothness)
+//   scan     exclusive scan of the flags (three launches); per-room ids are differences of the global scan
+//   label    label[i] = scan[key of i's component] - scan[room start] + 1 if kept, else 0; n_clusters per room
+//
+// Visibility (MI355X: per-XCD L2s are not coherent).  Inside the union launch every parent word is read with an agent-scope
+// relaxed atomic load (global_load sc1: never from a stale L1) and changed only by agent-scope CAS, which is performed at the
+// device's coherence point.  Correctness needs only that CAS: parents only ever decrease, so a value read late is still an
+// ancestor of the word's point (a larger one), and a root seen as a root that is no longer one fails its CAS and the loop
+// continues from the value the CAS returned.  Every other cross-workgroup read (hash values, final parents, sizes, keys,
+// flags, scans) is separated from its writes by a launch boundary.
+#include "lrg_common.h"
+
+#define BL_THREADS 256
+#define BL_SCAN_ITEMS 8                       // per thread: 2048 elements per block
+
+enum { BL_NORMAL = 0, BL_CURVATURE = 1, BL_COLOR = 2, BL_FEATURE = 3, BL_SMOOTHNESS = 4 };
+// status bits (lrg_baseline_status)
+enum { BL_ST_WINDOW = 1, BL_ST_DUPLICATE = 2, BL_ST_RANK = 4, BL_ST_STACK = 8 };
+
+struct LrgBaselineLayout {
+    size_t keys, vals;                 // hash: 4 n + 64 rooms slots
+    size_t rooms, room_of, parent, size, minkey, ckey, visited, flag, scan, bsum, stack, scal;
+    size_t total;
+    long hslots, stack_cap;
+    int nb;
+};
+
+static int bl_layout(int N, int R, int mcs, LrgBaselineLayout *L) {
+    if (N < 0 || R < 0 || N > (1 << 26) || R > (1 << 20)) return LRG_EINVAL - 70;
+    if (mcs < 1 || mcs > LRG_BASELINE_MAX_MIN_CLUSTER) return LRG_EINVAL - 71;
+    L->hslots = 4L * N + 64L * R;
+    // a replayed component of c <= mcs points pushes at most 26 c times (only a point's first pop finds unvisited
+    // neighbours): 1 + 26 c entries each, at most 27 n over all components
+    L->stack_cap = 27L * N;
+    const long per_block = BL_THREADS * BL_SCAN_ITEMS;
+    L->nb = (int)((N + 1 + per_block - 1) / per_block);
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t at = o; o = lrg_align_up(o + bytes, 256); return at; };
+    L->keys = take((size_t)L->hslots * 8);
+    L->vals = take((size_t)L->hslots * 4);
+    L->rooms = take((size_t)(R + 1) * 4);
+    L->room_of = take((size_t)N * 4);
+    L->parent = take((size_t)N * 4);
+    L->size = take((size_t)N * 4);
+    L->minkey = take((size_t)N * 8);
+    L->ckey = take((size_t)N * 4);
+    L->visited = take((size_t)N * 4);
+    L->flag = take((size_t)(N + 1) * 4);
+    L->scan = take((size_t)(N + 1) * 4);
+    L->bsum = take((size_t)(L->nb + 1) * 4);
+    L->stack = take((size_t)L->stack_cap * 4);
+    L->scal = take(64 * 4);
+    L->total = o;
+    return 0;
+}
+
+struct BlArgs {
+    const float *pts; int ld;
+    const int32_t *room_start; int n_rooms, n;
+    float res; int mode;
+    const double *normals, *curv; const int32_t *rank;
+    double t1, t2, t3; int mcs;
+    uint64_t *keys; int32_t *vals, *room_of, *parent, *size; unsigned long long *minkey;
+    int32_t *ckey, *visited, *flag, *scan, *bsum, *stack, *scal;
+    long hslots, stack_cap;
+    int32_t *labels, *n_clusters;
+};
+
+// Bounds of room r (room_start was checked on the host: this only keeps a bad word from turning into an address)
+__device__ __forceinline__ bool bl_room(const BlArgs &a, int r, int *s, int *e) {
+    const int s0 = a.room_start[r], e0 = a.room_start[r + 1];
+    if (s0 < 0 || e0 < s0 || e0 > a.n) return false;
+    *s = s0; *e = e0;
+    return true;
+}
+
+// the room's hash segment: capacity the smallest power of two >= max(64, 2 n_room) (< 4 n_room + 64), at 4 start + 64 r
+__device__ __forceinline__ void bl_segment(const BlArgs &a, int r, int s, int e, uint64_t **keys, int32_t **vals, int *mask) {
+    int cap = 64;
+    while (cap < 2 * (e - s)) cap <<= 1;
+    const long off = 4L * s + 64L * r;
+    *keys = a.keys + off; *vals = a.vals + off; *mask = cap - 1;
+}
+
+// normals[k].dot(normals[i]) as OpenBLAS's ddot computes it for n = 3: fma(a2, b2, fma(a1, b1, a0 * b0))
+__device__ __forceinline__ bool bl_normal_edge(const double *nrm, int i, int k, double t) {
+    const double *a = nrm + 3L * k, *b = nrm + 3L * i;
+    const double d = __fma_rn(a[2], b[2], __fma_rn(a[1], b[1], __dmul_rn(a[0], b[0])));
+    return d > t;
+}
+
+// abs(curvatures[k] - curvatures[i]) < t in float64
+__device__ __forceinline__ bool bl_curv_edge(const double *c, int i, int k, double t) { return fabs(__dsub_rn(c[k], c[i])) < t; }
+
+// numpy.sum((p[k,3:6] - p[i,3:6])**2) < t on float32 rows: squares rounded to float32, summed (d0 + d1) + d2, compared with
+// float32(t) (NumPy 2 casts the Python float to the array's dtype).  No contraction.
+__device__ __forceinline__ bool bl_color_edge(const float *pts, int ld, int i, int k, float t) {
+    const float *p = pts + (long)k * ld + 3, *q = pts + (long)i * ld + 3;
+    const float d0 = __fsub_rn(p[0], q[0]), d1 = __fsub_rn(p[1], q[1]), d2 = __fsub_rn(p[2], q[2]);
+    const float s = __fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2));
+    return s < t;
+}
+
+__device__ __forceinline__ bool bl_edge(const BlArgs &a, int i, int k) {
+    switch (a.mode) {
+    case BL_NORMAL: case BL_SMOOTHNESS: return bl_normal_edge(a.normals, i, k, a.t1);
+    case BL_CURVATURE: return bl_curv_edge(a.curv, i, k, a.t1);
+    case BL_COLOR: return bl_color_edge(a.pts, a.ld, i, k, (float)a.t1);
+    default:
+        return bl_normal_edge(a.normals, i, k, a.t1) && bl_curv_edge(a.curv, i, k, a.t2) &&
+               bl_color_edge(a.pts, a.ld, i, k, (float)a.t3);
+    }
+}
+
+__device__ __forceinline__ int bl_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// root of x with path halving (x's parent replaced by its grandparent by CAS: still an ancestor, still smaller)
+__device__ __forceinline__ int bl_find(int32_t *parent, int x) {
+    int p = bl_load(parent + x);
+    while (p != x) {
+        const int g = bl_load(parent + p);
+        if (g == p) return p;
+        int expect = p;
+        __hip_atomic_compare_exchange_strong(parent + x, &expect, g, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = p;
+        p = g;
+    }
+    return x;
+}
+
+__device__ __forceinline__ void bl_union(int32_t *parent, int x, int y) {
+    int rx = bl_find(parent, x), ry = bl_find(parent, y);
+    while (rx != ry) {
+        const int hi = rx > ry ? rx : ry, lo = rx > ry ? ry : rx;
+        int seen = hi;
+        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            return;
+        // hi was linked meanwhile: continue from the parent the CAS returned, not from a fresh load of parent[hi]
+        rx = bl_find(parent, seen);
+        ry = bl_find(parent, lo);
+    }
+}
+
+__global__ __launch_bounds__(BL_THREADS) void bl_init_kernel(BlArgs a) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < a.hslots) { a.keys[t] = LRG_HASH_EMPTY; a.vals[t] = -1; }
+    if (t < 64) a.scal[t] = 0;
+    if (t <= a.n) a.flag[t] = 0;
+    if (t >= a.n) return;
+    const int i = (int)t;
+    int lo = 0, hi = a.n_rooms - 1;                // the last r with room_start[r] <= i
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.room_start[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    a.room_of[i] = lo;
+    a.parent[i] = i;
+    a.size[i] = 0;
+    a.minkey[i] = ~0ULL;
+    a.ckey[i] = -1;
+    a.visited[i] = 0;
+}
+
+__device__ __forceinline__ uint64_t bl_key(const BlArgs &a, int i, int dx, int dy, int dz) {
+    const float *p = a.pts + (long)i * a.ld;
+    return lrg_pack_voxel(lrg_voxel_of(p[0], a.res) + dx, lrg_voxel_of(p[1], a.res) + dy, lrg_voxel_of(p[2], a.res) + dz);
+}
+
+__global__ __launch_bounds__(BL_THREADS) void bl_insert_kernel(BlArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const int r = a.room_of[i];
+    int s, e;
+    if (!bl_room(a, r, &s, &e)) return;
+    const uint64_t key = bl_key(a, i, 0, 0, 0);
+    if (key == LRG_HASH_EMPTY) { atomicOr(&a.scal[0], BL_ST_WINDOW); a.room_of[i] = -1; return; }
+    uint64_t *keys; int32_t *vals; int mask;
+    bl_segment(a, r, s, e, &keys, &vals, &mask);
+    unsigned h = (unsigned)lrg_fmix64(key) & (unsigned)mask;
+    for (int probe = 0; probe <= mask; ++probe) {
+        const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&keys[h]), (unsigned long long)LRG_HASH_EMPTY,
+                                                  (unsigned long long)key);
+        if (prev == LRG_HASH_EMPTY) { vals[h] = i; return; }
+        if (prev == key) { atomicOr(&a.scal[0], BL_ST_DUPLICATE); return; }      // the room is not equalised
+        h = (h + 1) & (unsigned)mask;
+    }
+}
+
+__global__ __launch_bounds__(BL_THREADS) void bl_union_kernel(BlArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const int r = a.room_of[i];
+    if (r < 0) return;
+    int s, e;
+    if (!bl_room(a, r, &s, &e)) return;
+    uint64_t *keys; int32_t *vals; int mask;
+    bl_segment(a, r, s, e, &keys, &vals, &mask);
+    const float *p = a.pts + (long)i * a.ld;
+    const int vx = lrg_voxel_of(p[0], a.res), vy = lrg_voxel_of(p[1], a.res), vz = lrg_voxel_of(p[2], a.res);
+    for (int dx = -1; dx <= 1; ++dx)
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dz = -1; dz <= 1; ++dz) {
+                if (!dx && !dy && !dz) continue;
+                const int k = lrg_hash_lookup(keys, vals, mask, lrg_pack_voxel(vx + dx, vy + dy, vz + dz));
+                if (k < 0 || k >= i) continue;
+                if (bl_edge(a, i, k)) bl_union(a.parent, i, k);
+            }
+}
+
+// every point's root (written back: the parents are final after the union launch), sizes, smoothness keys
+__global__ __launch_bounds__(BL_THREADS) void bl_count_kernel(BlArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n || a.room_of[i] < 0) return;
+    const int root = bl_find(a.parent, i);
+    __hip_atomic_store(a.parent + i, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // every parent is its root after this launch
+    atomicAdd(&a.size[root], 1);
+    if (a.mode == BL_SMOOTHNESS) {
+        const int s = a.room_start[a.room_of[i]], rk = a.rank[i];
+        if (rk < 0 || rk >= a.room_start[a.room_of[i] + 1] - s) { atomicOr(&a.scal[0], BL_ST_RANK); return; }
+        atomicMin(&a.minkey[root], ((unsigned long long)(unsigned)rk << 32) | (unsigned)(i - s));
+    }
+}
+
+// The reference's DFS (:384-405) from `seed`: LIFO stack, neighbours pushed in offset order when unvisited and on an edge,
+// visited marked at pop time.  Returns the pop count len(C), or -1 when the stack would overflow its reservation.
+__device__ int bl_replay(const BlArgs &a, int s, int e, int r, int seed, int32_t *stk, int cap) {
+    uint64_t *keys; int32_t *vals; int mask;
+    bl_segment(a, r, s, e, &keys, &vals, &mask);
+    int top = 0, pops = 0;
+    stk[top++] = seed;
+    while (top > 0) {
+        const int i = stk[--top];
+        ++pops;
+        a.visited[i] = 1;
+        const float *p = a.pts + (long)i * a.ld;
+        const int vx = lrg_voxel_of(p[0], a.res), vy = lrg_voxel_of(p[1], a.res), vz = lrg_voxel_of(p[2], a.res);
+        for (int dx = -1; dx <= 1; ++dx)
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dz = -1; dz <= 1; ++dz) {
+                    if (!dx && !dy && !dz) continue;
+                    const int k = lrg_hash_lookup(keys, vals, mask, lrg_pack_voxel(vx + dx, vy + dy, vz + dz));
+                    if (k < 0 || a.visited[k] || !bl_normal_edge(a.normals, i, k, a.t1)) continue;
+                    if (top >= cap) return -1;
+                    stk[top++] = k;
+                }
+    }
+    return pops;
+}
+
+__global__ __launch_bounds__(BL_THREADS) void bl_keep_kernel(BlArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const int r = a.room_of[i];
+    if (r < 0 || a.parent[i] != i) return;                  // one lane per component: its root
+    const int s = a.room_start[r], e = a.room_start[r + 1], c = a.size[i];
+    int key = i - s;
+    bool keep = c > a.mcs;
+    if (a.mode == BL_SMOOTHNESS) {
+        const unsigned long long mk = a.minkey[i];
+        if (mk == ~0ULL) return;                            // a rank was out of range (status set)
+        key = (int)(mk >> 32);
+        if (!keep && c >= 2) {
+            const int cap = 1 + 26 * c;
+            const long at = atomicAdd(&a.scal[1], cap);
+            if (at + cap > a.stack_cap) { atomicOr(&a.scal[0], BL_ST_STACK); return; }
+            const int pops = bl_replay(a, s, e, r, s + (int)(mk & 0xffffffffu), a.stack + at, cap);
+            if (pops < 0) { atomicOr(&a.scal[0], BL_ST_STACK); return; }
+            keep = pops > a.mcs;
+        }
+    }
+    a.ckey[i] = key;
+    if (keep) a.flag[s + key] = 1;
+}
+
+// ---- exclusive scan of flag[0 .. n] (n + 1 entries) into scan ----
+__device__ __forceinline__ int bl_block_exscan(int v, int *sh, int *total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int inc = lrg_wave_incl_scan_i32(v);
+    if (lane == 63) sh[w] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+    for (int k = 0; k < BL_THREADS / 64; ++k) {
+        if (k < w) base += sh[k];
+        tot += sh[k];
+    }
+    __syncthreads();
+    *total = tot;
+    return base + inc - v;
+}
+
+__global__ __launch_bounds__(BL_THREADS) void bl_scan_sums_kernel(const int32_t *x, long n, int32_t *bsum) {
+    __shared__ int sh[BL_THREADS / 64];
+    const long base = ((long)blockIdx.x * BL_THREADS + threadIdx.x) * BL_SCAN_ITEMS;
+    int s = 0;
+    for (int k = 0; k < BL_SCAN_ITEMS; ++k) s += base + k < n ? x[base + k] : 0;
+    int tot;
+    bl_block_exscan(s, sh, &tot);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(BL_THREADS) void bl_scan_top_kernel(int32_t *bsum, int nb) {
+    __shared__ int sh[BL_THREADS / 64];
+    int carry = 0;
+    for (int b0 = 0; b0 < nb; b0 += BL_THREADS) {
+        const int i = b0 + threadIdx.x;
+        const int v = i < nb ? bsum[i] : 0;
+        int tot;
+        const int ex = bl_block_exscan(v, sh, &tot);
+        if (i < nb) bsum[i] = carry + ex;
+        carry += tot;
+    }
+}
+
+__global__ __launch_bounds__(BL_THREADS) void bl_scan_apply_kernel(const int32_t *x, long n, const int32_t *bsum, int32_t *out) {
+    __shared__ int sh[BL_THREADS / 64];
+    const long base = ((long)blockIdx.x * BL_THREADS + threadIdx.x) * BL_SCAN_ITEMS;
+    int v[BL_SCAN_ITEMS], s = 0;
+    for (int k = 0; k < BL_SCAN_ITEMS; ++k) { v[k] = base + k < n ? x[base + k] : 0; s += v[k]; }
+    int tot;
+    int run = bsum[blockIdx.x] + bl_block_exscan(s, sh, &tot);
+    for (int k = 0; k < BL_SCAN_ITEMS; ++k) {
+        if (base + k < n) out[base + k] = run;
+        run += v[k];
+    }
+}
+
+__global__ __launch_bounds__(BL_THREADS) void bl_label_kernel(BlArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.n_rooms) {
+        int s, e;
+        a.n_clusters[i] = bl_room(a, i, &s, &e) ? a.scan[e] - a.scan[s] : 0;
+    }
+    if (i >= a.n) return;
+    const int r = a.room_of[i];
+    int lab = 0;
+    if (r >= 0) {
+        const int s = a.room_start[r], k = a.ckey[a.parent[i]];
+        if (k >= 0 && a.flag[s + k]) lab = a.scan[s + k] - a.scan[s] + 1;
+    }
+    a.labels[i] = lab;
+}
+
+extern "C" {
+
+size_t lrg_baseline_workspace_bytes(int n_points, int n_rooms, int min_cluster_size) {
+    LrgBaselineLayout L;
+    if (bl_layout(n_points, n_rooms, min_cluster_size, &L)) return 0;
+    return L.total;
+}
+
+int lrg_baseline_segment(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode,
+                         const double *normals, const double *curvatures, const int32_t *rank, double t1, double t2, double t3,
+                         int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream) {
+    LrgBaselineLayout L;
+    if (n_rooms < 1 || n_rooms > (1 << 20) || !room_start || room_start[0] != 0) return LRG_EINVAL - 73;
+    for (int r = 0; r < n_rooms; ++r)
+        if (room_start[r + 1] < room_start[r]) return LRG_EINVAL - 73;
+    const int n_points = room_start[n_rooms];
+    int rc = bl_layout(n_points, n_rooms, min_cluster_size, &L);
+    if (rc) return rc;
+    if (mode < BL_NORMAL || mode > BL_SMOOTHNESS) return LRG_EINVAL - 72;
+    if (!ws || !labels || !n_clusters) return LRG_EINVAL - 73;
+    if (n_points > 0 && (!pts || ld < 6)) return LRG_EINVAL - 73;
+    const bool need_n = mode == BL_NORMAL || mode == BL_FEATURE || mode == BL_SMOOTHNESS;
+    const bool need_c = mode == BL_CURVATURE || mode == BL_FEATURE;
+    if ((need_n && !normals) || (need_c && !curvatures) || (mode == BL_SMOOTHNESS && !rank)) return LRG_EINVAL - 74;
+    if (ws_bytes < L.total || ((uintptr_t)ws & 255)) return LRG_EINVAL - 75;
+    if (!(resolution > 0.f)) return LRG_EINVAL - 76;
+    hipStream_t st = (hipStream_t)stream;
+    char *w = static_cast<char *>(ws);
+    BlArgs a;
+    int32_t *rooms = reinterpret_cast<int32_t *>(w + L.rooms);     // a device copy of room_start (the caller's is host memory)
+    LRG_HIP_CHECK(hipMemcpyAsync(rooms, room_start, (size_t)(n_rooms + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    a.pts = pts; a.ld = ld; a.room_start = rooms; a.n_rooms = n_rooms; a.n = n_points; a.res = resolution; a.mode = mode;
+    a.normals = normals; a.curv = curvatures; a.rank = rank; a.t1 = t1; a.t2 = t2; a.t3 = t3; a.mcs = min_cluster_size;
+    a.keys = reinterpret_cast<uint64_t *>(w + L.keys); a.vals = reinterpret_cast<int32_t *>(w + L.vals);
+    a.room_of = reinterpret_cast<int32_t *>(w + L.room_of); a.parent = reinterpret_cast<int32_t *>(w + L.parent);
+    a.size = reinterpret_cast<int32_t *>(w + L.size); a.minkey = reinterpret_cast<unsigned long long *>(w + L.minkey);
+    a.ckey = reinterpret_cast<int32_t *>(w + L.ckey); a.visited = reinterpret_cast<int32_t *>(w + L.visited);
+    a.flag = reinterpret_cast<int32_t *>(w + L.flag); a.scan = reinterpret_cast<int32_t *>(w + L.scan);
+    a.bsum = reinterpret_cast<int32_t *>(w + L.bsum); a.stack = reinterpret_cast<int32_t *>(w + L.stack);
+    a.scal = reinterpret_cast<int32_t *>(w + L.scal); a.hslots = L.hslots; a.stack_cap = L.stack_cap;
+    a.labels = labels; a.n_clusters = n_clusters;
+    const long init_n = L.hslots > (long)n_points + 64 ? L.hslots : (long)n_points + 64;
+    const int gi = (int)((init_n + BL_THREADS - 1) / BL_THREADS);
+    const int gn = (int)(((long)(n_points > n_rooms ? n_points : n_rooms) + BL_THREADS - 1) / BL_THREADS);
+    hipLaunchKernelGGL(bl_init_kernel, dim3(gi), dim3(BL_THREADS), 0, st, a);
+    if (n_points > 0) {
+        hipLaunchKernelGGL(bl_insert_kernel, dim3(gn), dim3(BL_THREADS), 0, st, a);
+        hipLaunchKernelGGL(bl_union_kernel, dim3(gn), dim3(BL_THREADS), 0, st, a);
+        hipLaunchKernelGGL(bl_count_kernel, dim3(gn), dim3(BL_THREADS), 0, st, a);
+        hipLaunchKernelGGL(bl_keep_kernel, dim3(gn), dim3(BL_THREADS), 0, st, a);
+    }
+    const long nf = (long)n_points + 1;
+    hipLaunchKernelGGL(bl_scan_sums_kernel, dim3(L.nb), dim3(BL_THREADS), 0, st, a.flag, nf, a.bsum);
+    hipLaunchKernelGGL(bl_scan_top_kernel, dim3(1), dim3(BL_THREADS), 0, st, a.bsum, L.nb);
+    hipLaunchKernelGGL(bl_scan_apply_kernel, dim3(L.nb), dim3(BL_THREADS), 0, st, a.flag, nf, a.bsum, a.scan);
+    hipLaunchKernelGGL(bl_label_kernel, dim3(gn), dim3(BL_THREADS), 0, st, a);
+    LRG_LAUNCH_CHECK();
+    return 0;
+}
+
+int lrg_baseline_status(const void *ws, int n_points, int n_rooms, int min_cluster_size, int32_t *host_status, void *stream) {
+    LrgBaselineLayout L;
+    int rc = bl_layout(n_points, n_rooms, min_cluster_size, &L);
+    if (rc) return rc;
+    if (!ws || !host_status) return LRG_EINVAL - 73;
+    LRG_HIP_CHECK(hipMemcpyAsync(host_status, static_cast<const char *>(ws) + L.scal, sizeof(int32_t), hipMemcpyDeviceToHost,
+                                 (hipStream_t)stream));
+    LRG_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+}
+
+}  // extern "C"
