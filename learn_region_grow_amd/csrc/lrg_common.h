@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <limits.h>
 #include <math.h>
+#include <stdlib.h>
 #include "../../include/lrg_hip.h"
 
 #define LRG_HIP_CHECK(expr)                                 \
@@ -19,6 +20,12 @@
     } while (0)
 
 static inline size_t lrg_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Switches from the environment (A/B runs and test hooks): the variable's value as atoi / atof reads it, `dflt` while it is not set.
+// LRG_ENV_UNSET as `dflt`: a switch whose default is decided by the caller.
+#define LRG_ENV_UNSET INT_MIN
+static inline int lrg_env_int(const char *name, int dflt) { const char *s = getenv(name); return s ? atoi(s) : dflt; }
+static inline double lrg_env_real(const char *name, double dflt) { const char *s = getenv(name); return s ? atof(s) : dflt; }
 
 // Function attributes (dynamic-LDS cap) are per device: remember per device ordinal which kernels were raised.  A race
 // between host threads only repeats an idempotent call.

@@ -189,7 +189,7 @@ int lrg_fused_layer(const LrgFusedArgs &a, int nprob, hipStream_t st) {
         if (a.p[i].nlayers != 1 || !a.p[i].L[0].gout || (a.p[i].L[0].flags & (LRG_FL_KEEP | LRG_FL_INPLACE | LRG_FL_POOL)) || a.p[i].fw) return LRG_EINVAL - 30;
         K = a.p[i].Kin > K ? a.p[i].Kin : K;
     }
-    static const int v = getenv("LRG_LAYER_VARIANT") ? atoi(getenv("LRG_LAYER_VARIANT")) : 5;
+    static const int v = lrg_env_int("LRG_LAYER_VARIANT", 5);
     if (v >= 3) {
         const int ng = a.p[0].L[0].ng, N = a.p[0].L[0].N;
         bool same = true, aligned = true;

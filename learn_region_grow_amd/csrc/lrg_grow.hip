@@ -3,6 +3,8 @@
 // Reference: test_region_grow.py:175-316 (greedy) and test_random_restart.py:141-303 (restarts).
 // The reference runs ONE region of ONE room per step on the host; here S "slots" (region instances)
 // advance in lock-step, one workgroup per slot (or per slot group), all state device-resident.
+#include <atomic>
+#include <mutex>
 #include "lrg_common.h"
 #include "lrg_rng.h"
 #include "lrg_median.h"
@@ -1577,10 +1579,12 @@ static bool lrg_wave_branch_fits(const LrgWeights *w) {
 // the side stream and the two events of a wave-branch launch (per device; created once)
 // (a ring of event pairs: a launch's events are not recorded again while an earlier launch's waits on them may still be queued -- callers run a few launches ahead)
 #define LRG_SIDE_EVENTS 64
-struct LrgSideStream { hipStream_t stream; hipEvent_t start[LRG_SIDE_EVENTS], done[LRG_SIDE_EVENTS]; unsigned next; bool ok; };
+struct LrgSideStream { hipStream_t stream; hipEvent_t start[LRG_SIDE_EVENTS], done[LRG_SIDE_EVENTS]; std::atomic<unsigned> next; bool ok; };
 static LrgSideStream *lrg_side_stream() {
     static LrgSideStream side[LRG_MAX_DEVICES] = {};
+    static std::mutex init;                                  // (host threads that launch at once: one of them creates the stream and events, the others wait for it)
     LrgSideStream *s = &side[lrg_current_device()];
+    std::lock_guard<std::mutex> lock(init);
     if (!s->ok) {
         // HIP streams are mapped onto a few hardware queues (four per priority level), round robin by creation, and kernels of two streams that share a queue never run
         // side by side: with a side stream of the callers' own priority every fourth new caller stream landed on its queue -- the worker kernel waited out its 4 s for a
@@ -1607,8 +1611,49 @@ size_t lrg_grow_async_pool_rows_bytes(const LrgWeights *weights, int n_slots) {
     return (size_t)n_slots * 2 * 16 * (size_t)weights->conv_ch[weights->n_conv - 1] * sizeof(float);      // [slot][side][tile][columns of the pooled layer]
 }
 
-int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, const LrgGrowParams *params, const LrgWeights *weights,
-                   const LrgPackedBuffers *b, const LrgAsyncBuffers *ab, int max_steps, int budget_us, void *stream) {
+// The free-running launch's switches (A/B runs and test hooks; none changes a label), read from the environment on every call.
+// The shape of a launch that the Python host chooses -- front workgroups, teams, units, parts, CUs, fill-in workgroups, branch_waves -- is set in LrgAsyncBuffers.
+struct LrgAsyncSwitches {
+    int unit_pairs;              // LRG_ASYNC_UNIT_PAIRS: 0 / non-zero forces the units' half-teams off / on; unset: on from 84 slots
+    int gemv_batch;              // LRG_ASYNC_GEMV_BATCH: > 0 batched pooled products where they fit (a launch without units); -1: off
+    double gemv_batch_us;        // LRG_ASYNC_GEMV_BATCH_US: how long a batch waits for more slots, in us; 1.5
+    int tail_heads;              // LRG_ASYNC_TAIL_HEADS: 0 = a head tile of the slot's own per tail; 1: the heads of the tails on the shared tiles too
+    int rt_bb_every;             // LRG_ASYNC_RT_BB_EVERY: every so-manyth register-tile CU runs branch tiles on both teams (0: none); unset: 4 from 120 slots, else 0
+    int wave_fronts;             // LRG_ASYNC_WAVE_FRONTS: > 0 front workgroups of a two-kernel launch; 0: as many as the shader engines they claim have room for
+    int wave_extra_wgs;          // LRG_ASYNC_WAVE_EXTRA_WGS: (test hook) worker workgroups beyond what the shader engines hold; 0
+    int wave_wgs;                // LRG_ASYNC_WAVE_WGS: > 0 wave-branch CUs; 0: 62 % (with units) | 55 % of the worker CUs
+    int wave_a_wgs;              // LRG_ASYNC_WAVE_A_WGS: > 0 PREFIX CUs among them; 0: a fifth
+    int wave_split;              // LRG_ASYNC_WAVE_SPLIT: 8 = a wave-branch tile as eight tasks; 0: four
+    int rt_team_heads;           // LRG_ASYNC_RT_TEAM_HEADS: non-zero = register branch tiles with team head tiles; 0
+    int fill_hybrid;             // LRG_ASYNC_FILL_HYBRID: 0 = a fourth team's fill-in team serves the fill-in ring only; 1: ring 1 too while no fill-in waits
+    int ring0_halves;            // LRG_ASYNC_RING0_HALVES: > 0 half-teams per worker workgroup on branch tiles, -1 = one ring; 0: 3 with three teams or more, else 2
+    int small_teams;             // LRG_ASYNC_SMALL_TEAMS: with four teams, 3 = three branch-only teams, 23 = 2 / 3 on even / odd workgroups; 0: two
+};
+
+static LrgAsyncSwitches async_switches() {
+    LrgAsyncSwitches s;
+    s.unit_pairs = lrg_env_int("LRG_ASYNC_UNIT_PAIRS", LRG_ENV_UNSET);
+    s.gemv_batch = lrg_env_int("LRG_ASYNC_GEMV_BATCH", -1);
+    s.gemv_batch_us = lrg_env_real("LRG_ASYNC_GEMV_BATCH_US", 1.5);
+    s.tail_heads = lrg_env_int("LRG_ASYNC_TAIL_HEADS", 1);
+    s.rt_bb_every = lrg_env_int("LRG_ASYNC_RT_BB_EVERY", LRG_ENV_UNSET);
+    s.wave_fronts = lrg_env_int("LRG_ASYNC_WAVE_FRONTS", 0);
+    s.wave_extra_wgs = lrg_env_int("LRG_ASYNC_WAVE_EXTRA_WGS", 0);
+    s.wave_wgs = lrg_env_int("LRG_ASYNC_WAVE_WGS", 0);
+    s.wave_a_wgs = lrg_env_int("LRG_ASYNC_WAVE_A_WGS", 0);
+    s.wave_split = lrg_env_int("LRG_ASYNC_WAVE_SPLIT", 0);
+    s.rt_team_heads = lrg_env_int("LRG_ASYNC_RT_TEAM_HEADS", 0);
+    s.fill_hybrid = lrg_env_int("LRG_ASYNC_FILL_HYBRID", 1);
+    s.ring0_halves = lrg_env_int("LRG_ASYNC_RING0_HALVES", 0);
+    s.small_teams = lrg_env_int("LRG_ASYNC_SMALL_TEAMS", 0);
+    return s;
+}
+
+static int async_row_stride(const LrgGrowParams *params) { return (max(params->n_inlier, params->n_neighbor) + 31) / 32 * 32; }
+
+// The tests that need nothing but the arguments (the codes of those that need derived values are returned by async_plan)
+static int async_check(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, const LrgGrowParams *params, const LrgWeights *weights,
+                       const LrgPackedBuffers *b, const LrgAsyncBuffers *ab, int max_steps, int budget_us) {
     int rc = check_params(params);
     if (rc) return rc;
     if (!slots || !rooms || !weights || !b || !ab || n_slots <= 0 || max_points <= 0 || max_steps < 1 || budget_us < 0) return LRG_EINVAL - 1;
@@ -1617,14 +1662,51 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
     if (!b->center || !b->sample_in || !b->sample_nb || !b->x_in || !b->x_nb || !b->row_slot_in || !b->row_slot_nb || !b->upd_in ||
         !b->upd_nb || !b->rmv_logits || !b->add_logits || !b->slot_rows || !b->counters || !b->workspace || !ab->queue || !ab->sync)
         return LRG_EINVAL - 4;
-    const int row_stride = (max(params->n_inlier, params->n_neighbor) + 31) / 32 * 32;
-    if (b->row_cap % LRG_ROW_TILE != 0 || (long)b->row_cap < (long)n_slots * row_stride) return LRG_EINVAL - 5;
-    const size_t qbytes = lrg_grow_async_queue_bytes(n_slots);
-    if (ab->queue_bytes < qbytes || ((uintptr_t)ab->queue & 255) || n_slots >= (1 << 20)) return LRG_EINVAL - 6;
+    if (b->row_cap % LRG_ROW_TILE != 0 || (long)b->row_cap < (long)n_slots * async_row_stride(params)) return LRG_EINVAL - 5;
+    if (ab->queue_bytes < lrg_grow_async_queue_bytes(n_slots) || ((uintptr_t)ab->queue & 255) || n_slots >= (1 << 20)) return LRG_EINVAL - 6;
+    return 0;
+}
+
+// Whether this launch takes register tiles (a two-kernel launch) is previewed here and decided later, and the two tests do not agree today (making them agree
+// changes launches: left to a change of its own).
+// async_reg_candidate: asked before the pooled-product units are decided, so that register-tile launches keep their units up to LRG_REG_TILE_AUTO_MAX slots.
+// It looks at what was ASKED for: want == 1 (or 0 inside the automatic range), LrgAsyncBuffers.rows16, no shared tail tiles, no pool rows, the paper's network,
+// the whole chip.
+static bool async_reg_candidate(int want, int n_slots, const LrgAsyncBuffers *ab, const LrgWeights *weights, bool tails_on, int cus) {
+    return (want == 1 || (want == 0 && n_slots >= LRG_REG_TILE_AUTO_MIN && n_slots <= LRG_REG_TILE_AUTO_MAX)) && ab->rows16 && !tails_on && !ab->pool_rows &&
+           lrg_wave_branch_fits(weights) && !(ab->compute_units > 0 && ab->compute_units < cus);
+}
+// async_two_kernels_fit: whether a two-kernel launch (register tiles or wave-branch tasks) can be made, asked once the rest of the launch is decided.  Unlike the
+// preview it looks at what was GRANTED -- rows at a 64-byte stride (which also needs 9 .. 16 features and aligned rows), no shared tail tiles, no pool rows, no
+// batched pooled products -- and further at the branch problem's layers, a chip of whole shader engines (a multiple of 32, at least 64 CUs) and n_slots < 2^20;
+// it does not look at `want`.
+static bool async_two_kernels_fit(const LrgAsyncArgs &A, const LrgAsyncBuffers *ab, const LrgWeights *weights, int n_slots, int wgs, int cus) {
+    return A.front.rows16 && !A.tail && !A.pool_rows && !A.gemv_batch && lrg_wave_branch_fits(weights) &&      // (batched pooled products: tasks of the one-kernel launch's teams)
+           A.prob[0].nlayers == 5 && A.prob[0].L[1].gout && A.prob[0].pool &&
+           (ab->compute_units <= 0 || ab->compute_units >= cus) && (wgs % 32) == 0 && wgs >= 64 && n_slots < (1 << 20);
+}
+
+// A free-running launch as async_plan decides it and async_launch carries it out
+struct LrgAsyncPlan {
+    LrgAsyncKArgs K;             // the front kernel's arguments (the worker kernel's: the same but for worker_base)
+    bool two_kernels;            // the worker kernel on the side stream beside the front kernel
+    int front_wgs;               // workgroups of the front kernel (the one-kernel launch: every CU it may use)
+    int worker_wgs;              // workgroups of the worker kernel
+    size_t lds, worker_lds;      // the two kernels' dynamic LDS
+    int need_cus;                // the CUs the caller's stream must be allowed
+    size_t tail_ctl_bytes;       // the shared tail tiles' control words, zeroed before the launch (0: no shared tail tiles)
+};
+
+// The launch's shape from the checked arguments, the device's CU count and the switches: no HIP call, no state
+static int async_plan(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, const LrgGrowParams *params, const LrgWeights *weights,
+                      const LrgPackedBuffers *b, const LrgAsyncBuffers *ab, int max_steps, int budget_us, int cus, const LrgAsyncSwitches &sw,
+                      LrgAsyncPlan *plan) {
+    int rc;
+    const int row_stride = async_row_stride(params);
     size_t poff = 0, pcnt = 0;
     if ((rc = lrg_forward_packed_pooled_view(weights, n_slots, b->row_cap, &poff, &pcnt))) return rc;
 
-    LrgAsyncKArgs K;
+    LrgAsyncKArgs &K = plan->K;
     K.slots = slots; K.rooms = rooms; K.prm = *params;
     LrgAsyncArgs &A = K.A;
     LrgFusedArgs branches, heads;
@@ -1664,9 +1746,7 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
     }
     a.phase_dbg = ab->debug_ticks ? reinterpret_cast<unsigned long long *>(ab->debug_ticks) + 20 : nullptr;
 
-    hipDeviceProp_t prop;
-    LRG_HIP_CHECK(hipGetDeviceProperties(&prop, lrg_current_device()));
-    int wgs = prop.multiProcessorCount;
+    int wgs = cus;
     if (ab->compute_units > 0 && ab->compute_units < wgs) wgs = ab->compute_units;
     // Front workgroups: one per two slots (a front step takes ~23 us of a ~85 us step, and a CU a front workgroup holds is a CU without
     // tile teams: 68 slots, two teams: 34 / 40 / 46 / 68 front workgroups 806 / 810 / 807 / 792 k instance-steps/s, profiles/r03_units_sweep.log);
@@ -1702,10 +1782,7 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
         int units = (g.C % LRG_GEMV_UNIT_COLS == 0) ? 2 * g.C / LRG_GEMV_UNIT_COLS : 0;
         // (register-tile launches keep the units up to their last slot count: 160 slots with units and every fourth worker CU on two branch teams 1.26 M against 1.20 M
         //  instance-steps/s for the one-kernel launch without units, profiles/r06_reg_tiles_slots.txt)
-        static const int wave_env0 = getenv("LRG_ASYNC_WAVES") ? atoi(getenv("LRG_ASYNC_WAVES")) : 0;
-        const int want0 = wave_env0 ? wave_env0 : ab->branch_waves;
-        const bool reg_candidate = (want0 == 1 || (want0 == 0 && n_slots >= LRG_REG_TILE_AUTO_MIN && n_slots <= LRG_REG_TILE_AUTO_MAX)) && ab->rows16 && !tails_on && !ab->pool_rows &&
-                                   lrg_wave_branch_fits(weights) && !(ab->compute_units > 0 && ab->compute_units < prop.multiProcessorCount);
+        const bool reg_candidate = async_reg_candidate(ab->branch_waves, n_slots, ab, weights, tails_on, cus);
         if (ab->gemv_units < 0 || (ab->gemv_units == 0 && n_slots > (reg_candidate ? LRG_REG_TILE_AUTO_MAX : 148)) || (size_t)max((int)LRG_GEMV_UNIT_FLOATS(g.P), (int)LRG_GEMV_UNIT2_FLOATS(g.P)) * sizeof(float) + 16 > 160 * 1024 || n_slots > LRG_GEMV_UNIT_MAX_SLOTS || (((uintptr_t)g.pooled) & 15) || (g.P & 127) ||
             n_front + units > wgs / 2 + wgs / 4 || n_slots >= (1 << 20))
             units = 0;
@@ -1713,11 +1790,10 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
         // (half-teams in the units, lrg_async_gemv_unit2: eight tasks in flight per unit, each a little longer.  68 / 100 / 136 slots with register tiles: 992 -> 975,
         //  1 147 -> 1 189, 1 156 -> 1 206 k instance-steps/s (profiles/r06_unit_pairs.txt): on from 84 slots, where the units' capacity is what a slot queues for;
         //  LRG_ASYNC_UNIT_PAIRS=0 / 1 forces)
-        A.unit_pairs = getenv("LRG_ASYNC_UNIT_PAIRS") ? (atoi(getenv("LRG_ASYNC_UNIT_PAIRS")) ? 1 : 0) : (units && n_slots >= 84 ? 1 : 0);
+        A.unit_pairs = sw.unit_pairs != LRG_ENV_UNSET ? (sw.unit_pairs ? 1 : 0) : (units && n_slots >= 84 ? 1 : 0);
         // without the units: the pooled products in batches (lrg_async.inl, LRG_GEMV_BATCH) where slots become ready faster than a batch's patience --
         // LRG_ASYNC_GEMV_BATCH=0 / =1: off / on whatever the slot count; LRG_ASYNC_GEMV_BATCH_US: the patience
-        const int batch_env = getenv("LRG_ASYNC_GEMV_BATCH") ? atoi(getenv("LRG_ASYNC_GEMV_BATCH")) : -1;
-        const int batch_us10 = getenv("LRG_ASYNC_GEMV_BATCH_US") ? (int)(10.0 * atof(getenv("LRG_ASYNC_GEMV_BATCH_US"))) : 15;
+        const int batch_us10 = (int)(10.0 * sw.gemv_batch_us);
         const bool fits = (size_t)(LRG_GEMV_BATCH * (g.P + 4)) <= (size_t)LRG_ASYNC_TILE_FLOATS && g.P == 1024 && (g.C & 31) == 0 && n_slots < LRG_GEMV_NOBODY;      // (half ranges of eight k-groups: the paper's 2 x 512 pooled features)
         // (2 176 room jobs, rooms/s without | with: 200 slots 771 | 731, 272: 873 | 800, 320: 888 | 850, 400: 880 | 896 -- a block takes 68 us for ~7.7 slots instead
         //  of 23 us for one, 35 instead of 93 team-us per evaluation, but the pooled stage of a slot's step grows from 71 to 108 us and below ~400 slots the launch is
@@ -1726,7 +1802,7 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
         // 544: 906 | 905 (profiles/r05_gemv_batch_v3_mfma_pipelined.txt, r05_tail_heads2.txt).  The block for one slot costs the tile teams' CU nothing but L2 latency
         // (its few FMAs run beside the other teams' MFMAs); the batch's block costs matrix-pipe time -- 32-row tiles for ~8 slots -- which is what the launch is short of.
         // Off unless asked for (LRG_ASYNC_GEMV_BATCH=1).
-        A.gemv_batch = (units == 0 && fits && batch_env > 0) ? LRG_GEMV_BATCH : 0;
+        A.gemv_batch = (units == 0 && fits && sw.gemv_batch > 0) ? LRG_GEMV_BATCH : 0;
         A.gemv_batch_ticks = (long long)batch_us10 * 10;
     }
     // With the units, a branch tile leaves its column maxima of the pooled layer as one row of 16-byte stores (pool_rows) and the units take
@@ -1745,6 +1821,7 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
     }
     // Shared tail tiles: the caller's row arrays continue behind the slots' own rows
     A.tail = nullptr; A.tail_tiles = 0; A.tail_ticks = 0; A.tail_heads = 0;
+    plan->tail_ctl_bytes = 0;
     a.tail_cur = nullptr; a.tail_base = nullptr; a.tail_rows = 0; a.tail_row0 = 0;
     if (ab->tail_ctl && ab->tail_rows > 0 && a.rows16 && !ab->pool_rows) {
         // (+ 32 rows: a slot's own head tile on its tail rows stages a full tile from the tail's first row, tail_heads == 0)
@@ -1757,8 +1834,8 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
         a.tail_base = ab->tail_ctl + 32 + 4 * (size_t)A.tail_tiles;
         // (the heads of the tails on the shared tiles too -- without the units, whose head tiles start before the pooled product is complete and wait inside;
         //  LRG_ASYNC_TAIL_HEADS=0: a head tile of the slot's own per tail)
-        A.tail_heads = (A.gemv_units == 0 && !(getenv("LRG_ASYNC_TAIL_HEADS") && atoi(getenv("LRG_ASYNC_TAIL_HEADS")) == 0)) ? 1 : 0;
-        LRG_HIP_CHECK(hipMemsetAsync(ab->tail_ctl, 0, (32 + 4 * (size_t)A.tail_tiles) * sizeof(int32_t), (hipStream_t)stream));
+        A.tail_heads = (A.gemv_units == 0 && sw.tail_heads != 0) ? 1 : 0;
+        plan->tail_ctl_bytes = (32 + 4 * (size_t)A.tail_tiles) * sizeof(int32_t);
     }
     A.pool_rows = nullptr; A.pool_rows_stride = 0;
     if (A.gemv_units && ab->pool_rows && row_stride <= 512 && n_slots <= 4096) {
@@ -1778,16 +1855,12 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
     // whole chip (the two grids are sized per shader engine: a CU-masked launch keeps the one-kernel form).
     A.wave_wgs = 0; A.wave_a_wgs = 0; A.wave_waves = 0; A.wave_split = 4; A.wave_fill = 0; A.wmask = (int)async_wave_ring_entries(n_slots) - 1; A.h3[0] = A.h3[1] = nullptr; A.reg_tiles = 0;
     // (every fourth register-tile CU with two branch teams from 120 slots: a slot's branch tiles queue for their teams there -- 68 slots -2.5 %, 100: +0.3 %, 136: +3.6 %, 160: +4.6 %)
-    A.rt_bb_every = getenv("LRG_ASYNC_RT_BB_EVERY") ? atoi(getenv("LRG_ASYNC_RT_BB_EVERY")) : (n_slots >= 120 ? 4 : 0);
+    A.rt_bb_every = sw.rt_bb_every != LRG_ENV_UNSET ? sw.rt_bb_every : (n_slots >= 120 ? 4 : 0);
     int worker_wgs = 0;                                      // workgroups of the worker kernel (wave-branch mode)
     {
-        static const int wave_env = getenv("LRG_ASYNC_WAVES") ? atoi(getenv("LRG_ASYNC_WAVES")) : 0;
-        int want = wave_env ? wave_env : ab->branch_waves;
+        int want = ab->branch_waves;
         if (want == 0 && n_slots >= LRG_REG_TILE_AUTO_MIN && n_slots <= LRG_REG_TILE_AUTO_MAX) want = 1;      // (register tiles where they win: include/lrg_hip.h)
-        const bool can = a.rows16 && !A.tail && !A.pool_rows && !A.gemv_batch && lrg_wave_branch_fits(weights) &&      // (batched pooled products: tasks of the one-kernel launch's teams)
-                         A.prob[0].nlayers == 5 && A.prob[0].L[1].gout && A.prob[0].pool &&
-                         (ab->compute_units <= 0 || ab->compute_units >= prop.multiProcessorCount) && (wgs % 32) == 0 && wgs >= 64 && n_slots < (1 << 20);
-        if (can && want > 0) {
+        if (async_two_kernels_fit(A, ab, weights, n_slots, wgs, cus) && want > 0) {
             // Both kernels' workgroups go round the 8 XCDs in turn, and inside an XCD round its 4 shader engines (8 CUs each) -- a workgroup whose engine has no CU
             // free WAITS for one instead of going elsewhere, and where a kernel's round starts depends on what was dispatched before.  So the grids are sized per
             // shader engine for ANY alignment of the two rounds: the front kernel's F = n_front + units workgroups put at most f = ceil(ceil(F / 8) / 4) on one
@@ -1796,36 +1869,32 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
             // tools/two_kernel_rendezvous.hip, profiles/r03_side_stream: "a kernel of another stream is only placed when EVERY shader engine has a CU to spare".)
             // Front workgroups are added while the engines they already claim have room and there are slots for them.
             const int engines = 32, per_engine = wgs / engines;
-            static const int fronts_env = getenv("LRG_ASYNC_WAVE_FRONTS") ? atoi(getenv("LRG_ASYNC_WAVE_FRONTS")) : 0;
-            if (ab->front_workgroups <= 0 && !a.spec_k && fronts_env > 0) n_front = min(fronts_env, n_slots);
+            if (ab->front_workgroups <= 0 && !a.spec_k && sw.wave_fronts > 0) n_front = min(sw.wave_fronts, n_slots);
             int f = ((n_front + A.gemv_units + 7) / 8 + 3) / 4;
-            if (ab->front_workgroups <= 0 && !a.spec_k && fronts_env <= 0) n_front = max(n_front, min(n_slots, engines * f - A.gemv_units));
+            if (ab->front_workgroups <= 0 && !a.spec_k && sw.wave_fronts <= 0) n_front = max(n_front, min(n_slots, engines * f - A.gemv_units));
             const int F = n_front + A.gemv_units;
             f = ((F + 7) / 8 + 3) / 4;
             worker_wgs = engines * (per_engine - f);
             // (test hook: that many worker workgroups MORE than the shader engines hold -- a launch that can never be resident as a whole: its front workgroups
             //  give up at the start rendezvous with reason 6, the workgroups that start after that find the abort word and leave;
             //  tests/test_gpu_free_run.py::test_wave_branch_launch_that_cannot_be_resident_gives_up_cleanly)
-            if (getenv("LRG_ASYNC_WAVE_EXTRA_WGS")) worker_wgs += max(0, atoi(getenv("LRG_ASYNC_WAVE_EXTRA_WGS")));
-            static const int wwgs_env = getenv("LRG_ASYNC_WAVE_WGS") ? atoi(getenv("LRG_ASYNC_WAVE_WGS")) : 0;
-            static const int awgs_env = getenv("LRG_ASYNC_WAVE_A_WGS") ? atoi(getenv("LRG_ASYNC_WAVE_A_WGS")) : 0;
-            static const int split_env = getenv("LRG_ASYNC_WAVE_SPLIT") ? atoi(getenv("LRG_ASYNC_WAVE_SPLIT")) : 0;
+            worker_wgs += max(0, sw.wave_extra_wgs);
             // (per evaluation ~7 tiles: PREFIX tasks ~7 x 10 us of one wavefront, POOL tasks ~28 x 9 us, four wavefronts to a CU; head tiles ~7 x 13-17 us of a team, two
             //  to a CU -- and the pooled blocks where there are no units: 62 % | 55 % of the worker CUs run branch tasks, a fifth of those the PREFIX tasks)
-            int wave_wgs = wwgs_env > 0 ? wwgs_env : worker_wgs * (A.gemv_units ? 62 : 55) / 100;
+            int wave_wgs = sw.wave_wgs > 0 ? sw.wave_wgs : worker_wgs * (A.gemv_units ? 62 : 55) / 100;
             wave_wgs = max(8, min(wave_wgs / 4 * 4, worker_wgs - 8));
-            int a_wgs = awgs_env > 0 ? awgs_env : (wave_wgs + 2) / 5;
+            int a_wgs = sw.wave_a_wgs > 0 ? sw.wave_a_wgs : (wave_wgs + 2) / 5;
             a_wgs = max(1, min(a_wgs, wave_wgs - 4));
             a_wgs += (wave_wgs - a_wgs) % 4;                 // (POOL CUs: a multiple of four -- the (side, half) kinds)
             size_t c3[2];
             if (want == 1) {
                 // REGISTER TILES (LrgAsyncBuffers.branch_waves = 1): every worker workgroup alike -- team 0 the branch tiles (four wavefronts per tile, activations in
                 // registers where that is free: lrg_team_branch_tile_reg), team 1 the pooled blocks and head tiles
-                if (worker_wgs >= 24) A.reg_tiles = (getenv("LRG_ASYNC_RT_TEAM_HEADS") && atoi(getenv("LRG_ASYNC_RT_TEAM_HEADS"))) ? 2 : 1;      // (2: register branch tiles, team head tiles)
+                if (worker_wgs >= 24) A.reg_tiles = sw.rt_team_heads ? 2 : 1;      // (2: register branch tiles, team head tiles)
             } else if (worker_wgs >= 24 && lrg_packed_conv3_view(weights, n_slots, b->row_cap, c3) == 0) {
                 A.wave_wgs = wave_wgs; A.wave_a_wgs = a_wgs;
                 A.wave_waves = want > 0 ? min(want, 8) : 4;
-                A.wave_split = split_env == 8 ? 8 : 4;
+                A.wave_split = sw.wave_split == 8 ? 8 : 4;
                 A.h3[0] = static_cast<float *>(b->workspace) + c3[0]; A.h3[1] = static_cast<float *>(b->workspace) + c3[1];
             }
         }
@@ -1842,11 +1911,10 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
     A.n_slots = n_slots; A.n_front = n_front; A.teams = two_kernels ? 2 : teams;
     A.worker_base = n_front + A.gemv_units; A.total_wgs = two_kernels ? n_front + A.gemv_units + worker_wgs : wgs;
     if (A.fill_list && A.reg_tiles) {
-        // both teams of a register-tile CU run tiles: the second team of the first fill_wgs of them serves the fill-in ring instead of ring 1 (LRG_ASYNC_RT_FILL_WGS / LrgAsyncBuffers.fill_wgs).
+        // both teams of a register-tile CU run tiles: the second team of the first fill_wgs of them serves the fill-in ring instead of ring 1 (LrgAsyncBuffers.fill_wgs).
         // Default 0: the host fills finished rooms in between launches -- 68 rooms in flight, 0 / 8 / 16 / 32 such workgroups: 931 / 892 / 918 / 920 k instance-steps/s
         // (profiles/r06_reg_tiles_sweep.txt): a head team less per CU costs more than the fill-ins between two launches
-        static const int rt_fill_env = getenv("LRG_ASYNC_RT_FILL_WGS") ? atoi(getenv("LRG_ASYNC_RT_FILL_WGS")) : -1;
-        const int want_fill = ab->fill_wgs > 0 ? ab->fill_wgs : rt_fill_env >= 0 ? rt_fill_env : 0;
+        const int want_fill = ab->fill_wgs > 0 ? ab->fill_wgs : 0;
         A.fill_wgs = min(want_fill, worker_wgs / 4);
         if (A.fill_wgs < 1) { A.fill_list = nullptr; a.fill_in_launch = 0; }
     } else if (A.fill_list && A.wave_wgs) {
@@ -1865,17 +1933,14 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
         if (A.fill_wgs < 1) { A.fill_list = nullptr; a.fill_in_launch = 0; }      // (too few workgroups: the host fills in)
         A.fill_extra = (A.fill_list && teams <= 3) ? 1 : 0;      // (a fourth team of 256 threads beside three tile teams; its LDS region is 16 KB)
         // four tile teams: the fill-in team is the CU's fourth tile team and serves ring 1 while no fill-in task waits (LRG_ASYNC_FILL_HYBRID=0: the fill-in ring only)
-        static const int hybrid_env = getenv("LRG_ASYNC_FILL_HYBRID") ? atoi(getenv("LRG_ASYNC_FILL_HYBRID")) : 1;
-        A.fill_hybrid = (A.fill_list && teams == 4 && hybrid_env) ? 1 : 0;
+        A.fill_hybrid = (A.fill_list && teams == 4 && sw.fill_hybrid) ? 1 : 0;
     }
     {
-        static const int r0_env = getenv("LRG_ASYNC_RING0_HALVES") ? atoi(getenv("LRG_ASYNC_RING0_HALVES")) : 0;
-        A.ring0_halves = r0_env > 0 ? r0_env : teams >= 3 ? 3 : 2;
-        A.head_ring = (teams > 1 && (r0_env >= 0 || teams == 4)) ? 1 : 0;      // (LRG_ASYNC_RING0_HALVES=-1: one ring)
+        A.ring0_halves = sw.ring0_halves > 0 ? sw.ring0_halves : teams >= 3 ? 3 : 2;
+        A.head_ring = (teams > 1 && (sw.ring0_halves >= 0 || teams == 4)) ? 1 : 0;      // (LRG_ASYNC_RING0_HALVES=-1: one ring)
         // four teams: 2 x (branch tile: 28 KB) + 2 x (head tile: 44.5 KB) = 145 KB of the CU's 160; the first two run branch tiles only
-        static const int small_env = getenv("LRG_ASYNC_SMALL_TEAMS") ? atoi(getenv("LRG_ASYNC_SMALL_TEAMS")) : 0;      // 2, 3, or 23 = 2 / 3 on even / odd workgroups
-        A.small_teams = teams == 4 ? (small_env == 3 ? 3 : 2) : 0;
-        A.small_alt = (teams == 4 && small_env == 23) ? 1 : 0;
+        A.small_teams = teams == 4 ? (sw.small_teams == 3 ? 3 : 2) : 0;
+        A.small_alt = (teams == 4 && sw.small_teams == 23) ? 1 : 0;
     }
     A.poll_sleep = ab->poll_sleep > 0 ? ab->poll_sleep : 1;
     // few slots, most teams idle: a branch tile as two tasks that share its pooled layer (tile 22.8 -> 18.4 us; eight 100 k-point scenes
@@ -1883,9 +1948,8 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
     A.branch_parts = ab->branch_parts > 0 ? (ab->branch_parts >= 4 ? 4 : ab->branch_parts >= 2 ? 2 : 1) : (n_slots <= 46 ? 2 : 1);      // (end of round 4, profiles/r04_teams_units_sweep.txt: 16 / 24 / 39 / 44 / 52 / 68 slots, 2 against 1 part: +8 / +6 / +2.3 / +1.5 / -2 / -17 %)
     if (A.wave_wgs) { A.branch_parts = A.wave_split; A.head_ring = 1; A.small_teams = 0; A.small_alt = 0; A.fill_extra = 0; }
     if (A.reg_tiles) {
-        // (a register branch tile as two tasks where CUs idle: LrgAsyncBuffers.branch_parts >= 2 / LRG_ASYNC_RT_PARTS, by default up to 24 slots)
-        static const int rt_parts_env = getenv("LRG_ASYNC_RT_PARTS") ? atoi(getenv("LRG_ASYNC_RT_PARTS")) : 0;
-        A.branch_parts = rt_parts_env > 0 ? (rt_parts_env >= 2 ? 2 : 1) : ab->branch_parts > 0 ? (ab->branch_parts >= 2 ? 2 : 1) : (n_slots <= 24 ? 2 : 1);
+        // (a register branch tile as two tasks where CUs idle: LrgAsyncBuffers.branch_parts >= 2, by default up to 24 slots)
+        A.branch_parts = ab->branch_parts > 0 ? (ab->branch_parts >= 2 ? 2 : 1) : (n_slots <= 24 ? 2 : 1);
         A.head_ring = 1; A.small_teams = 0; A.small_alt = 0; A.fill_extra = 0;
     }      // (a branch tile = its four quarters; ring 1 for everything else)
     A.max_steps = max_steps;
@@ -1893,9 +1957,6 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
     A.abort_ticks = (budget_us > 0 ? (long long)budget_us * 100 : 0) + 400000000LL;  // ... + 4 s without an end: something is broken
     A.start_ticks = ab->start_wait_us > 0 ? (long long)ab->start_wait_us * 100 : (budget_us > 0 ? (long long)budget_us * 100 : 0) + LRG_ASYNC_START_TICKS;
     static_assert(sizeof(LrgAsyncKArgs) <= 4096, "kernel arguments");
-    hipStream_t st = (hipStream_t)stream;
-    LRG_HIP_CHECK(hipMemsetAsync(ab->queue, 0, qbytes, st));
-    LRG_HIP_CHECK(hipMemsetAsync(ab->sync, 0, (size_t)n_slots * LRG_ASYNC_SYNC_WORDS * sizeof(int32_t), st));
     const size_t front_lds = ((sizeof(LrgFrontShared) + 15) & ~(size_t)15) + sizeof(LrgAsyncFrontCtl);
     // (small_alt: the odd workgroups have one small team more and one big team less -- the even ones' layout is the larger)
     const size_t team_lds = ((size_t)A.small_teams * LRG_ASYNC_SMALL_TEAM_FLOATS + (size_t)(teams - A.small_teams) * LRG_ASYNC_TEAM_FLOATS +
@@ -1903,11 +1964,24 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
     static_assert((3 * LRG_ASYNC_TEAM_FLOATS + LRG_ASYNC_FILL_TEAM_FLOATS) * sizeof(float) <= 160 * 1024, "three tile teams and a fill team per CU");
     static_assert((2 * LRG_ASYNC_SMALL_TEAM_FLOATS + 2 * LRG_ASYNC_TEAM_FLOATS) * sizeof(float) <= 160 * 1024, "four tile teams per CU");
     const size_t unit_lds = A.gemv_units ? (size_t)max((int)LRG_GEMV_UNIT_FLOATS(A.gemv.P), (int)LRG_GEMV_UNIT2_FLOATS(A.gemv.P)) * sizeof(float) + 16 : 0;
-    const size_t lds = (max(max(front_lds, two_kernels ? (size_t)0 : team_lds), unit_lds) + 15) & ~(size_t)15;
+    plan->lds = (max(max(front_lds, two_kernels ? (size_t)0 : team_lds), unit_lds) + 15) & ~(size_t)15;
     // (wave-branch mode, the worker kernel: a wave-branch CU's kernels + its fill-in team | two tile teams)
-    const size_t worker_lds = (max(max((size_t)(LRG_WB_FLOATS + LRG_ASYNC_FILL_TEAM_FLOATS), (size_t)2 * LRG_ASYNC_TEAM_FLOATS),
-                                   (size_t)(LRG_RT_WEIGHT_FLOATS + LRG_RT_TEAM0_FLOATS + max((int)LRG_ASYNC_TEAM_FLOATS, (int)LRG_RT_TEAM1_FLOATS))) * sizeof(float) + 15) & ~(size_t)15;
+    plan->worker_lds = (max(max((size_t)(LRG_WB_FLOATS + LRG_ASYNC_FILL_TEAM_FLOATS), (size_t)2 * LRG_ASYNC_TEAM_FLOATS),
+                            (size_t)(LRG_RT_WEIGHT_FLOATS + LRG_RT_TEAM0_FLOATS + max((int)LRG_ASYNC_TEAM_FLOATS, (int)LRG_RT_TEAM1_FLOATS))) * sizeof(float) + 15) & ~(size_t)15;
     static_assert((LRG_WB_FLOATS + LRG_ASYNC_FILL_TEAM_FLOATS) * sizeof(float) <= 160 * 1024, "a wave-branch CU: the kernels of its (side, quarter) and a fill-in team");
+    plan->two_kernels = two_kernels;
+    plan->front_wgs = two_kernels ? n_front + A.gemv_units : wgs;
+    plan->worker_wgs = worker_wgs;
+    plan->need_cus = two_kernels ? cus : wgs;                // (the two grids are sized for the whole chip)
+    return 0;
+}
+
+// The launch as planned: the memsets, the residency checks and the one or two kernels
+static int async_launch(const LrgAsyncPlan &plan, int cus, hipStream_t st) {
+    const LrgAsyncKArgs &K = plan.K;
+    if (plan.tail_ctl_bytes) LRG_HIP_CHECK(hipMemsetAsync(K.A.tail, 0, plan.tail_ctl_bytes, st));
+    LRG_HIP_CHECK(hipMemsetAsync(K.A.queue, 0, lrg_grow_async_queue_bytes(K.A.n_slots), st));
+    LRG_HIP_CHECK(hipMemsetAsync(K.A.sync, 0, (size_t)K.A.n_slots * LRG_ASYNC_SYNC_WORDS * sizeof(int32_t), st));
     static bool attr_done[LRG_MAX_DEVICES] = {};
     const int dev = lrg_current_device();
     if (!attr_done[dev]) {
@@ -1922,43 +1996,55 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
     // LRG_ASYNC_START_TICKS (lrg_async.inl: abort reason 6), not by the hand-overs' multi-second bounds.
     {
         int per_cu = 0;
-        LRG_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(lrg_grow_async_kernel), LRG_FRONT_THREADS, lds));
+        LRG_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(lrg_grow_async_kernel), LRG_FRONT_THREADS, plan.lds));
         if (per_cu < 1) return LRG_ERESIDENCY;
-        if (two_kernels) {
-            LRG_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(lrg_grow_async_worker_kernel), LRG_WORKER_THREADS, worker_lds));
+        if (plan.two_kernels) {
+            LRG_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(lrg_grow_async_worker_kernel), LRG_WORKER_THREADS, plan.worker_lds));
             if (per_cu < 1) return LRG_ERESIDENCY;
         }
         uint32_t cumask[32] = {};
-        const uint32_t words = (uint32_t)min(32, (prop.multiProcessorCount + 31) / 32);
+        const uint32_t words = (uint32_t)min(32, (cus + 31) / 32);
         if (hipExtStreamGetCUMask(st, words, cumask) == hipSuccess) {
             int visible = 0;
             for (uint32_t i = 0; i < words; ++i) visible += __builtin_popcount(cumask[i]);
-            if (visible > 0 && visible < (two_kernels ? prop.multiProcessorCount : wgs)) return LRG_ERESIDENCY;      // (no bit set: no mask reported)
+            if (visible > 0 && visible < plan.need_cus) return LRG_ERESIDENCY;      // (no bit set: no mask reported)
         } else {
             (void)hipGetLastError();
         }
     }
-    if (two_kernels) {
+    if (plan.two_kernels) {
         // Two kernels, resident together: the worker kernel on the side stream between two events of the caller's stream (it starts after everything the caller
         // enqueued before this call -- the memsets above included -- and the caller's stream goes on only when it has left), the front kernel on the caller's stream.
         LrgSideStream *side = lrg_side_stream();
         if (!side) return LRG_ERESIDENCY;
         LrgAsyncKArgs KW = K;
-        KW.A.worker_base = A.wave_wgs;                       // (the tile teams' workgroups are numbered from the first one behind the wave-branch CUs)
+        KW.A.worker_base = K.A.wave_wgs;                     // (the tile teams' workgroups are numbered from the first one behind the wave-branch CUs)
         const unsigned ev = side->next++ % LRG_SIDE_EVENTS;
         LRG_HIP_CHECK(hipEventRecord(side->start[ev], st));
         LRG_HIP_CHECK(hipStreamWaitEvent(side->stream, side->start[ev], 0));
-        hipLaunchKernelGGL(lrg_grow_async_worker_kernel, dim3(worker_wgs), dim3(LRG_WORKER_THREADS), worker_lds, side->stream, KW);
+        hipLaunchKernelGGL(lrg_grow_async_worker_kernel, dim3(plan.worker_wgs), dim3(LRG_WORKER_THREADS), plan.worker_lds, side->stream, KW);
         LRG_LAUNCH_CHECK();
         LRG_HIP_CHECK(hipEventRecord(side->done[ev], side->stream));
-        hipLaunchKernelGGL(lrg_grow_async_kernel, dim3(n_front + A.gemv_units), dim3(LRG_FRONT_THREADS), lds, st, K);
+        hipLaunchKernelGGL(lrg_grow_async_kernel, dim3(plan.front_wgs), dim3(LRG_FRONT_THREADS), plan.lds, st, K);
         LRG_LAUNCH_CHECK();
         LRG_HIP_CHECK(hipStreamWaitEvent(st, side->done[ev], 0));
         return 0;
     }
-    hipLaunchKernelGGL(lrg_grow_async_kernel, dim3(wgs), dim3(LRG_FRONT_THREADS), lds, st, K);
+    hipLaunchKernelGGL(lrg_grow_async_kernel, dim3(plan.front_wgs), dim3(LRG_FRONT_THREADS), plan.lds, st, K);
     LRG_LAUNCH_CHECK();
     return 0;
+}
+
+int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, const LrgGrowParams *params, const LrgWeights *weights,
+                   const LrgPackedBuffers *b, const LrgAsyncBuffers *ab, int max_steps, int budget_us, void *stream) {
+    int rc = async_check(slots, rooms, n_slots, max_points, params, weights, b, ab, max_steps, budget_us);
+    if (rc) return rc;
+    hipDeviceProp_t prop;
+    LRG_HIP_CHECK(hipGetDeviceProperties(&prop, lrg_current_device()));
+    LrgAsyncPlan plan;
+    if ((rc = async_plan(slots, rooms, n_slots, max_points, params, weights, b, ab, max_steps, budget_us, prop.multiProcessorCount, async_switches(), &plan)))
+        return rc;
+    return async_launch(plan, prop.multiProcessorCount, (hipStream_t)stream);
 }
 
 int lrg_beam_advance(LrgBeamGroup *groups, LrgSlot *slots, LrgRoom *rooms, int n_groups, int beam_width, int search_width,
@@ -2082,7 +2168,7 @@ int lrg_nn1_fill_batch(const LrgFillJob *jobs, int n_jobs, int F, void *workspac
         if (jobs[j].n < 0 || (jobs[j].n > 0 && (!jobs[j].points || !jobs[j].label_in || !jobs[j].label_out))) return LRG_EINVAL - 1;
     if (!workspace || workspace_bytes < lrg_nn1_fill_batch_workspace_bytes(jobs, n_jobs) || ((uintptr_t)workspace & 255)) return LRG_EINVAL - 2;
     hipStream_t st = (hipStream_t)stream;
-    static const bool generic = getenv("LRG_NN1_GENERIC") != nullptr;      // (A/B switch)
+    static const bool generic = lrg_env_int("LRG_NN1_GENERIC", LRG_ENV_UNSET) != LRG_ENV_UNSET;      // (A/B switch)
     for (int g = 0; g < n_jobs; g += LRG_FILL_BATCH) {
         LrgFillBatchArgs B = {};
         B.counts = static_cast<int32_t *>(workspace);
@@ -2105,8 +2191,8 @@ int lrg_nn1_fill_batch(const LrgFillJob *jobs, int n_jobs, int F, void *workspac
         // Query-block columns of the search grid: every column of a chunk's row stages that chunk again, and a workgroup's rounds (64 queries each) share its staging --
         // as few columns as still fill the chip (16 columns whatever the batch: 0.18 / 0.21 of the fp32 vector peak on the Area-5 set / 100 k-point scenes, 2: 0.23 / 0.27,
         // profiles/r04_fill_grid_ab.txt).  A lone small room keeps its 16.
-        static const int gx_env = getenv("LRG_NN1_GX") ? atoi(getenv("LRG_NN1_GX")) : 0;            // (A/B switches)
-        static const int wgs_env = getenv("LRG_NN1_WGS") ? atoi(getenv("LRG_NN1_WGS")) : 0;
+        static const int gx_env = lrg_env_int("LRG_NN1_GX", 0);            // (A/B switches)
+        static const int wgs_env = lrg_env_int("LRG_NN1_WGS", 0);
         long chunks = 0;
         for (int k = 0; k < nb; ++k) chunks += (B.n[k] + LRG_NN1_C - 1) / LRG_NN1_C;
         const int want = (int)(((wgs_env > 0 ? wgs_env : LRG_NN1_TARGET_WGS) + chunks - 1) / chunks);

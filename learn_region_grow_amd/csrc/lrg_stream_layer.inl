@@ -297,7 +297,7 @@ static int lrg_stream_layer_lds_launch(const LrgFusedArgs &a, int nprob, hipStre
     if (ncg & (ncg - 1)) return LRG_EINVAL - 33;
     for (b.cg_shift = 0; (1 << b.cg_shift) < ncg; ++b.cg_shift) {}
     b.K = a.p[0].Kin; b.N = a.p[0].L[0].N; b.relu = (a.p[0].L[0].flags & LRG_FL_RELU) != 0; b.nprob = nprob;
-    static const int dbg = getenv("LRG_STREAM_DBG") ? atoi(getenv("LRG_STREAM_DBG")) : 0;
+    static const int dbg = lrg_env_int("LRG_STREAM_DBG", 0);
     b.dbg = dbg;
     const size_t lds = (size_t)CT * NG * 1024;
     auto kern = lrg_stream_layer_lds_kernel<NG, CT, D, OCC, FIRST, W, RT>;
