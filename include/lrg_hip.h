@@ -702,6 +702,52 @@ int lrg_baseline_segment(const float *pts, int ld, const int32_t *room_start, in
  * 2 two points of one room in one voxel (the room is not equalised), 4 a rank outside [0, room size), 8 a replay stack
  * overflow (not reachable by the bound of DESIGN.md §3.8).  Labels are not valid when it is non-zero. */
 int lrg_baseline_status(const void *ws, int n_points, int n_rooms, int min_cluster_size, int32_t *host_status, void *stream);
+/* The edges of test_mcpnet.py:122-145 (MCPNet): emb[k].dot(emb[i]) > t on the 26-neighbour voxel graph, the dot a float64 sum of the
+ * exact products double(emb[k][d]) * double(emb[i][d]) taken in order d = 0, 1, ..., dim - 1 ((p0 + p1) + p2 ...: what OpenBLAS's ddot
+ * gives for n = 10).  emb [n, dim] float32 on the device, 1 <= dim <= 64.  Components of more than min_cluster_size
+ * points are numbered in networkx's order, as the non-smoothness modes of lrg_baseline_segment; same workspace, same status. */
+int lrg_baseline_segment_embedding(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const float *emb,
+                                   int dim, double t, int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels,
+                                   int32_t *n_clusters, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * MCPNet (test_mcpnet.py:71-120, learn_region_grow_util.py:191-225): candidate lists on 0.3 m cells, 50 neighbour rows per point,
+ * the embedding network.  extern "C"; int return; no entry point allocates.  DESIGN.md §3.9.
+ * ---------------------------------------------------------------------------------------------- */
+#define LRG_MCP_NEIGHBORS 50            /* num_neighbors (test_mcpnet.py:19)                                                  */
+#define LRG_MCP_RADIUS 0.3f             /* neighbor_radii (test_mcpnet.py:20): cells round(x / 0.3f) in float32, half to even   */
+#define LRG_MCP_HIDDEN 200
+#define LRG_MCP_EMBEDDING 10
+/* Workspace of lrg_mcp_candidates / lrg_mcp_neighbors: 0 when an argument is out of range (n_rooms >= 1). */
+size_t lrg_mcp_workspace_bytes(int n_points, int n_rooms);
+/* The candidate lists of a batch of centred, equalised rooms (test_mcpnet.py:75-104): the members of the 27 cells around a point's
+ * own cell, cells in itertools.product order (dz fastest), members in ascending index, the point included.  room_start as for
+ * lrg_baseline_segment (HOST memory); pts [n, ld] on the device; counts [n] int32: the candidate count of every point. */
+int lrg_mcp_candidates(const float *pts, int ld, const int32_t *room_start, int n_rooms, void *ws, size_t ws_bytes, int32_t *counts,
+                       void *stream);
+/* nbr [n, 50] int32 (global point indices) from the workspace lrg_mcp_candidates left, same pts and room_start
+ * (test_mcpnet.py:104, numpy.random.choice(neighbors, 50, replace=len(neighbors) < 50)):
+ *   positions != NULL (legacy)  positions [n, 50] int32 on the device, each in [0, count): drawn on the host; mapped here
+ *   positions == NULL (counter) Philox4x32-10 keyed by (seed, room_ids[r]) (room_ids HOST memory), counter (j / 4, 0, point index in
+ *                               the room, LRG_PURPOSE_MCP_NEIGHBOR): count >= 50 the first 50 of a Feistel permutation of
+ *                               [0, count), else 50 independent (w * count) >> 32. */
+int lrg_mcp_neighbors(const float *pts, int ld, const int32_t *room_start, int n_rooms, void *ws, size_t ws_bytes,
+                      const int32_t *positions, uint32_t seed, const int32_t *room_ids, int32_t *nbr, void *stream);
+/* Error bits of the last lrg_mcp_candidates / lrg_mcp_neighbors on this workspace (synchronises the stream): 1 a cell outside the
+ * 21-bit window, 2 a legacy position outside [0, count). */
+int lrg_mcp_status(const void *ws, int n_points, int n_rooms, int32_t *host_status, void *stream);
+/* Floats of the packed weights lrg_mcp_embed reads. */
+size_t lrg_mcp_packed_floats(void);
+/* The eight mcp_* trainables (device, TF layouts: kernel1 [1,6,200], bias1 [200], kernel2 [1,200,200], bias2 [200], kernel3 [204,200],
+ * bias3 [200], kernel4 [200,10], bias4 [10]) -> packed [lrg_mcp_packed_floats()] in the operand order of lrg_mcp_embed. */
+int lrg_mcp_pack_weights(const float *k1, const float *b1, const float *k2, const float *b2, const float *k3, const float *b3,
+                         const float *k4, const float *b4, float *packed, void *stream);
+/* emb [n, 10] float32 (learn_region_grow_util.py:210-225) for pts [n, ld] (ld >= 6) and nbr [n, 50]: rows points[nbr] - points[i]
+ * (all six columns), relu(. K1 + b1), relu(. K2 + b2) on v_mfma_f32_32x32x2_f32, max over the 50 rows, concat(points[i, 2:6], .),
+ * relu(. K3 + b3), . K4 + b4, l2_normalize.  One launch.  *status (device int32) gets bit 1 when a neighbour index is outside
+ * [0, n) (that row then uses the point itself). */
+int lrg_mcp_embed(const float *pts, int ld, int n_points, const int32_t *nbr, const float *packed, float *emb, int32_t *status,
+                  void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training side: the pieces of the backward pass and of AdamOptimizer

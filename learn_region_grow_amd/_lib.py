@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
-           'lrg_baselines.hip']
+           'lrg_baselines.hip', 'lrg_mcpnet.hip']
 
 LRG_ABI_VERSION = 10      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
@@ -260,6 +260,15 @@ _SIGS = {
                                             ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, _fp, ctypes.c_size_t,
                                             _fp, _fp, _fp]),
     'lrg_baseline_status': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp]),
+    'lrg_baseline_segment_embedding': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_float, _fp, ctypes.c_int, ctypes.c_double,
+                                                      ctypes.c_int, _fp, ctypes.c_size_t, _fp, _fp, _fp]),
+    'lrg_mcp_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    'lrg_mcp_candidates': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, _fp, ctypes.c_size_t, _fp, _fp]),
+    'lrg_mcp_neighbors': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, _fp, ctypes.c_size_t, _fp, ctypes.c_uint32, _fp, _fp, _fp]),
+    'lrg_mcp_status': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp]),
+    'lrg_mcp_packed_floats': (ctypes.c_size_t, []),
+    'lrg_mcp_pack_weights': (ctypes.c_int, [_fp] * 10),
+    'lrg_mcp_embed': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _fp]),
     'lrg_gemm_f32': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int,
                                     _fp, ctypes.c_int, _fp, _fp, ctypes.c_int, _fp]),
     'lrg_ce_grad': (ctypes.c_int, [_fp, _fp, ctypes.c_long, ctypes.c_float, ctypes.c_float, _fp, _fp, _fp]),

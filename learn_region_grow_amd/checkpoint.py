@@ -423,3 +423,22 @@ def load_lrgnet_weights(prefix, feature_size=13, lite=0, verify=True):
         if entries[name].dtype != 1:
             raise BundleError('%s: not float32' % name)
     return load_bundle(prefix, names=list(shapes), verify=verify)
+
+
+MCPNET_SHAPES = {'mcp_kernel1': (1, 6, 200), 'mcp_bias1': (200,), 'mcp_kernel2': (1, 200, 200), 'mcp_bias2': (200,),
+                 'mcp_kernel3': (204, 200), 'mcp_bias3': (200,), 'mcp_kernel4': (200, 10), 'mcp_bias4': (10,)}
+"""name -> TF shape of MCPNet's eight trainables (learn_region_grow_util.py:197-204; feature 6, hidden 200, embedding 10)."""
+
+
+def load_mcpnet_weights(prefix, verify=True):
+    """The eight ``mcp_*`` trainables of an MCPNet checkpoint (Adam slots and step ignored), shapes and dtypes checked, every
+    tensor's bytes against its CRC-32C -- what ``saver.restore`` assigns at test_mcpnet.py:52."""
+    _, entries = read_bundle_index(prefix, verify=verify)
+    for name, shp in MCPNET_SHAPES.items():
+        if name not in entries:
+            raise KeyError('%s: variable %s missing (not an MCPNet checkpoint?)' % (prefix, name))
+        if tuple(entries[name].shape) != tuple(shp):
+            raise BundleError('%s: checkpoint has shape %s, MCPNet needs %s' % (name, entries[name].shape, shp))
+        if entries[name].dtype != 1:
+            raise BundleError('%s: not float32' % name)
+    return load_bundle(prefix, names=list(MCPNET_SHAPES), verify=verify)

@@ -26,7 +26,7 @@
 #define BL_THREADS 256
 #define BL_SCAN_ITEMS 8                       // per thread: 2048 elements per block
 
-enum { BL_NORMAL = 0, BL_CURVATURE = 1, BL_COLOR = 2, BL_FEATURE = 3, BL_SMOOTHNESS = 4 };
+enum { BL_NORMAL = 0, BL_CURVATURE = 1, BL_COLOR = 2, BL_FEATURE = 3, BL_SMOOTHNESS = 4, BL_EMBEDDING = 5 };   // 5: lrg_baseline_segment_embedding only
 // status bits (lrg_baseline_status)
 enum { BL_ST_WINDOW = 1, BL_ST_DUPLICATE = 2, BL_ST_RANK = 4, BL_ST_STACK = 8 };
 
@@ -72,6 +72,7 @@ struct BlArgs {
     const int32_t *room_start; int n_rooms, n;
     float res; int mode;
     const double *normals, *curv; const int32_t *rank;
+    const float *emb; int dim;
     double t1, t2, t3; int mcs;
     uint64_t *keys; int32_t *vals, *room_of, *parent, *size; unsigned long long *minkey;
     int32_t *ckey, *visited, *flag, *scan, *bsum, *stack, *scal;
@@ -114,11 +115,21 @@ __device__ __forceinline__ bool bl_color_edge(const float *pts, int ld, int i, i
     return s < t;
 }
 
+// emb[k].dot(emb[i]) > t (test_mcpnet.py:131): float64 copies of float32 values, so every product is exact; summed in order
+// ((p0 + p1) + p2) + ... as OpenBLAS's ddot does for n = 10.  Symmetric in i and k.
+__device__ __forceinline__ bool bl_embedding_edge(const float *emb, int dim, int i, int k, double t) {
+    const float *a = emb + (long)k * dim, *b = emb + (long)i * dim;
+    double d = __dmul_rn((double)a[0], (double)b[0]);
+    for (int c = 1; c < dim; ++c) d = __dadd_rn(d, __dmul_rn((double)a[c], (double)b[c]));
+    return d > t;
+}
+
 __device__ __forceinline__ bool bl_edge(const BlArgs &a, int i, int k) {
     switch (a.mode) {
     case BL_NORMAL: case BL_SMOOTHNESS: return bl_normal_edge(a.normals, i, k, a.t1);
     case BL_CURVATURE: return bl_curv_edge(a.curv, i, k, a.t1);
     case BL_COLOR: return bl_color_edge(a.pts, a.ld, i, k, (float)a.t1);
+    case BL_EMBEDDING: return bl_embedding_edge(a.emb, a.dim, i, k, a.t1);
     default:
         return bl_normal_edge(a.normals, i, k, a.t1) && bl_curv_edge(a.curv, i, k, a.t2) &&
                bl_color_edge(a.pts, a.ld, i, k, (float)a.t3);
@@ -361,9 +372,13 @@ size_t lrg_baseline_workspace_bytes(int n_points, int n_rooms, int min_cluster_s
     return L.total;
 }
 
-int lrg_baseline_segment(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode,
-                         const double *normals, const double *curvatures, const int32_t *rank, double t1, double t2, double t3,
-                         int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream) {
+}  // extern "C"
+
+// lrg_baseline_segment and lrg_baseline_segment_embedding: the same checks and the same nine launches
+static int bl_segment_impl(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode,
+                           const double *normals, const double *curvatures, const int32_t *rank, const float *emb, int dim, double t1,
+                           double t2, double t3, int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters,
+                           void *stream) {
     LrgBaselineLayout L;
     if (n_rooms < 1 || n_rooms > (1 << 20) || !room_start || room_start[0] != 0) return LRG_EINVAL - 73;
     for (int r = 0; r < n_rooms; ++r)
@@ -371,7 +386,8 @@ int lrg_baseline_segment(const float *pts, int ld, const int32_t *room_start, in
     const int n_points = room_start[n_rooms];
     int rc = bl_layout(n_points, n_rooms, min_cluster_size, &L);
     if (rc) return rc;
-    if (mode < BL_NORMAL || mode > BL_SMOOTHNESS) return LRG_EINVAL - 72;
+    if (mode < BL_NORMAL || mode > BL_EMBEDDING) return LRG_EINVAL - 72;
+    if (mode == BL_EMBEDDING && (!emb || dim < 1 || dim > 64)) return LRG_EINVAL - 74;
     if (!ws || !labels || !n_clusters) return LRG_EINVAL - 73;
     if (n_points > 0 && (!pts || ld < 6)) return LRG_EINVAL - 73;
     const bool need_n = mode == BL_NORMAL || mode == BL_FEATURE || mode == BL_SMOOTHNESS;
@@ -385,7 +401,7 @@ int lrg_baseline_segment(const float *pts, int ld, const int32_t *room_start, in
     int32_t *rooms = reinterpret_cast<int32_t *>(w + L.rooms);     // a device copy of room_start (the caller's is host memory)
     LRG_HIP_CHECK(hipMemcpyAsync(rooms, room_start, (size_t)(n_rooms + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
     a.pts = pts; a.ld = ld; a.room_start = rooms; a.n_rooms = n_rooms; a.n = n_points; a.res = resolution; a.mode = mode;
-    a.normals = normals; a.curv = curvatures; a.rank = rank; a.t1 = t1; a.t2 = t2; a.t3 = t3; a.mcs = min_cluster_size;
+    a.normals = normals; a.curv = curvatures; a.rank = rank; a.emb = emb; a.dim = dim; a.t1 = t1; a.t2 = t2; a.t3 = t3; a.mcs = min_cluster_size;
     a.keys = reinterpret_cast<uint64_t *>(w + L.keys); a.vals = reinterpret_cast<int32_t *>(w + L.vals);
     a.room_of = reinterpret_cast<int32_t *>(w + L.room_of); a.parent = reinterpret_cast<int32_t *>(w + L.parent);
     a.size = reinterpret_cast<int32_t *>(w + L.size); a.minkey = reinterpret_cast<unsigned long long *>(w + L.minkey);
@@ -411,6 +427,22 @@ int lrg_baseline_segment(const float *pts, int ld, const int32_t *room_start, in
     hipLaunchKernelGGL(bl_label_kernel, dim3(gn), dim3(BL_THREADS), 0, st, a);
     LRG_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" {
+
+int lrg_baseline_segment(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode,
+                         const double *normals, const double *curvatures, const int32_t *rank, double t1, double t2, double t3,
+                         int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream) {
+    return bl_segment_impl(pts, ld, room_start, n_rooms, resolution, mode == BL_EMBEDDING ? -1 : mode, normals, curvatures, rank, nullptr, 0, t1, t2, t3,
+                           min_cluster_size, ws, ws_bytes, labels, n_clusters, stream);
+}
+
+int lrg_baseline_segment_embedding(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const float *emb,
+                                   int dim, double t, int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels,
+                                   int32_t *n_clusters, void *stream) {
+    return bl_segment_impl(pts, ld, room_start, n_rooms, resolution, BL_EMBEDDING, nullptr, nullptr, nullptr, emb, dim, t, 0.0, 0.0,
+                           min_cluster_size, ws, ws_bytes, labels, n_clusters, stream);
 }
 
 int lrg_baseline_status(const void *ws, int n_points, int n_rooms, int min_cluster_size, int32_t *host_status, void *stream) {

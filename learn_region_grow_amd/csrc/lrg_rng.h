@@ -10,6 +10,7 @@
 #define LRG_PURPOSE_NEIGHBOR 1u
 #define LRG_PURPOSE_ADD 2u
 #define LRG_PURPOSE_RMV 3u
+#define LRG_PURPOSE_MCP_NEIGHBOR 4u      // MCPNet's 50 neighbour rows (lrg_mcpnet.hip), seed_point = the point's index in its room
 #define LRG_PURPOSE_PERMKEY 0x80u
 
 struct lrg_u32x4 { uint32_t x, y, z, w; };

@@ -64,3 +64,49 @@ def aggregate_line(ms):
     return 'NMI: %.2f+-%.2f AMI: %.2f+-%.2f ARS: %.2f+-%.2f PRC %.2f+-%.2f RCL %.2f+-%.2f IOU %.2f+-%.2f' % (
         a['nmi'].mean(), a['nmi'].std(), a['ami'].mean(), a['ami'].std(), a['ars'].mean(), a['ars'].std(),
         a['prc'].mean(), a['prc'].std(), a['rcl'].mean(), a['rcl'].std(), a['iou'].mean(), a['iou'].std())
+
+
+def room_metrics_set_order(obj_id, cluster_label, with_sklearn=True):
+    """The evaluation block of test_mcpnet.py:146-170, which differs from room_metrics: ground-truth instances are visited in
+    ``for i in set(obj_id)`` order (not largest first), a matched cluster is relabelled ``i`` (not its rank) and an unmatched one
+    ``j + obj_id.max()``.  Same keys as room_metrics, so room_line / aggregate_line apply."""
+    obj_id = np.asarray(obj_id)
+    cluster_label = np.asarray(cluster_label)
+    n_cluster = int(cluster_label.max()) if len(cluster_label) else 0
+    unique_id, inv, count = np.unique(obj_id, return_inverse=True, return_counts=True)
+    cont = np.zeros((len(unique_id), n_cluster + 1), dtype=np.int64)
+    np.add.at(cont, (inv.reshape(-1), cluster_label), 1)
+    csize = cont.sum(axis=0)
+    row = {v: g for g, v in enumerate(unique_id.tolist())}
+    dt_match = np.zeros(n_cluster, dtype=bool)                                                  # :149
+    cluster_label2 = np.zeros(len(cluster_label), dtype=int)
+    gt_match = 0
+    room_iou = []
+    ids = set(obj_id)                                                                           # :152, numpy scalars as the reference has them
+    for i in ids:
+        g = row[int(i)]
+        best_iou = 0
+        for j in range(1, n_cluster + 1):
+            if not dt_match[j - 1]:
+                inter = cont[g, j]
+                iou = 1.0 * inter / (count[g] + csize[j] - inter)                               # :156
+                best_iou = max(best_iou, iou)
+                if iou > 0.5:
+                    dt_match[j - 1] = True
+                    gt_match += 1
+                    cluster_label2[cluster_label == j] = i
+                    break
+        room_iou.append(best_iou)
+    for j in range(1, n_cluster + 1):                                                            # :164-166
+        if not dt_match[j - 1]:
+            cluster_label2[cluster_label == j] = j + obj_id.max()
+    out = dict(prc=float(np.mean(dt_match)) if n_cluster else float('nan'),                      # :167
+               rcl=1.0 * gt_match / len(ids),                                                    # :168
+               iou=float(np.mean(room_iou)),                                                     # :169
+               cluster_label2=cluster_label2)
+    if with_sklearn:
+        from sklearn.metrics import normalized_mutual_info_score, adjusted_rand_score, adjusted_mutual_info_score
+        out['nmi'] = normalized_mutual_info_score(obj_id, cluster_label)                         # :171
+        out['ami'] = adjusted_mutual_info_score(obj_id, cluster_label)
+        out['ars'] = adjusted_rand_score(obj_id, cluster_label)
+    return out
