@@ -1,10 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- region-grow throughput on synthetic S3DIS-Area-5-shaped rooms (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 With N > 1 and no torch.distributed environment the script starts its N ranks itself (torch.distributed.run, 127.0.0.1); a
 WORLD_SIZE that contradicts --gpus is an error.  Inputs (13-D room features, weights) are resident in HBM before any clock starts.
+
+A plain run is the steady leg alone: set-up, W warm-up steps, the K timed steps, --dump-outputs, the line (``value``, ``ms_per_step``,
+and the roofline of the timed launches from their own events and counters).  --full adds everything else the line can carry, each
+measured by work of its own: the fixed-work leg and its slot sweep, the lock-step forward and dense side launches of the roofline, the
+one-rank RCCL communicator of the label gather, ONE room on the chip, the steady leg at more rooms in flight and the named ScanNet /
+KITTI configurations (runs of this script of their own), the CPU oracle baseline and preprocessing (P0) rates.  Without --full
+``rooms_per_sec`` is the steady leg's (rooms finished per second), as with --fixed-rooms 0.
 
   steady leg (``value``, instance-steps/s).  The rooms of the Area-5-shaped set (BASELINE.json configs[1]), `--rooms` = 68 of them
       in flight; every in-flight room takes region-grow steps (box query, medians, sampling, one LrgNet evaluation on its 512 + 512
@@ -19,7 +26,7 @@ WORLD_SIZE that contradicts --gpus is an error.  Inputs (13-D room features, wei
       An instance-step is counted per slot and iteration of the loop, whatever the number of rows its LrgNet evaluation needed: the
       distinct rows of a 512 + 512 set are evaluated, the copies that pad it are not (``rows_evaluated_fraction``), so the unit is a
       PADDED-EQUIVALENT one -- the roofline object prices the rows that were evaluated, not 271.7 MFLOP per instance-step.
-  fixed-work leg (``rooms_per_sec``).  R = max(8 per geometry, 4 waves x 8 GPUs x slots per GPU) room jobs (2 176 at 68 slots: the 68
+  fixed-work leg (``rooms_per_sec``; --full).  R = max(8 per geometry, 4 waves x 8 GPUs x slots per GPU) room jobs (2 176 at 68 slots: the 68
       geometries x 32 random-stream keys) sharded over the N ranks by point count (longest first), pushed through
       `--rooms` slots per GPU from reset to final labels (grow + fill-in), the labels gathered over RCCL -- the only collective of
       the path.  Same R for every N (strong scaling): at N = 8 a rank still has four waves of rooms per slot (``waves_per_rank``), so
@@ -60,6 +67,10 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='besides the steady leg, every other measurement of the line: the roofline\'s side launches and the legs that '
+                         '--fixed-rooms, --best-slots, --steady-slots, --named-configs, --one-room-ks, --one-rank-collective, --cpu-seconds, '
+                         '--cpu-box-seconds and --p0-rooms set up (a plain run leaves them out)')
     ap.add_argument('--mode', default='auto', choices=['auto', 'free', 'lockstep'],
                     help='auto: free-running launches (lrg_grow_async) up to 96 greedy slots per GPU, lock-step iterations above')
     ap.add_argument('--step-ms', type=float, default=25.0, help='free-running launches: budget of one launch = one step')
@@ -200,6 +211,49 @@ def cpu_baseline(rooms, weights, seconds, policy, gpu_room_steps, box_seconds=0.
     return out
 
 
+def _single_threaded_pool(processes):
+    """A pool of spawned processes whose BLAS and OpenMP run one thread each (they read these variables when NumPy loads)."""
+    import multiprocessing as mp
+    saved = {k: os.environ.get(k) for k in ('OMP_NUM_THREADS', 'OPENBLAS_NUM_THREADS', 'MKL_NUM_THREADS')}
+    os.environ.update({k: '1' for k in saved})
+    try:
+        return mp.get_context('spawn').Pool(processes)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _area5_room(job):
+    i, seed_base, target, cache_dir = job
+    from learn_region_grow_amd import workloads
+    return workloads.area5_rooms(1, seed_base=seed_base + i, cache_dir=cache_dir, targets=[target])[0]
+
+
+def start_area5_rooms(n_rooms, seed_base, cache_dir, processes):
+    """workloads.area5_rooms(n_rooms, seed_base) generated by `processes` processes side by side, from now on; call the result for the
+    rooms.  Room i of the set is area5_rooms(1, seed_base + i, targets=[AREA5_POINTS[i % 68]]) -- the same arrays -- and is cached
+    under `cache_dir` by itself.  One process takes ~40 s for the 68 rooms: most of a plain run's set-up if nothing else helped."""
+    from learn_region_grow_amd import synthetic
+    targets = synthetic.AREA5_POINTS
+    jobs = sorted(range(n_rooms), key=lambda i: -targets[i % len(targets)])      # the largest rooms first: they bound the wall time
+    pool = _single_threaded_pool(max(1, min(processes, n_rooms)))
+    atexit.register(pool.terminate)      # (a run that ends before it takes the rooms)
+    pending = pool.map_async(_area5_room, [(i, seed_base, targets[i % len(targets)], cache_dir) for i in jobs], chunksize=1)
+
+    def rooms():
+        made = pending.get()
+        pool.terminate()
+        pool.join()
+        out = [None] * n_rooms
+        for i, room in zip(jobs, made):
+            out[i] = room
+        return out
+    return rooms
+
+
 def _cpu_pool_worker(job):
     room, weights, seconds, policy, key = job
     try:
@@ -215,7 +269,6 @@ def cpu_baseline_all_cores(rooms, weights, seconds, policy, gpu_room_steps):
     """The same oracle on MANY rooms at once, one single-threaded process per room (the rooms are independent, test_region_grow.py:110-183: what a
     user of the reference with a many-core host would do): rooms spread evenly over the set's size order, each grown for `seconds` (or to its end).
     value = all steps / the longest worker's time."""
-    import multiprocessing as mp
     cores = max(1, min(len(rooms), (os.cpu_count() or 2) - 2, 64))
     order = np.argsort([len(r['points']) for r in rooms])
     # ... and beside them the SMALLEST rooms of the set grown to the end and filled in (up to four windows each), so that rooms/s is also MEASURED on
@@ -227,18 +280,9 @@ def cpu_baseline_all_cores(rooms, weights, seconds, policy, gpu_room_steps):
     keep = ('points', 'obj_id', 'order')
     jobs = [({k: rooms[i][k] for k in keep}, weights, seconds, policy, 0) for i in picks]
     jobs += [({k: rooms[i][k] for k in keep}, weights, 4.0 * seconds, policy, 0) for i in small]
-    saved = {k: os.environ.get(k) for k in ('OMP_NUM_THREADS', 'OPENBLAS_NUM_THREADS', 'MKL_NUM_THREADS')}
-    os.environ.update({k: '1' for k in saved})                    # (the children are spawned: they read these when NumPy loads)
     t0 = time.time()
-    try:
-        with mp.get_context('spawn').Pool(workers + n_small) as pool:
-            res_all = pool.map(_cpu_pool_worker, jobs, chunksize=1)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+    with _single_threaded_pool(workers + n_small) as pool:
+        res_all = pool.map(_cpu_pool_worker, jobs, chunksize=1)
     wall = time.time() - t0
     res, res_small = res_all[:workers], res_all[workers:]
     steps = sum(r[0] for r in res)
@@ -460,6 +504,58 @@ class _Leg:
             g._release_graph()
 
 
+def dense_side_launches(net, weights, S, dev):
+    """roofline.dense (--full): the dense evaluation (all 512 + 512 rows of S instances): the formulation SURVEY.md 8d prices, a side launch
+    outside the timed loop."""
+    import torch
+    reps = 10
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    rs = np.random.RandomState(0)
+    d_inl = torch.from_numpy((rs.randn(S, 512, 13) * 0.5).astype(np.float32)).to(dev)
+    d_nbr = torch.from_numpy((rs.randn(S, 512, 13) * 0.5).astype(np.float32)).to(dev)
+    net.forward(d_inl, d_nbr)
+    torch.cuda.synchronize()
+    ev0.record()
+    for _ in range(reps):
+        net.forward(d_inl, d_nbr)
+    ev1.record()
+    torch.cuda.synchronize()
+    fwd_ms = ev0.elapsed_time(ev1) / reps
+    dflops = S * FLOPS_PER_INSTANCE_STEP
+    dense = {'note': 'side launch, NOT in the timed loop: lrg_forward on all 512 + 512 rows of %d instances' % S,
+             'achieved': dflops / (fwd_ms * 1e-3) / 1e12, 'frac': dflops / (fwd_ms * 1e-3) / 1e12 / FP32_MATRIX_PEAK_TFLOPS,
+             'ms_per_launch': fwd_ms, 'algorithmic_flops': dflops,
+             'hbm_accounting': {'note': 'SURVEY.md 8d layer-streamed accounting (what an unfused implementation would stream); the fused kernels '
+                                        'keep activations in LDS, so this is NOT traffic', 'bytes_per_instance': BYTES_PER_INSTANCE_STEP,
+                                'GBps': S * BYTES_PER_INSTANCE_STEP / (fwd_ms * 1e-3) / 1e9,
+                                'frac_of_hbm_peak': S * BYTES_PER_INSTANCE_STEP / (fwd_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}}
+    # north_star's MLP metric: the SAME evaluation run layer by layer, every activation through HBM (LRG_FWD_STREAM_TILES: csrc/lrg_stream_layer.inl), a side launch
+    # at 1 088 instances, priced with the algorithmic bytes of SURVEY.md 8d (the counters' figure: profiles/r05_traffic_streamed_tiles.json)
+    try:
+        from learn_region_grow_amd.lrgnet import LrgNetHIP
+        Sb = 1088
+        snet = LrgNetHIP(1, 1, 512, 512, 13, 0, device=dev, mode='streamed-tiles').load_weights(weights)
+        s_inl = torch.from_numpy((rs.randn(Sb, 512, 13) * 0.5).astype(np.float32)).to(dev)
+        s_nbr = torch.from_numpy((rs.randn(Sb, 512, 13) * 0.5).astype(np.float32)).to(dev)
+        snet.forward(s_inl, s_nbr)
+        torch.cuda.synchronize()
+        ev0.record()
+        for _ in range(reps):
+            snet.forward(s_inl, s_nbr)
+        ev1.record()
+        torch.cuda.synchronize()
+        s_ms = ev0.elapsed_time(ev1) / reps
+        dense['layer_streamed'] = {'note': 'side launch, NOT in the timed loop: one launch per layer, activations through HBM (mode streamed-tiles), %d instances' % Sb,
+                                   'ms_per_evaluation': s_ms, 'algorithmic_bytes': Sb * BYTES_PER_INSTANCE_STEP,
+                                   'GBps': Sb * BYTES_PER_INSTANCE_STEP / (s_ms * 1e-3) / 1e9,
+                                   'frac_of_hbm_peak': Sb * BYTES_PER_INSTANCE_STEP / (s_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                   'counters': 'profiles/r05_traffic_streamed_tiles.json (FETCH_SIZE + WRITE_SIZE: 12.16 GB in 3.41 ms under the profiler = 0.446)'}
+        del snet, s_inl, s_nbr
+    except Exception as e:       # (a side figure: never the reason the line is missing)
+        dense['layer_streamed'] = {'error': repr(e)}
+    return dense
+
+
 DUMP_BYTES_MAX = 64 * 1024 * 1024
 
 
@@ -542,17 +638,21 @@ def main():
     sys.stdout.flush()
     json_fd = os.dup(1)
     os.dup2(2, 1)
-    import torch
-    import torch.distributed as dist
-    from learn_region_grow_amd import _lib, synthetic, workloads, dist as lrg_dist
-    from learn_region_grow_amd.lrgnet import LrgNetHIP, _ptr
-
     rank = int(os.environ.get('RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if world != args.gpus:
         raise SystemExit('bench.py: --gpus %d but WORLD_SIZE=%d (launch with --nproc-per-node %d, or without a torch.distributed environment)'
                          % (args.gpus, world, args.gpus))
+    # the Area-5 set is generated on the host while torch and the device come up: at most 16 processes per run, shared by its ranks (the
+    # set's largest room is 1/18 of its points: more would not finish it sooner)
+    area5_ready = start_area5_rooms(min(args.rooms, 68), 1000, args.cache, min(16, len(os.sched_getaffinity(0))) // world) \
+        if args.workload == 'area5' else None
+    import torch
+    import torch.distributed as dist
+    from learn_region_grow_amd import _lib, synthetic, workloads, dist as lrg_dist
+    from learn_region_grow_amd.lrgnet import LrgNetHIP, _ptr
+
     if not torch.cuda.is_available():
         raise SystemExit('bench.py needs a GPU (the HIP path has no CPU fallback)')
     # LRG_BENCH_ONE_DEVICE=1 (testing on a 1-GPU box): every rank uses cuda:0 and the collectives go over gloo
@@ -575,7 +675,7 @@ def main():
         backend = dist.get_backend()
     force_coll = False
     collective_error = None
-    if world == 1 and args.one_rank_collective and not dist.is_initialized():
+    if world == 1 and args.full and args.one_rank_collective and not dist.is_initialized():
         # One GPU: the exchange of the N > 1 path (learn_region_grow_amd/dist.py: all_gather of the label buffers, all_reduce of the counts) still
         # runs, over a one-rank RCCL communicator -- so that the code an 8-GPU run takes has executed on the device in every record of this
         # script.  Nothing depends on it: if RCCL cannot be brought up the single-rank short cut is taken and the line says why.
@@ -600,7 +700,7 @@ def main():
     elif args.workload == 'scannet':
         base = workloads.scannet_rooms(min(args.rooms, 39), seed_base=7000, cache_dir=args.cache)
     else:
-        base = workloads.area5_rooms(min(args.rooms, 68), seed_base=1000, cache_dir=args.cache)
+        base = area5_ready()
     slots = min(args.rooms, 8) if args.workload == 'kitti' else args.rooms
     if args.speculate < 0:
         from learn_region_grow_amd.grow import auto_speculate
@@ -751,8 +851,10 @@ def main():
                      'speculation': ({'depth': args.speculate, 'regions_voided': dw[4], 'evaluations_voided': dw[5], 'steps_voided': dw[6],
                                       'note': 'algorithmic_flops_in_loop counts every evaluation executed, voided ones included (work done, not work kept); '
                                               '`value` counts kept steps only'} if args.speculate > 1 else None),
-                     'reproduce': 'rocprofv3 --kernel-trace --stats -- python bench.py --gpus 1 --steps %d --warmup %d  (profiles/r06_bench_kernel_stats.csv)'
+                     'reproduce': 'rocprofv3 --kernel-trace --stats -- python bench.py --gpus 1 --steps %d --warmup %d --full  (profiles/r06_bench_kernel_stats.csv)'
                                   % (args.steps, args.warmup)})
+    elif not args.full:
+        roof['note'] = 'lock-step iterations: the packed forward is timed by launches of its own, with --full'
     else:
         reps = 20
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -790,52 +892,8 @@ def main():
                      'flops_per_launch': flops, 'avg_us': 1e3 * loop_ms, 'packed_rows': [int(rows[0]), int(rows[1])],
                      'rows_evaluated_fraction': float(rows.sum()) / (max(act, 1) * 1024.0), 'slots_evaluated': int(act),
                      'flops_definition': 'distinct rows evaluated x (165 504 + 98 816 FLOP per row) + active slots x 1 048 576'})
-    # the dense evaluation (all 512 + 512 rows of S instances): the formulation SURVEY.md 8d prices, a side launch outside the timed loop
-    reps = 10
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    rs = np.random.RandomState(0)
-    d_inl = torch.from_numpy((rs.randn(S, 512, 13) * 0.5).astype(np.float32)).to(dev)
-    d_nbr = torch.from_numpy((rs.randn(S, 512, 13) * 0.5).astype(np.float32)).to(dev)
-    net.forward(d_inl, d_nbr)
-    torch.cuda.synchronize()
-    ev0.record()
-    for _ in range(reps):
-        net.forward(d_inl, d_nbr)
-    ev1.record()
-    torch.cuda.synchronize()
-    fwd_ms = ev0.elapsed_time(ev1) / reps
-    dflops = S * FLOPS_PER_INSTANCE_STEP
-    roof['dense'] = {'note': 'side launch, NOT in the timed loop: lrg_forward on all 512 + 512 rows of %d instances' % S,
-                     'achieved': dflops / (fwd_ms * 1e-3) / 1e12, 'frac': dflops / (fwd_ms * 1e-3) / 1e12 / FP32_MATRIX_PEAK_TFLOPS,
-                     'ms_per_launch': fwd_ms, 'algorithmic_flops': dflops,
-                     'hbm_accounting': {'note': 'SURVEY.md 8d layer-streamed accounting (what an unfused implementation would stream); the fused kernels '
-                                                'keep activations in LDS, so this is NOT traffic', 'bytes_per_instance': BYTES_PER_INSTANCE_STEP,
-                                        'GBps': S * BYTES_PER_INSTANCE_STEP / (fwd_ms * 1e-3) / 1e9,
-                                        'frac_of_hbm_peak': S * BYTES_PER_INSTANCE_STEP / (fwd_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}}
-    # north_star's MLP metric: the SAME evaluation run layer by layer, every activation through HBM (LRG_FWD_STREAM_TILES: csrc/lrg_stream_layer.inl), a side launch
-    # at 1 088 instances, priced with the algorithmic bytes of SURVEY.md 8d (the counters' figure: profiles/r05_traffic_streamed_tiles.json)
-    try:
-        from learn_region_grow_amd.lrgnet import LrgNetHIP
-        Sb = 1088
-        snet = LrgNetHIP(1, 1, 512, 512, 13, 0, device=dev, mode='streamed-tiles').load_weights(weights)
-        s_inl = torch.from_numpy((rs.randn(Sb, 512, 13) * 0.5).astype(np.float32)).to(dev)
-        s_nbr = torch.from_numpy((rs.randn(Sb, 512, 13) * 0.5).astype(np.float32)).to(dev)
-        snet.forward(s_inl, s_nbr)
-        torch.cuda.synchronize()
-        ev0.record()
-        for _ in range(reps):
-            snet.forward(s_inl, s_nbr)
-        ev1.record()
-        torch.cuda.synchronize()
-        s_ms = ev0.elapsed_time(ev1) / reps
-        roof['dense']['layer_streamed'] = {'note': 'side launch, NOT in the timed loop: one launch per layer, activations through HBM (mode streamed-tiles), %d instances' % Sb,
-                                           'ms_per_evaluation': s_ms, 'algorithmic_bytes': Sb * BYTES_PER_INSTANCE_STEP,
-                                           'GBps': Sb * BYTES_PER_INSTANCE_STEP / (s_ms * 1e-3) / 1e9,
-                                           'frac_of_hbm_peak': Sb * BYTES_PER_INSTANCE_STEP / (s_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                           'counters': 'profiles/r05_traffic_streamed_tiles.json (FETCH_SIZE + WRITE_SIZE: 12.16 GB in 3.41 ms under the profiler = 0.446)'}
-        del snet, s_inl, s_nbr
-    except Exception as e:       # (a side figure: never the reason the line is missing)
-        roof['dense']['layer_streamed'] = {'error': repr(e)}
+    if args.full:
+        roof['dense'] = dense_side_launches(net, weights, S, dev)
     # HBM traffic / matrix-pipe occupancy of the loop's kernel: PMC passes of their own (tools/pmc_free_run.sh), quoted from the committed
     # file only when it was measured on this ABI and formulation
     roof['traffic'] = None
@@ -952,7 +1010,7 @@ def main():
     fixed = best = None
     if args.fixed_rooms < 0:
         args.fixed_rooms = max(8 * len(base), 4 * 8 * slots)      # R >= 8 GPUs x slots per GPU x 4 waves, the same R for every N
-    if args.fixed_rooms > 0 and args.restarts == 1:
+    if args.full and args.fixed_rooms > 0 and args.restarts == 1:
         fixed = fixed_work(args.fixed_rooms, slots, measure_fill=True)
         sweep = [int(x) for x in args.best_slots.split(',') if x.strip()] if args.workload != 'kitti' else []
         tried = {slots: fixed}
@@ -1025,29 +1083,28 @@ def main():
                                                       'reach at best (no 1 -> 8 curve has been measured by the builder: one GPU per box)'}
         if best:
             out['fixed_work_best'] = best
-        if world == 1 and args.steady_slots and args.workload == 'area5' and args.restarts == 1:
-            # the steady leg again with more rooms of the same set in flight (a run of this script of its own; `value` stays the
+        if world == 1 and args.full and args.steady_slots and args.workload == 'area5' and args.restarts == 1:
+            # the steady leg again with more rooms of the same set in flight (a plain run of this script of its own; `value` stays the
             # 68-room configuration the metric is quoted on)
             sweep = {}
             for sl in [int(x) for x in args.steady_slots.split(',') if x]:
                 try:
                     r = subprocess.run([sys.executable, os.path.abspath(__file__), '--gpus', '1', '--rooms', str(sl), '--steps', str(max(4, args.steps // 2)),
-                                        '--warmup', str(args.warmup), '--step-ms', str(args.step_ms), '--fixed-rooms', '0', '--best-slots', '', '--steady-slots', '',
-                                        '--cpu-seconds', '0', '--p0-rooms', '0', '--policy', args.policy, '--weights', args.weights, '--cache', args.cache],
-                                       capture_output=True, text=True, timeout=600)
+                                        '--warmup', str(args.warmup), '--step-ms', str(args.step_ms), '--policy', args.policy, '--weights', args.weights,
+                                        '--cache', args.cache], capture_output=True, text=True, timeout=600)
                     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
                     sweep[str(sl)] = {'value': d['value'], 'unit': d['unit'], 'formulation': d['config']['formulation'],
                                       'us_per_instance_step_per_slot': d.get('us_per_instance_step_per_slot')}
                 except Exception as e:      # (informational leg: never fails the line)
                     sweep[str(sl)] = {'error': repr(e)[:200]}
             out['steady_more_rooms_in_flight'] = sweep
-        if world == 1 and args.named_configs and args.workload == 'area5' and args.restarts == 1:
+        if world == 1 and args.full and args.named_configs and args.workload == 'area5' and args.restarts == 1:
             # BASELINE configs 3 and 5 in the driver's own line (round-5 review: "the driver's line carries no KITTI or ScanNet figure"): eight ScanNet-shaped rooms and
             # eight Semantic-KITTI-shaped scenes in flight on this GPU, each a short run of this script of its own (steady leg + the rooms / scenes from reset to labels)
             named = {}
             for wl, fixed_n in (('scannet', 39), ('kitti', 8)):
                 try:
-                    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--gpus', '1', '--workload', wl, '--rooms', '8', '--steps', str(max(4, args.steps // 2)),
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--full', '--gpus', '1', '--workload', wl, '--rooms', '8', '--steps', str(max(4, args.steps // 2)),
                                         '--warmup', str(args.warmup), '--step-ms', str(args.step_ms), '--fixed-rooms', str(fixed_n), '--best-slots', '', '--steady-slots', '',
                                         '--one-room-ks', '', '--named-configs', '0', '--cpu-seconds', '0', '--p0-rooms', '0', '--policy', args.policy, '--weights', args.weights,
                                         '--cache', args.cache], capture_output=True, text=True, timeout=600)
@@ -1060,7 +1117,7 @@ def main():
                 except Exception as e:      # (informational legs: never fail the line)
                     named[wl] = {'error': repr(e)[:200]}
             out['named_configs'] = named
-        if world == 1 and args.one_room_ks and args.restarts == 1 and packed:
+        if world == 1 and args.full and args.one_room_ks and args.restarts == 1 and packed:
             ks = [int(x) for x in args.one_room_ks.split(',') if x.strip()]
             by_size = sorted(range(len(base)), key=lambda i: len(base[i]['points']))
             picks = [('scene_0', 0)] if args.workload == 'kitti' else [('median_room', by_size[len(by_size) // 2]), ('largest_room', by_size[-1])]
@@ -1068,9 +1125,9 @@ def main():
                 out['one_room_per_gpu'] = one_room_corner(net, base, picks, ks, grow_kw, dev, step_us)
             except Exception as e:      # noqa: BLE001 -- a side measurement must not take the line down
                 out['one_room_per_gpu'] = {'error': repr(e)[:300]}
-        if world == 1 and args.cpu_seconds > 0:
+        if world == 1 and args.full and args.cpu_seconds > 0:
             out['cpu_baseline'] = cpu_baseline(base, weights, args.cpu_seconds, args.policy, room_steps, args.cpu_box_seconds)
-        if world == 1 and args.p0_rooms > 0:
+        if world == 1 and args.full and args.p0_rooms > 0:
             out['preprocessing_p0'] = p0_rates(args.p0_rooms, dev)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + '\n').encode())

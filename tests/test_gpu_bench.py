@@ -1,6 +1,6 @@
 """GPU: bench.py end to end on tiny configurations -- the one JSON line the driver parses, with its roofline and cpu_baseline
-objects, for both formulations of the loop; `--gpus 2` started WITHOUT a torch.distributed environment (the script spawns its
-ranks itself); a WORLD_SIZE that contradicts --gpus is refused."""
+objects (--full), for both formulations of the loop; a plain run (the steady leg alone); `--gpus 2` started WITHOUT a torch.distributed
+environment (the script spawns its ranks itself); a WORLD_SIZE that contradicts --gpus is refused."""
 import json
 import os
 import subprocess
@@ -26,7 +26,7 @@ def run_bench(argv, env=None, timeout=1200):
 
 @pytest.mark.parametrize('mode,lanes,graph', [('free', 0, 0), ('lockstep', 1, 0), ('lockstep', 2, 4)])
 def test_bench_line(cuda_device, tmp_path, mode, lanes, graph):
-    r, lines = run_bench(['--gpus', '1', '--steps', '3', '--warmup', '2', '--iters-per-step', '16', '--step-ms', '2', '--rooms', '6', '--fixed-rooms', '12',
+    r, lines = run_bench(['--full', '--gpus', '1', '--steps', '3', '--warmup', '2', '--iters-per-step', '16', '--step-ms', '2', '--rooms', '6', '--fixed-rooms', '12',
                           '--best-slots', '3,6', '--steady-slots', '9' if mode == 'free' else '', '--named-configs', '1' if mode == 'free' else '0', '--cpu-seconds', '3', '--cpu-box-seconds', '2', '--p0-rooms', '1', '--mode', mode, '--lanes', str(lanes), '--graph', str(graph),
                           '--cache', str(tmp_path / 'cache')])
     assert r.returncode == 0, r.stderr[-3000:]
@@ -84,16 +84,23 @@ def test_bench_line(cuda_device, tmp_path, mode, lanes, graph):
 @pytest.mark.parametrize('mode', ['free', 'lockstep'])
 def test_bench_dump_outputs_repeat(cuda_device, tmp_path, mode):
     """--dump-outputs DIR: float32 / float64 arrays of what the steady leg computed, within 64 MB, the same bits from run to run
-    (free-running launches: the final labels of the rooms that took the slots first; lock-step: every room's state after the last step)."""
+    (free-running launches: the final labels of the rooms that took the slots first; lock-step: every room's state after the last step).
+    A plain run (no --full) is the steady leg alone: none of the other legs, no side launch of the roofline."""
     dumps = []
     for k in range(2):
         out = tmp_path / ('dump%d' % k)
         r, lines = run_bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--iters-per-step', '16', '--step-ms', '2', '--rooms', '6', '--mode', mode,
-                              '--fixed-rooms', '0', '--best-slots', '', '--steady-slots', '', '--named-configs', '0', '--cpu-seconds', '0', '--p0-rooms', '0',
-                              '--one-room-ks', '', '--cache', str(tmp_path / 'cache'), '--dump-outputs', str(out)])
+                              '--cache', str(tmp_path / 'cache'), '--dump-outputs', str(out)])
         assert r.returncode == 0, r.stderr[-3000:]
+        assert len(lines) == 1
         d = json.loads(lines[0])
         assert d['steps'] == 3 and d['ms_per_step'] > 0 and d['dumped_outputs']['rooms'] == 6
+        assert d['value'] > 0 and d['unit'] == 'instance-steps/s' and d['higher_is_better'] is True and d['dtype'] == 'f32' and 'metric' in d
+        for k_ in ('fixed_work', 'fixed_work_best', 'p14_fill', 'steady_more_rooms_in_flight', 'named_configs', 'one_room_per_gpu', 'cpu_baseline', 'preprocessing_p0'):
+            assert k_ not in d, k_
+        assert 'dense' not in d['roofline'] and d['rooms_per_sec'] == d['rooms_per_sec_steady']
+        if mode == 'free':      # (the roofline of the timed launches needs no run of its own)
+            assert d['roofline']['launches'] == 3 and d['roofline']['frac'] > 0
         files = sorted(os.listdir(out))
         assert files == ['cluster_labels.npy', 'labels.npy', 'room_keys.npy', 'room_points.npy', 'room_regions.npy']
         assert sum(os.path.getsize(out / f) for f in files) <= 64 * 1024 * 1024
@@ -111,7 +118,7 @@ def test_bench_dump_outputs_repeat(cuda_device, tmp_path, mode):
 def test_bench_line_with_restarts_counts_rows_per_slot(cuda_device, tmp_path):
     """test_random_restart.py's loop, 4 restarts per seed batched per launch: rows_evaluated_fraction is per SLOT (rooms x restarts), so it stays <= 1
     (round 5 divided by the rooms: 2.65 in the 16-restart record)."""
-    r, lines = run_bench(['--gpus', '1', '--steps', '2', '--warmup', '1', '--iters-per-step', '8', '--rooms', '4', '--restarts', '4', '--fixed-rooms', '0',
+    r, lines = run_bench(['--full', '--gpus', '1', '--steps', '2', '--warmup', '1', '--iters-per-step', '8', '--rooms', '4', '--restarts', '4', '--fixed-rooms', '0',
                           '--best-slots', '', '--steady-slots', '', '--named-configs', '0', '--cpu-seconds', '0', '--p0-rooms', '0', '--one-room-ks', '', '--cache', str(tmp_path / 'cache')])
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(lines[0])
@@ -122,7 +129,7 @@ def test_bench_line_with_restarts_counts_rows_per_slot(cuda_device, tmp_path):
 def test_bench_two_ranks_started_by_the_script_itself(cuda_device, tmp_path):
     """`python bench.py --gpus 2` with no torch.distributed environment: the script starts its two ranks (here both on cuda:0,
     collectives over gloo: LRG_BENCH_ONE_DEVICE=1), shards the fixed work over them and gathers every room's labels."""
-    common = ['--steps', '2', '--warmup', '1', '--step-ms', '2', '--rooms', '4', '--fixed-rooms', '8', '--best-slots', '', '--steady-slots', '', '--named-configs', '0', '--cpu-seconds', '0',
+    common = ['--full', '--steps', '2', '--warmup', '1', '--step-ms', '2', '--rooms', '4', '--fixed-rooms', '8', '--best-slots', '', '--steady-slots', '', '--named-configs', '0', '--cpu-seconds', '0',
               '--p0-rooms', '0', '--cache', str(tmp_path / 'cache')]
     # (both ranks share the one device here: lock-step launches -- two free-running launches side by side on one chip each assume that all
     #  their workgroups are resident at once, DESIGN.md section 4; on a multi-GPU node every rank has a device to itself)
@@ -142,7 +149,7 @@ def test_bench_two_ranks_started_by_the_script_itself(cuda_device, tmp_path):
     assert d1['fixed_work']['labels_crc32'] == d2['fixed_work']['labels_crc32']      # the gathered labels of all rooms equal the one-rank run's
     assert abs(d2['fixed_work']['waves_per_rank'] - 1.0) < 1e-9 and abs(d1['fixed_work']['waves_per_rank'] - 2.0) < 1e-9      # 8 jobs, 4 slots, 2 / 1 ranks
     # the default sizing of the leg: the same R for every N, and four waves of rooms per slot and rank at N = 8
-    r3, l3 = run_bench(['--gpus', '1', '--steps', '1', '--warmup', '1', '--step-ms', '2', '--rooms', '3', '--best-slots', '', '--steady-slots', '', '--named-configs', '0', '--cpu-seconds', '0',
+    r3, l3 = run_bench(['--full', '--gpus', '1', '--steps', '1', '--warmup', '1', '--step-ms', '2', '--rooms', '3', '--best-slots', '', '--steady-slots', '', '--named-configs', '0', '--cpu-seconds', '0',
                         '--p0-rooms', '0', '--cache', str(tmp_path / 'cache')])
     assert r3.returncode == 0, r3.stderr[-3000:]
     d3 = json.loads(l3[0])

@@ -74,3 +74,18 @@ def test_bench_arguments():
         assert a.speculate == -1 and a.one_room_ks == '1,2,3,4,6' and a.one_rank_collective == 1 and '320' in a.best_slots
     finally:
         sys.argv = old
+
+
+def test_bench_area5_rooms_side_by_side_are_the_set(tmp_path):
+    """bench.py generates the Area-5 set in processes side by side (start_area5_rooms, the largest rooms first): the rooms of
+    workloads.area5_rooms in its order, bit for bit -- generated and cached, then read back from the cache."""
+    import bench
+    from learn_region_grow_amd import workloads
+    want = workloads.area5_rooms(3, seed_base=1000)
+    for _ in range(2):
+        got = bench.start_area5_rooms(3, 1000, str(tmp_path), 2)()
+        assert len(got) == 3
+        for a, b in zip(got, want):
+            assert a['room_id'] == b['room_id']
+            for k in ('points', 'obj_id', 'order'):
+                assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
