@@ -35,6 +35,44 @@ def _softmax_conf(logits):
     return (e / e.sum(axis=-1, keepdims=True))[..., 1]
 
 
+def _env_overrides():
+    """The LRG_* switches of the growers' set-up, read in one place: by load_rooms as it loads rooms, by the previews for LRG_FREE_RUN."""
+    env = os.environ.get
+    return dict(free_run=env('LRG_FREE_RUN', '1') != '0', chan_major=env('LRG_NO_CHAN_MAJOR') != '1', vgrid=env('LRG_NO_VGRID') != '1',
+                tail_rows=env('LRG_FREE_RUN_TAIL_ROWS', ''), fill_cus=env('LRG_FREE_RUN_FILL_CUS'),      # (unset: the grower's option holds)
+                fronts=int(env('LRG_FREE_RUN_FRONTS', '0')), teams=int(env('LRG_FREE_RUN_TEAMS', '0')), cus=int(env('LRG_FREE_RUN_CUS', '0')),
+                poll=int(env('LRG_FREE_RUN_POLL', '0')), tail_us=int(env('LRG_FREE_RUN_TAIL_US', '0')),
+                parts=int(env('LRG_FREE_RUN_PARTS', '0')), units=int(env('LRG_FREE_RUN_UNITS', '0')), waves=int(env('LRG_FREE_RUN_WAVES', '0')),
+                rows16=env('LRG_FREE_RUN_ROWS16', '1') != '0', pool_rows=env('LRG_FREE_RUN_POOL_ROWS', '0') == '1',
+                fill=env('LRG_FREE_RUN_FILL', '1') != '0', fill_wgs=int(env('LRG_FREE_RUN_FILL_WGS', '0')), debug=env('LRG_FREE_RUN_DEBUG') == '1')
+
+
+def choose_formulation(*, mode, lite, n_inlier, n_neighbor, room_points, have_pvox, S, G, restarts, rng, packed, free_run,
+                       skip_duplicate_rows, speculate, packed_workspace, env_free_run):
+    """-> (packed, free_run): a RegionGrower's formulation -- lrg_grow_step (False, False), lrg_grow_step_packed (True, False) or
+    lrg_grow_async (True, True) -- from the wishes packed / free_run (None = where it applies) and the facts; room_points empty: no rooms
+    known yet; env_free_run False: LRG_FREE_RUN=0, no free-running launches unless asked for.  A wish the facts rule out: ValueError."""
+    n, sets = max(room_points, default=0), max(n_inlier, n_neighbor)
+    can_pack = (rng == 'counter' and mode == 'fused' and n <= _lib.LRG_PACKED_MAX_POINTS and sets <= 1024 and skip_duplicate_rows and
+                packed_workspace)
+    if free_run and not can_pack:
+        raise ValueError('free-running launches need packed iterations')
+    if packed and not can_pack:
+        raise ValueError('packed iterations need the counter stream, the fused network and rooms of at most %d points' % _lib.LRG_PACKED_MAX_POINTS)
+    if not ((can_pack and n <= _lib.LRG_PACKED_AUTO_POINTS) if packed is None else packed):
+        return False, False
+    # free-running launches (lrg_grow_async): greedy growing through the single-launch front, lite 0 / 2
+    can_free = (G == 1 or speculate) and restarts == 1 and have_pvox and sets <= 512 and lite != 1
+    if free_run and not can_free:
+        raise ValueError('free-running launches need greedy growing (restarts = group_size = 1), rooms with packed voxel words, '
+                         'at most 512 + 512 points per set and lite 0 or 2')
+    if free_run is None:
+        # (auto: where a step is a chain of latencies -- up to ~100 slots; with hundreds of slots in flight the lock-step
+        #  launches, whose tiles pack the rows of all slots, get more out of the chip: 272 rooms 1.20 M against 0.80 M)
+        free_run = can_free and S <= _lib.LRG_FREE_RUN_AUTO_SLOTS and n <= _lib.LRG_FREE_RUN_AUTO_POINTS and env_free_run
+    return True, bool(free_run)
+
+
 class RoomResult:
     def __init__(self, room_id, cluster_label, filled_label, regions):
         self.room_id = room_id
@@ -133,38 +171,66 @@ class RegionGrower:
         self.room_order_mode = room_order              # 'queue': dist.queue_order where rooms wait for slots (more than two rounds of them); 'loaded': as loaded
         self.free_run_waves = int(free_run_waves)      # wave-branch launches (LrgAsyncBuffers.branch_waves): 0 = by the slot count, -1 = off, n = on with n wavefronts per wave-branch CU
         self.debug_hook = None      # tests: called once per active slot per legacy iteration with the step's data
-        self._rooms_loaded = False
+        # the free-running path's state, set where load_rooms builds its buffers and kept across loads
+        self.fill_cus, self.main_stream, self.fill_stream, self._in_fill_stream, self.fill_in_launch, self.a_dbg = 0, None, None, False, False, None
+        self._filled_in_launch, self.fills_redone, self.launches, self.last_stats, self._trace_done = [], 0, 0, (0, 0, 0), None
 
     # ------------------------------------------------------------------------------------------
     @staticmethod
     def free_run_applies(net, rooms, rooms_in_flight, restarts=1, group_size=None, rng='counter', resolution=0.1, packed=None, free_run=None,
                          skip_duplicate_rows=True, **_):
-        """Whether a RegionGrower built with these arguments would grow `rooms` with free-running launches (the decision load_rooms takes
-        once it has the rooms on the device), from the host arrays alone -- so that a caller who builds its growers around that answer
-        (LanedRegionGrower: one free-running lane, or several lock-step lanes) need not build them twice."""
-        if free_run is False or rng != 'counter' or net.mode != 'fused' or not skip_duplicate_rows or packed is False or not rooms:
+        """Whether a RegionGrower built with these arguments would grow `rooms` with free-running launches (choose_formulation, as
+        load_rooms takes it once it has the rooms on the device), from the host arrays alone -- so that a caller who builds its growers
+        around that answer (LanedRegionGrower: one free-running lane, or several lock-step lanes) need not build them twice."""
+        if not rooms:
             return False
         G = int(restarts if group_size is None else group_size)
-        ns = [int(len(r['points'])) for r in rooms]
-        if G != 1 or int(restarts) != 1 or max(net.num_inlier_points, net.num_neighbor_points) > 512 or getattr(net, 'lite', 0) == 1:
+        # packed voxel words: every room within 2048 x 2048 x 1024 voxels (lrg_voxelize: rint(x / resolution) in float32)
+        have_pvox = not any((np.ptp(np.rint(np.asarray(r['points'], dtype=np.float32)[:, :3] / np.float32(resolution)), axis=0) >
+                             np.array([2047, 2047, 1023])).any() for r in rooms if len(r['points']))
+        # (a falsy wish other than False, such as 0, counts as None here -- load_rooms takes it as False)
+        packed, free_run = [w if w or w is False else None for w in (packed, free_run)]
+        try:      # (no library call: the packed workspace is not sized here)
+            return choose_formulation(mode=net.mode, lite=net.lite, n_inlier=net.num_inlier_points, n_neighbor=net.num_neighbor_points,
+                                      room_points=[int(len(r['points'])) for r in rooms], have_pvox=have_pvox, S=int(rooms_in_flight) * G,
+                                      G=G, restarts=int(restarts), rng=rng, packed=packed, free_run=free_run,
+                                      skip_duplicate_rows=skip_duplicate_rows, speculate=0, packed_workspace=True,
+                                      env_free_run=_env_overrides()['free_run'])[1]
+        except ValueError:      # (a wish load_rooms would refuse)
             return False
-        if max(ns) > (_lib.LRG_PACKED_MAX_POINTS if packed else _lib.LRG_PACKED_AUTO_POINTS):
-            return False
-        for r in rooms:      # packed voxel words: every room within 2048 x 2048 x 1024 voxels (lrg_voxelize: rint(x / resolution) in float32)
-            if len(r['points']):
-                v = np.rint(np.asarray(r['points'], dtype=np.float32)[:, :3] / np.float32(resolution))
-                if ((v.max(axis=0) - v.min(axis=0)) > np.array([2047, 2047, 1023])).any():
-                    return False
-        if free_run:
-            return True
-        return (int(rooms_in_flight) * G <= _lib.LRG_FREE_RUN_AUTO_SLOTS and max(ns) <= _lib.LRG_FREE_RUN_AUTO_POINTS and
-                os.environ.get('LRG_FREE_RUN', '1') != '0')
 
     def load_rooms(self, rooms):
         """rooms: list of dicts with points [n,F] float32, obj_id [n], order [n] (= argsort(curvatures),
-        test_region_grow.py:183) and optional room_id.  Uploads them, voxelises (:175) and builds the
-        per-room voxel tables."""
-        dev, F, S = self.dev, self.net.feature_size, self.S
+        test_region_grow.py:183) and optional room_id.  Uploads them, voxelises (:175), builds the per-room voxel
+        tables and the buffers of the formulation choose_formulation picks for them."""
+        env = _env_overrides()
+        self._upload_rooms(rooms, env)
+        self._build_voxel_tables(rooms, env)
+        self._alloc_slots()
+        self._release_graph()
+        self.packed, self.free_run = choose_formulation(
+            mode=self.net.mode, lite=self.net.lite, n_inlier=self.net.num_inlier_points, n_neighbor=self.net.num_neighbor_points,
+            room_points=self.room_n, have_pvox=self.have_pvox, S=self.S, G=self.G, restarts=self.params.restarts, rng=self.rng,
+            packed=self.want_packed, free_run=self.want_free_run, skip_duplicate_rows=self.skip_duplicate_rows, speculate=self.speculate,
+            packed_workspace=self.lib.lrg_forward_packed_workspace_bytes(ctypes.byref(self.net._w), self.S, 32) > 0, env_free_run=env['free_run'])
+        if self.params.scoring == 1 and not self.packed:
+            raise ValueError("scoring='ml' needs the packed iteration (fused network, rooms of at most %d points)" % _lib.LRG_PACKED_MAX_POINTS)
+        if self.packed:
+            self._alloc_packed_buffers(env)
+        if self.free_run:
+            self._alloc_async_buffers(env)
+        self.h_stats = [torch.zeros(LRG_STATS_WORDS, dtype=torch.int64).pin_memory() for _ in range(self.depth)]
+        self.ev = [torch.cuda.Event() for _ in range(self.depth)]
+        self.group_room = [-1] * self.n_groups
+        self._reset_pending = set()
+        self.iterations = 0
+        self._seen_done = 0
+        self._polls = 0
+        self._polls_seen = -1
+        return self
+
+    def _upload_rooms(self, rooms, env):
+        dev, F = self.dev, self.net.feature_size
         ns = [int(len(r['points'])) for r in rooms]
         # every room starts at a multiple of 16 points in the arenas: the packed iteration reads masks, visited flags and packed
         # voxel words four points per load
@@ -188,7 +254,7 @@ class RegionGrower:
         # -- mostly runs of consecutive indices -- then come from a few dense lines per channel instead of one word per row
         cch = [c for c in range(F) if c < 2 or c >= 6]
         self.d_chan = None
-        if tot and len(cch) * tot < 2 ** 31 and os.environ.get('LRG_NO_CHAN_MAJOR') != '1':
+        if tot and len(cch) * tot < 2 ** 31 and env['chan_major']:
             self.d_chan = self.d_points[:, cch].t().contiguous()
         self.d_obj = torch.from_numpy(obj).to(dev)
         self.d_order = torch.from_numpy(order).to(dev)
@@ -198,6 +264,11 @@ class RegionGrower:
         self.d_label = torch.zeros(tot, dtype=torch.int32, device=dev)
         self.d_filled = torch.zeros(tot, dtype=torch.int32, device=dev)
         self.d_rlog = torch.zeros((tot, _lib.LRG_LOG_WORDS), dtype=torch.int32, device=dev)
+
+    def _build_voxel_tables(self, rooms, env):
+        """Every room's voxels (:175), packed voxel words, dense voxel grid and voxel hash table; its LrgRoom record."""
+        dev, F, ns, offs = self.dev, self.net.feature_size, self.room_n, self.room_off
+        tot = int(offs[-1])
         caps = [max(16, 1 << int(np.ceil(np.log2(2 * n + 1)))) for n in ns]
         hoffs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
         self.d_hkeys = torch.empty(int(hoffs[-1]), dtype=torch.int64, device=dev)
@@ -220,7 +291,7 @@ class RegionGrower:
         # dense voxel grids (LrgRoom.vgrid): 4 bytes per voxel of a room's bounding box -- a few MB per room; rooms whose box
         # exceeds LRG_VGRID_MAX_CELLS (or a set above LRG_VGRID_TOTAL_CELLS in all) keep the hash table and the room-wide pass
         cells = [dims[r][0] * dims[r][1] * dims[r][2] if ns[r] else 0 for r in range(len(rooms))]
-        use_grid = [self.have_pvox and 0 < c <= _lib.LRG_VGRID_MAX_CELLS and os.environ.get('LRG_NO_VGRID') != '1' for c in cells]
+        use_grid = [self.have_pvox and 0 < c <= _lib.LRG_VGRID_MAX_CELLS and env['vgrid'] for c in cells]
         if sum(c for c, u in zip(cells, use_grid) if u) > _lib.LRG_VGRID_TOTAL_CELLS:
             use_grid = [False] * len(rooms)
         goffs = np.concatenate([[0], np.cumsum([(c + 15) // 16 * 16 if u else 0 for c, u in zip(cells, use_grid)])]).astype(np.int64)
@@ -268,8 +339,11 @@ class RegionGrower:
                                    'the grow resolution (test_region_grow.py:125-134)' % dup)
         self.room_ids = [int(self.h_rooms[r].room_id) for r in range(len(rooms))]
         self.d_rooms = torch.from_numpy(np.frombuffer(bytes(self.h_rooms), dtype=np.uint8).copy()).to(dev)
-        # ---- slots ----
-        cap = (max(ns) + 15) // 16 * 16           # (lrg_grow_step_packed sets mask bytes with word-wide atomics)
+
+    def _alloc_slots(self):
+        """The slots (LrgSlot records, masks and index lists of a room's size) and the buffers of a lock-step iteration (LrgStepBuffers)."""
+        dev, F, S = self.dev, self.net.feature_size, self.S
+        cap = (max(self.room_n) + 15) // 16 * 16           # (lrg_grow_step_packed sets mask bytes with word-wide atomics)
         self.cap = cap
         self.d_cur = torch.zeros((S, cap), dtype=torch.uint8, device=dev)
         self.d_best = torch.zeros((S, cap), dtype=torch.uint8, device=dev)
@@ -289,7 +363,6 @@ class RegionGrower:
             sl.status = LRG_IDLE
             sl.seed = -1
         self.d_slots = torch.from_numpy(np.frombuffer(bytes(self.h_slots), dtype=np.uint8).copy()).to(dev)
-        # ---- step buffers ----
         Ni, Nn = self.net.num_inlier_points, self.net.num_neighbor_points
         self.b_center = torch.zeros((S, 16), dtype=torch.float32, device=dev)
         self.b_sin = torch.zeros((S, Ni), dtype=torch.int32, device=dev)
@@ -318,141 +391,113 @@ class RegionGrower:
         if self.skip_duplicate_rows:
             sb.rows_in, sb.rows_nb = self.b_rows_in.data_ptr(), self.b_rows_nb.data_ptr()
         self.step_buffers = sb
-        self._release_graph()
-        can_pack = (self.rng == 'counter' and self.net.mode == 'fused' and max(ns) <= _lib.LRG_PACKED_MAX_POINTS and
-                    max(Ni, Nn) <= 1024 and self.skip_duplicate_rows and
-                    self.lib.lrg_forward_packed_workspace_bytes(ctypes.byref(self.net._w), S, 32) > 0)
-        self.free_run = False
-        if self.want_free_run and not can_pack:
-            raise ValueError('free-running launches need packed iterations')
-        if self.want_packed and not can_pack:
-            raise ValueError('packed iterations need the counter stream, the fused network and rooms of at most %d points'
-                             % _lib.LRG_PACKED_MAX_POINTS)
-        self.packed = (can_pack and max(ns) <= _lib.LRG_PACKED_AUTO_POINTS) if self.want_packed is None else bool(self.want_packed)
-        if self.params.scoring == 1 and not self.packed:
-            raise ValueError("scoring='ml' needs the packed iteration (fused network, rooms of at most %d points)" % _lib.LRG_PACKED_MAX_POINTS)
-        if self.packed:
-            cap_rows = S * ((max(Ni, Nn) + 31) // 32 * 32)     # (a slot's rows are allocated in multiples of 8 -- or, free-running, have
-                                                                 #  a place of their own of whole 32-row tiles)
-            # Shared tail tiles of the free-running launches (LrgAsyncBuffers.tail_ctl): rows behind the slots' own that the slots' tails share, so that the rows
-            # beyond a slot's last full tile fill tiles together.  Sized for a 25 ms launch at the rate the slot count sustains (~32 k evaluations x 2 x 16 rows:
-            # when a launch runs out of them, the slots pad tiles of their own again).  On from 224 slots, where the tile teams are what the launch is bound by and
-            # the CUs they save can serve slots instead (44 front workgroups instead of 34: lrg_grow_async): 2 176 room jobs at 272 slots 828 -> 872 rooms/s, 320: ->
-            # 886; below, a step is a chain of latencies and a tile that waits for a second slot's tail only lengthens it (68 slots: 868 -> 714 k instance-steps/s,
-            # 136: 1.14 -> 1.07 M; profiles/r05_tail_sweep_v2.txt, r05_tail_fronts*.txt).  LRG_FREE_RUN_TAIL_ROWS: 0 = off, n = that many rows per side.
-            self.tail_rows = 0
-            if self.want_free_run is not False and F >= 9 and F <= 16:
-                env = os.environ.get('LRG_FREE_RUN_TAIL_ROWS', '')
-                want = int(env) if env else (self.free_run_tail_rows if self.free_run_tail_rows is not None else (min(1 << 20, 4096 * S) if (S >= 224 and not self.speculate) else 0))
-                self.tail_rows = max(0, want) // 32 * 32
-            cap_rows += self.tail_rows + (32 if self.tail_rows else 0)      # (+ a tile: a head tile on a slot's tail rows stages 32 rows from the tail's first)
-            self.row_cap = cap_rows
-            # (room for rows at a 64-byte stride: the free-running kernel gathers and stages its rows in 16-byte pieces, LrgAsyncBuffers.rows16; the
-            #  lock-step launches use the first cap_rows x F floats of the same arrays)
-            self.p_xin = torch.zeros((cap_rows, max(F, 16)), dtype=torch.float32, device=dev)
-            self.p_xnb = torch.zeros((cap_rows, max(F, 16)), dtype=torch.float32, device=dev)
-            self.p_rsin = torch.zeros(cap_rows, dtype=torch.int32, device=dev)
-            self.p_rsnb = torch.zeros(cap_rows, dtype=torch.int32, device=dev)
-            self.p_updin = torch.zeros((S, Ni, 4), dtype=torch.float32, device=dev)
-            self.p_updnb = torch.zeros((S, Nn, 4), dtype=torch.float32, device=dev)
-            self.p_rmv = torch.zeros((cap_rows, 2), dtype=torch.float32, device=dev)
-            self.p_add = torch.zeros((cap_rows, 2), dtype=torch.float32, device=dev)
-            self.p_slot_rows = torch.zeros((S, 4), dtype=torch.int32, device=dev)
-            self.p_counters = torch.zeros(4, dtype=torch.int32, device=dev)
-            pbytes = self.lib.lrg_forward_packed_workspace_bytes(ctypes.byref(self.net._w), S, cap_rows)
-            self.p_ws = torch.zeros(pbytes, dtype=torch.uint8, device=dev)
-            pb = LrgPackedBuffers()
-            pb.center, pb.sample_in, pb.sample_nb = self.b_center.data_ptr(), self.b_sin.data_ptr(), self.b_snb.data_ptr()
-            pb.x_in, pb.x_nb = self.p_xin.data_ptr(), self.p_xnb.data_ptr()
-            pb.row_slot_in, pb.row_slot_nb = self.p_rsin.data_ptr(), self.p_rsnb.data_ptr()
-            pb.upd_in, pb.upd_nb = self.p_updin.data_ptr(), self.p_updnb.data_ptr()
-            pb.rmv_logits, pb.add_logits = self.p_rmv.data_ptr(), self.p_add.data_ptr()
-            pb.slot_rows, pb.counters = self.p_slot_rows.data_ptr(), self.p_counters.data_ptr()
-            pb.workspace, pb.workspace_bytes = self.p_ws.data_ptr(), self.p_ws.numel()
-            pb.stats = self.d_stats.data_ptr()
-            pb.row_cap = cap_rows
-            self.p_big = torch.zeros((S, 2), dtype=torch.int32, device=dev)
-            pb.slot_big = self.p_big.data_ptr()
-            pb.rooms_have_pvox = 1 if self.have_pvox else 0
-            self.packed_buffers = pb
-            # free-running launches (lrg_grow_async): greedy growing through the single-launch front, lite 0 / 2
-            can_free = ((self.G == 1 or self.speculate) and self.params.restarts == 1 and self.have_pvox and max(Ni, Nn) <= 512 and
-                        getattr(self.net, 'lite', 0) != 1)
-            if self.want_free_run and not can_free:
-                raise ValueError('free-running launches need greedy growing (restarts = group_size = 1), rooms with packed voxel words, '
-                                 'at most 512 + 512 points per set and lite 0 or 2')
-            if self.want_free_run is None:
-                # (auto: where a step is a chain of latencies -- up to ~100 slots; with hundreds of slots in flight the lock-step
-                #  launches, whose tiles pack the rows of all slots, get more out of the chip: 272 rooms 1.20 M against 0.80 M)
-                self.free_run = can_free and S <= _lib.LRG_FREE_RUN_AUTO_SLOTS and max(ns) <= _lib.LRG_FREE_RUN_AUTO_POINTS and os.environ.get('LRG_FREE_RUN', '1') != '0'
-            else:
-                self.free_run = bool(self.want_free_run)
-            if self.free_run:
-                qbytes = self.lib.lrg_grow_async_queue_bytes(S)
-                self.a_queue = torch.zeros(qbytes // 4, dtype=torch.int32, device=dev)
-                self.a_sync = torch.zeros((S, 16), dtype=torch.int32, device=dev)
-                ab = LrgAsyncBuffers()
-                ab.queue, ab.queue_bytes, ab.sync = self.a_queue.data_ptr(), qbytes, self.a_sync.data_ptr()
-                ab.front_workgroups = self.free_run_fronts or int(os.environ.get('LRG_FREE_RUN_FRONTS', '0'))
-                ab.teams = self.free_run_teams or int(os.environ.get('LRG_FREE_RUN_TEAMS', '0'))
-                ab.compute_units = int(os.environ.get('LRG_FREE_RUN_CUS', '0'))
-                self.fill_cus = int(os.environ.get('LRG_FREE_RUN_FILL_CUS', '0' if self.free_run_fill_cus is None else str(int(self.free_run_fill_cus))))
-                self.main_stream = None
-                if self.fill_cus > 0 and ab.compute_units == 0:
-                    ab.compute_units = max(64, torch.cuda.get_device_properties(dev).multi_processor_count - self.fill_cus)
-                    self.main_stream, self.fill_stream = fill_streams(dev, self.fill_cus)
-                ab.poll_sleep = int(os.environ.get('LRG_FREE_RUN_POLL', '0'))
-                ab.branch_parts = int(os.environ.get('LRG_FREE_RUN_PARTS', '0'))
-                ab.gemv_units = self.free_run_units or int(os.environ.get('LRG_FREE_RUN_UNITS', '0'))          # -1: the pooled product as tasks of the tile teams
-                ab.branch_waves = self.free_run_waves or int(os.environ.get('LRG_FREE_RUN_WAVES', '0'))
-                ab.rows16 = 1 if (9 <= F <= 16 and os.environ.get('LRG_FREE_RUN_ROWS16', '1') != '0') else 0
-                # LRG_FREE_RUN_POOL_ROWS=1: a branch tile leaves its column maxima as ONE row of 16-byte stores and the pooled-product units take
-                # the maximum over a slot's tiles while loading (no atomicMax per column, no zeroing by the front workgroup).  Same labels;
-                # measured 832 k against 850 k instance-steps/s at 68 rooms in flight (profiles/r04_pool_rows_ab.txt): each of the sixteen
-                # units then loads ~3.5 rows per side instead of one pooled row, on the step's critical path -- off by default.
-                if os.environ.get('LRG_FREE_RUN_POOL_ROWS', '0') == '1':
-                    nb = self.lib.lrg_grow_async_pool_rows_bytes(ctypes.byref(self.net._w), S)
-                    self.a_pool_rows = torch.zeros(nb // 4, dtype=torch.float32, device=dev)
-                    ab.pool_rows, ab.pool_rows_bytes = self.a_pool_rows.data_ptr(), nb
-                # in-launch fill-in (lrg_async.inl): finished rooms are filled in (:308-316) by tile teams of the same launch; the host only
-                # reads the statistics block between two launches.  LRG_FREE_RUN_FILL=0: lrg_nn1_fill_batch between the launches, as in round 3.
-                self.fill_in_launch = F == 13 and os.environ.get('LRG_FREE_RUN_FILL', '1') != '0' and getattr(self, 'fill_cus', 0) == 0
-                if self.fill_in_launch:
-                    self.a_fill_list = torch.zeros(tot, dtype=torch.int32, device=dev)
-                    self.a_fill_best = torch.zeros(tot, dtype=torch.int64, device=dev)
-                    self.a_fill_sync = torch.zeros((len(rooms), 4), dtype=torch.int32, device=dev)
-                    ab.fill_list, ab.fill_best, ab.fill_sync = self.a_fill_list.data_ptr(), self.a_fill_best.data_ptr(), self.a_fill_sync.data_ptr()
-                    ab.fill_label_base, ab.fill_out_base = self.d_label.data_ptr(), self.d_filled.data_ptr()
-                    ab.fill_rooms = len(rooms)
-                    ab.fill_wgs = int(os.environ.get('LRG_FREE_RUN_FILL_WGS', '0'))
-                if self.tail_rows and ab.rows16:
-                    tb = self.lib.lrg_grow_async_tail_bytes(S, self.tail_rows)
-                    self.a_tail = torch.zeros(tb // 4 + 16, dtype=torch.int32, device=dev)
-                    ab.tail_ctl = (self.a_tail.data_ptr() + 63) // 64 * 64
-                    ab.tail_rows = self.tail_rows
-                    ab.tail_close_us = int(os.environ.get('LRG_FREE_RUN_TAIL_US', '0'))
-                self.a_work = torch.zeros(8, dtype=torch.int64, device=dev)      # evaluations, inlier rows, neighbour rows, tiles; speculation: regions voided, their evaluations
-                ab.speculate = self.speculate if self.speculate > 1 else 0
-                ab.work = self.a_work.data_ptr()
-                if os.environ.get('LRG_FREE_RUN_DEBUG') == '1':          # stage-by-stage tick accumulators (tools/free_run_perf.py)
-                    self.a_dbg = torch.zeros(64, dtype=torch.int64, device=dev)
-                    ab.debug_ticks = self.a_dbg.data_ptr()
-                self.async_buffers = ab
-        self.h_stats = [torch.zeros(LRG_STATS_WORDS, dtype=torch.int64).pin_memory() for _ in range(self.depth)]
-        self.ev = [torch.cuda.Event() for _ in range(self.depth)]
-        self.group_room = [-1] * self.n_groups
-        self._reset_pending = set()
-        self.iterations = 0
-        self._seen_done = 0
-        self._polls = 0
-        self._polls_seen = -1
-        self._rooms_loaded = True
-        return self
+
+    def _alloc_packed_buffers(self, env):
+        """The packed iterations' rows (LrgPackedBuffers), which the free-running launches use too."""
+        dev, F, S = self.dev, self.net.feature_size, self.S
+        Ni, Nn = self.net.num_inlier_points, self.net.num_neighbor_points
+        cap_rows = S * ((max(Ni, Nn) + 31) // 32 * 32)     # (a slot's rows are allocated in multiples of 8 -- or, free-running, have
+                                                             #  a place of their own of whole 32-row tiles)
+        # Shared tail tiles of the free-running launches (LrgAsyncBuffers.tail_ctl): rows behind the slots' own that the slots' tails share, so that the rows
+        # beyond a slot's last full tile fill tiles together.  Sized for a 25 ms launch at the rate the slot count sustains (~32 k evaluations x 2 x 16 rows:
+        # when a launch runs out of them, the slots pad tiles of their own again).  On from 224 slots, where the tile teams are what the launch is bound by and
+        # the CUs they save can serve slots instead (44 front workgroups instead of 34: lrg_grow_async): 2 176 room jobs at 272 slots 828 -> 872 rooms/s, 320: ->
+        # 886; below, a step is a chain of latencies and a tile that waits for a second slot's tail only lengthens it (68 slots: 868 -> 714 k instance-steps/s,
+        # 136: 1.14 -> 1.07 M; profiles/r05_tail_sweep_v2.txt, r05_tail_fronts*.txt).  LRG_FREE_RUN_TAIL_ROWS: 0 = off, n = that many rows per side.
+        self.tail_rows = 0
+        if self.want_free_run is not False and F >= 9 and F <= 16:
+            want = int(env['tail_rows']) if env['tail_rows'] else (self.free_run_tail_rows if self.free_run_tail_rows is not None else (min(1 << 20, 4096 * S) if (S >= 224 and not self.speculate) else 0))
+            self.tail_rows = max(0, want) // 32 * 32
+        cap_rows += self.tail_rows + (32 if self.tail_rows else 0)      # (+ a tile: a head tile on a slot's tail rows stages 32 rows from the tail's first)
+        self.row_cap = cap_rows
+        # (room for rows at a 64-byte stride: the free-running kernel gathers and stages its rows in 16-byte pieces, LrgAsyncBuffers.rows16; the
+        #  lock-step launches use the first cap_rows x F floats of the same arrays)
+        self.p_xin = torch.zeros((cap_rows, max(F, 16)), dtype=torch.float32, device=dev)
+        self.p_xnb = torch.zeros((cap_rows, max(F, 16)), dtype=torch.float32, device=dev)
+        self.p_rsin = torch.zeros(cap_rows, dtype=torch.int32, device=dev)
+        self.p_rsnb = torch.zeros(cap_rows, dtype=torch.int32, device=dev)
+        self.p_updin = torch.zeros((S, Ni, 4), dtype=torch.float32, device=dev)
+        self.p_updnb = torch.zeros((S, Nn, 4), dtype=torch.float32, device=dev)
+        self.p_rmv = torch.zeros((cap_rows, 2), dtype=torch.float32, device=dev)
+        self.p_add = torch.zeros((cap_rows, 2), dtype=torch.float32, device=dev)
+        self.p_slot_rows = torch.zeros((S, 4), dtype=torch.int32, device=dev)
+        self.p_counters = torch.zeros(4, dtype=torch.int32, device=dev)
+        pbytes = self.lib.lrg_forward_packed_workspace_bytes(ctypes.byref(self.net._w), S, cap_rows)
+        self.p_ws = torch.zeros(pbytes, dtype=torch.uint8, device=dev)
+        pb = LrgPackedBuffers()
+        pb.center, pb.sample_in, pb.sample_nb = self.b_center.data_ptr(), self.b_sin.data_ptr(), self.b_snb.data_ptr()
+        pb.x_in, pb.x_nb = self.p_xin.data_ptr(), self.p_xnb.data_ptr()
+        pb.row_slot_in, pb.row_slot_nb = self.p_rsin.data_ptr(), self.p_rsnb.data_ptr()
+        pb.upd_in, pb.upd_nb = self.p_updin.data_ptr(), self.p_updnb.data_ptr()
+        pb.rmv_logits, pb.add_logits = self.p_rmv.data_ptr(), self.p_add.data_ptr()
+        pb.slot_rows, pb.counters = self.p_slot_rows.data_ptr(), self.p_counters.data_ptr()
+        pb.workspace, pb.workspace_bytes = self.p_ws.data_ptr(), self.p_ws.numel()
+        pb.stats = self.d_stats.data_ptr()
+        pb.row_cap = cap_rows
+        self.p_big = torch.zeros((S, 2), dtype=torch.int32, device=dev)
+        pb.slot_big = self.p_big.data_ptr()
+        pb.rooms_have_pvox = 1 if self.have_pvox else 0
+        self.packed_buffers = pb
+
+    def _alloc_async_buffers(self, env):
+        """The free-running launches' buffers and settings (LrgAsyncBuffers): the grower's options, else the LRG_FREE_RUN_* switches."""
+        dev, F, S = self.dev, self.net.feature_size, self.S
+        qbytes = self.lib.lrg_grow_async_queue_bytes(S)
+        self.a_queue = torch.zeros(qbytes // 4, dtype=torch.int32, device=dev)
+        self.a_sync = torch.zeros((S, 16), dtype=torch.int32, device=dev)
+        ab = LrgAsyncBuffers()
+        ab.queue, ab.queue_bytes, ab.sync = self.a_queue.data_ptr(), qbytes, self.a_sync.data_ptr()
+        ab.front_workgroups = self.free_run_fronts or env['fronts']
+        ab.teams = self.free_run_teams or env['teams']
+        ab.compute_units = env['cus']
+        self.fill_cus = int(env['fill_cus'] if env['fill_cus'] is not None else self.free_run_fill_cus or 0)
+        self.main_stream = None
+        if self.fill_cus > 0 and ab.compute_units == 0:
+            ab.compute_units = max(64, torch.cuda.get_device_properties(dev).multi_processor_count - self.fill_cus)
+            self.main_stream, self.fill_stream = fill_streams(dev, self.fill_cus)
+        ab.poll_sleep = env['poll']
+        ab.branch_parts = env['parts']
+        ab.gemv_units = self.free_run_units or env['units']          # -1: the pooled product as tasks of the tile teams
+        ab.branch_waves = self.free_run_waves or env['waves']
+        ab.rows16 = 1 if (9 <= F <= 16 and env['rows16']) else 0
+        # LRG_FREE_RUN_POOL_ROWS=1: a branch tile leaves its column maxima as ONE row of 16-byte stores and the pooled-product units take
+        # the maximum over a slot's tiles while loading (no atomicMax per column, no zeroing by the front workgroup).  Same labels;
+        # measured 832 k against 850 k instance-steps/s at 68 rooms in flight (profiles/r04_pool_rows_ab.txt): each of the sixteen
+        # units then loads ~3.5 rows per side instead of one pooled row, on the step's critical path -- off by default.
+        if env['pool_rows']:
+            nb = self.lib.lrg_grow_async_pool_rows_bytes(ctypes.byref(self.net._w), S)
+            self.a_pool_rows = torch.zeros(nb // 4, dtype=torch.float32, device=dev)
+            ab.pool_rows, ab.pool_rows_bytes = self.a_pool_rows.data_ptr(), nb
+        # in-launch fill-in (lrg_async.inl): finished rooms are filled in (:308-316) by tile teams of the same launch; the host only
+        # reads the statistics block between two launches.  LRG_FREE_RUN_FILL=0: lrg_nn1_fill_batch between the launches, as in round 3.
+        self.fill_in_launch = F == 13 and env['fill'] and self.fill_cus == 0
+        if self.fill_in_launch:
+            tot = int(self.room_off[-1])
+            self.a_fill_list = torch.zeros(tot, dtype=torch.int32, device=dev)
+            self.a_fill_best = torch.zeros(tot, dtype=torch.int64, device=dev)
+            self.a_fill_sync = torch.zeros((self.n_rooms, 4), dtype=torch.int32, device=dev)
+            ab.fill_list, ab.fill_best, ab.fill_sync = self.a_fill_list.data_ptr(), self.a_fill_best.data_ptr(), self.a_fill_sync.data_ptr()
+            ab.fill_label_base, ab.fill_out_base = self.d_label.data_ptr(), self.d_filled.data_ptr()
+            ab.fill_rooms = self.n_rooms
+            ab.fill_wgs = env['fill_wgs']
+        if self.tail_rows and ab.rows16:
+            tb = self.lib.lrg_grow_async_tail_bytes(S, self.tail_rows)
+            self.a_tail = torch.zeros(tb // 4 + 16, dtype=torch.int32, device=dev)
+            ab.tail_ctl = (self.a_tail.data_ptr() + 63) // 64 * 64
+            ab.tail_rows = self.tail_rows
+            ab.tail_close_us = env['tail_us']
+        self.a_work = torch.zeros(8, dtype=torch.int64, device=dev)      # evaluations, inlier rows, neighbour rows, tiles; speculation: regions voided, their evaluations
+        ab.speculate = self.speculate if self.speculate > 1 else 0
+        ab.work = self.a_work.data_ptr()
+        if env['debug']:          # stage-by-stage tick accumulators (tools/free_run_perf.py)
+            self.a_dbg = torch.zeros(64, dtype=torch.int64, device=dev)
+            ab.debug_ticks = self.a_dbg.data_ptr()
+        self.async_buffers = ab
 
     # ------------------------------------------------------------------------------------------
     def reset_room(self, r):
         """Return room r to its pristine state (visited / labels cleared, cursor at 0)."""
-        if getattr(self, 'fill_stream', None) is not None:      # (a fill-in of the room may still be reading its labels)
+        if self.fill_stream is not None:      # (a fill-in of the room may still be reading its labels)
             torch.cuda.current_stream(self.dev).wait_stream(self.fill_stream)
         if self.rng == 'counter' and self.device_bind:
             self._reset_pending.add(r)          # folded into the device-side bind that follows (one launch, no upload)
@@ -507,35 +552,20 @@ class RegionGrower:
         """1-NN fill-in of room r's unlabeled points (test_region_grow.py:308-316) into d_filled.  Free-running launches with CUs
         left out for it (free_run_fill_cus): on the fill stream, beside the next launch -- the room was reported finished by a launch
         that has completed (poll_done), its labels are final; wait_fills() before reading d_filled."""
-        if getattr(self, 'free_run', False) and getattr(self, 'fill_cus', 0) > 0 and not getattr(self, '_in_fill_stream', False):
-            self._in_fill_stream = True
-            try:
-                with torch.cuda.stream(self.fill_stream):
-                    self.fill(r)
-            finally:
-                self._in_fill_stream = False
-            return
         o, n = int(self.room_off[r]), self.room_n[r]
         F = self.net.feature_size
-        if getattr(self, '_fill_ws', None) is None:
-            self._fill_ws = torch.empty(self.lib.lrg_nn1_fill_workspace_bytes(max(self.room_n)), dtype=torch.uint8, device=self.dev)
-        _lib.check(self.lib.lrg_nn1_fill_ws(ctypes.c_void_p(self.d_points.data_ptr() + o * F * 4), n, F,
-                                            ctypes.c_void_p(self.d_label.data_ptr() + o * 4),
-                                            ctypes.c_void_p(self.d_filled.data_ptr() + o * 4), _ptr(self._fill_ws),
-                                            self._fill_ws.numel(), _stream_ptr(self.dev)), 'lrg_nn1_fill_ws')
+        with torch.cuda.stream(self._fill_target()):
+            if self._fill_ws is None:
+                self._fill_ws = torch.empty(self.lib.lrg_nn1_fill_workspace_bytes(max(self.room_n)), dtype=torch.uint8, device=self.dev)
+            _lib.check(self.lib.lrg_nn1_fill_ws(ctypes.c_void_p(self.d_points.data_ptr() + o * F * 4), n, F,
+                                                ctypes.c_void_p(self.d_label.data_ptr() + o * 4),
+                                                ctypes.c_void_p(self.d_filled.data_ptr() + o * 4), _ptr(self._fill_ws),
+                                                self._fill_ws.numel(), _stream_ptr(self.dev)), 'lrg_nn1_fill_ws')
 
     def fill_many(self, rs):
         """fill(r) for every r of rs, the rooms filled in together (lrg_nn1_fill_batch: three launches per 64 rooms instead of four per
         room; the rooms that finish during one free-running launch)."""
         rs = list(rs)
-        if getattr(self, 'free_run', False) and getattr(self, 'fill_cus', 0) > 0 and not getattr(self, '_in_fill_stream', False):
-            self._in_fill_stream = True          # (CUs left out for the fill-ins: on the fill stream, as fill() does)
-            try:
-                with torch.cuda.stream(self.fill_stream):
-                    self.fill_many(rs)
-            finally:
-                self._in_fill_stream = False
-            return
         if len(rs) <= 1:
             for r in rs:
                 self.fill(r)
@@ -549,18 +579,24 @@ class RegionGrower:
             jobs[k].label_out = self.d_filled.data_ptr() + o * 4
             jobs[k].n = n
         need = self.lib.lrg_nn1_fill_batch_workspace_bytes(jobs, len(rs))
-        if getattr(self, '_fill_ws', None) is None or self._fill_ws.numel() < need:
-            self._fill_ws = torch.empty(max(need, self.lib.lrg_nn1_fill_workspace_bytes(max(self.room_n))), dtype=torch.uint8, device=self.dev)
-        _lib.check(self.lib.lrg_nn1_fill_batch(jobs, len(rs), F, _ptr(self._fill_ws), self._fill_ws.numel(), _stream_ptr(self.dev)), 'lrg_nn1_fill_batch')
+        with torch.cuda.stream(self._fill_target()):
+            if self._fill_ws is None or self._fill_ws.numel() < need:
+                self._fill_ws = torch.empty(max(need, self.lib.lrg_nn1_fill_workspace_bytes(max(self.room_n))), dtype=torch.uint8, device=self.dev)
+            _lib.check(self.lib.lrg_nn1_fill_batch(jobs, len(rs), F, _ptr(self._fill_ws), self._fill_ws.numel(), _stream_ptr(self.dev)), 'lrg_nn1_fill_batch')
+
+    def _fill_target(self):
+        """The stream of the fill-ins: the fill stream where CUs are left out of the free-running launches for them (free_run_fill_cus),
+        unless _in_fill_stream asks for the current one; None = the current stream."""
+        return self.fill_stream if self.free_run and self.fill_cus > 0 and not self._in_fill_stream else None
 
     def wait_fills(self):
         """Fill-ins enqueued on the fill stream are complete on return."""
-        if getattr(self, 'fill_stream', None) is not None:
+        if self.fill_stream is not None:
             self.fill_stream.synchronize()
 
     # ------------------------------------------------------------------------------------------
     def _release_graph(self):
-        if getattr(self, '_graph', None):
+        if self._graph:      # (a grower whose __init__ raised has none: __del__ ignores the AttributeError)
             self.lib.lrg_step_graph_destroy(self._graph)
         self._graph = None
 
@@ -636,10 +672,9 @@ class RegionGrower:
         return row
 
     def free_run_ticks(self):
-        import numpy as _np
-        if getattr(self, 'a_dbg', None) is None:
+        if self.a_dbg is None:
             return None
-        return self.a_dbg.cpu().numpy().astype(_np.float64)
+        return self.a_dbg.cpu().numpy().astype(np.float64)
 
     def enqueue_free_run(self, steps=None, budget_us=None):
         """One free-running launch: every slot up to `steps` grow steps at its own pace (lrg_grow_async)."""
@@ -649,7 +684,7 @@ class RegionGrower:
                                      ctypes.byref(self.net._w), ctypes.byref(self.packed_buffers), ctypes.byref(self.async_buffers),
                                      steps, budget, _stream_ptr(self.dev))
         _lib.check(rc, 'lrg_grow_async')
-        self.launches = getattr(self, 'launches', 0) + 1      # (`iterations` counts lock-step iterations only; the steps taken: instance_steps)
+        self.launches += 1      # (`iterations` counts lock-step iterations only; the steps taken: instance_steps)
         self._record_poll()
 
     def enqueue(self):
@@ -722,23 +757,36 @@ class RegionGrower:
         from .dist import queue_order
         return queue_order(list(range(self.n_rooms)), [int(n) for n in self.room_n[:self.n_rooms]], self.n_groups)
 
+    def bind_first(self, queue):
+        """Every slot group bound to the next room of `queue` (taken off it; -1 once it is empty).  Returns the rooms left waiting."""
+        for g in range(self.n_groups):
+            self.bind(g, queue.pop(0) if queue else -1)
+        return queue
+
+    def lockstep_round(self, queue, fill=True, enqueue=None):
+        """One round of the lock-step room loop: the next iterations (`enqueue`, else self.enqueue), the groups whose room finished
+        (poll_done), those rooms' fill-ins and the next rooms of `queue` bound to the groups.  Returns how many rooms finished."""
+        (enqueue or self.enqueue)()
+        gs = self.poll_done()
+        if fill:
+            self.fill_many([self.group_room[g] for g in gs])
+        for g in gs:
+            self.bind(g, queue.pop(0) if queue else -1)
+        return len(gs)
+
     def free_run_begin(self):
         """Free-running launches over ALL loaded rooms: the first S rooms bound by the host, the rest handed out on the device."""
         self.reset_state()
-        order = self.room_order()
-        first = min(self.n_groups, self.n_rooms)
-        for g in range(self.n_groups):
-            self.bind(g, order[g] if g < first else -1)
-        self.set_room_queue(order[first:])
+        self.set_room_queue(self.bind_first(self.room_order()))
         self.rooms_finished = 0
 
     def verify_fills_in_launch(self):
         """A room the done ring reported as filled in by its launch (bit 31) must have its 'filled' word set by the last fill task
         (LrgAsyncBuffers.fill_sync[room][3]); a room whose tasks did not complete is filled in here, by the host-launched kernels --
         never left with stale labels.  Returns the rooms that needed it (normally none)."""
-        rooms = sorted(set(getattr(self, '_filled_in_launch', [])))
+        rooms = sorted(set(self._filled_in_launch))
         self._filled_in_launch = []
-        if not rooms or not getattr(self, 'fill_in_launch', False):
+        if not rooms or not self.fill_in_launch:
             return []
         torch.cuda.current_stream(self.dev).synchronize()
         flags = self.a_fill_sync[:, 3].cpu().numpy()
@@ -746,7 +794,7 @@ class RegionGrower:
         if missing:
             self.fill_many(missing)
             torch.cuda.current_stream(self.dev).synchronize()
-        self.fills_redone = getattr(self, 'fills_redone', 0) + len(missing)
+        self.fills_redone += len(missing)
         return missing
 
     def free_run_step(self, fill=True, steps=None, budget_us=None, wait=False):
@@ -756,25 +804,23 @@ class RegionGrower:
         self.poll_done(wait=wait)
         n = len(self.done_rooms)
         # (the last rooms of a pass: no launch follows that their fill-ins could run beside -- on the launches' stream, with the whole chip)
-        last = getattr(self, 'fill_cus', 0) > 0 and self.rooms_finished + n >= self.n_rooms
+        last = self.fill_cus > 0 and self.rooms_finished + n >= self.n_rooms
         if last:
             self.wait_fills()
             self._in_fill_stream = True
         if fill:
             self.fill_many([r for r, f in zip(self.done_rooms, self.done_filled) if not f])
-            if not hasattr(self, '_filled_in_launch'):
-                self._filled_in_launch = []
             self._filled_in_launch.extend(r for r, f in zip(self.done_rooms, self.done_filled) if f)
         if last:
             self._in_fill_stream = False
         self.rooms_finished += n
-        if getattr(self, '_trace_done', None) is not None:
+        if self._trace_done is not None:
             self._trace_done.extend(int(r) for r in self.done_rooms)
         self.done_rooms = []
         return n
 
     def _grow_loaded_free_run(self, fill=True):
-        main = getattr(self, 'main_stream', None)
+        main = self.main_stream
         if main is not None and torch.cuda.current_stream(self.dev).cuda_stream != main.cuda_stream:
             # CUs left out for the fill-ins: the launches go to the stream confined to the rest (fill_streams)
             main.wait_stream(torch.cuda.current_stream(self.dev))
@@ -787,7 +833,7 @@ class RegionGrower:
         while self.rooms_finished < self.n_rooms:
             self.free_run_step(fill)
             if trace is not None:
-                trace.append((round(time.perf_counter() - t0, 4), self.rooms_finished, getattr(self, 'last_stats', (0, 0, 0))[2]))
+                trace.append((round(time.perf_counter() - t0, 4), self.rooms_finished, self.last_stats[2]))
         torch.cuda.current_stream(self.dev).synchronize()
         if trace is not None:
             import sys
@@ -805,18 +851,10 @@ class RegionGrower:
         if self.free_run:
             return self._grow_loaded_free_run(fill)
         self.reset_state()
-        queue = self.room_order()
-        for g in range(self.n_groups):
-            self.bind(g, queue.pop(0) if queue else -1)
+        queue = self.bind_first(self.room_order())
         finished = 0
         while finished < self.n_rooms:
-            self.enqueue()
-            gs = self.poll_done()
-            if fill:
-                self.fill_many([self.group_room[g] for g in gs])
-            for g in gs:
-                finished += 1
-                self.bind(g, queue.pop(0) if queue else -1)
+            finished += self.lockstep_round(queue, fill)
         torch.cuda.current_stream(self.dev).synchronize()
         return self.n_rooms
 
@@ -967,8 +1005,7 @@ class RegionGrower:
             torch.cuda.synchronize()
             return self.collect(fill)
         queue = list(range(self.n_rooms)) if self.rng == 'legacy' else self.room_order()      # (legacy streams are consumed in the loaded order: the reference's)
-        for g in range(self.n_groups):
-            self.bind(g, queue.pop(0) if queue else -1)
+        self.bind_first(queue)
         finished = 0
         if self.rng == 'legacy':
             if legacy_shared_seed is not None:
@@ -994,13 +1031,7 @@ class RegionGrower:
             #  share their buffers and give the same results -- instead of one launch of up to free_run_steps steps per slot)
             step = self.enqueue_iteration if (self.free_run and max_iterations) else self.enqueue
             while finished < self.n_rooms:
-                step()
-                gs = self.poll_done()
-                if fill:
-                    self.fill_many([self.group_room[g] for g in gs])
-                for g in gs:
-                    finished += 1
-                    self.bind(g, queue.pop(0) if queue else -1)
+                finished += self.lockstep_round(queue, fill, step)
                 if max_iterations and self.iterations >= max_iterations:
                     break
         torch.cuda.synchronize()
@@ -1046,10 +1077,20 @@ def auto_lanes(slots_in_flight):
     return 2 if slots_in_flight < 64 else 3
 
 
-_LANE_STREAMS = {}       # (device index, CU-masked lane count or 0) -> ([torch streams], [raw handles]), one set per process
+_LANE_STREAMS = {}       # (device index, CU-masked lane count or 0) -> [torch streams], one set per process
+_FILL_STREAMS = {}       # (device index, fill_cus) -> (launch stream, fill stream), one pair per process
 
 
-_FILL_STREAMS = {}
+def _cu_masked_stream(device, cus):
+    """A new stream of `device` confined to the compute units `cus` (lrg_stream_create_cu_mask; never destroyed)."""
+    ncu = torch.cuda.get_device_properties(device).multi_processor_count
+    mask = (ctypes.c_uint32 * ((ncu + 31) // 32))()
+    for b in cus:
+        mask[b // 32] |= 1 << (b % 32)
+    h = ctypes.c_void_p()
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().lrg_stream_create_cu_mask(mask, len(mask), ctypes.byref(h)), 'lrg_stream_create_cu_mask')
+        return torch.cuda.ExternalStream(h.value, device=device)
 
 
 def fill_streams(device, fill_cus):
@@ -1059,23 +1100,11 @@ def fill_streams(device, fill_cus):
     with the two streams masked to disjoint sets the fill-ins run on their few CUs while the launch runs on the rest
     (tools/r03_masked_streams.py: CUs 0 .. 7 of the mask's numbering work, one CU in eight does not)."""
     device = torch.device(device)
-    dev_index = device.index if device.index is not None else torch.cuda.current_device()
-    key = (dev_index, int(fill_cus))
+    key = (device.index if device.index is not None else torch.cuda.current_device(), int(fill_cus))
     if key not in _FILL_STREAMS:
-        lib = _lib.load()
         ncu = torch.cuda.get_device_properties(device).multi_processor_count
-        words = (ncu + 31) // 32
-        out = []
-        with torch.cuda.device(device):
-            for cus in (range(int(fill_cus), ncu), range(int(fill_cus))):
-                mask = (ctypes.c_uint32 * words)()
-                for b in cus:
-                    mask[b // 32] |= 1 << (b % 32)
-                h = ctypes.c_void_p()
-                _lib.check(lib.lrg_stream_create_cu_mask(mask, words, ctypes.byref(h)), 'lrg_stream_create_cu_mask')
-                out.append((h, torch.cuda.ExternalStream(h.value, device=device)))
-        _FILL_STREAMS[key] = out
-    return _FILL_STREAMS[key][0][1], _FILL_STREAMS[key][1][1]
+        _FILL_STREAMS[key] = tuple(_cu_masked_stream(device, cus) for cus in (range(int(fill_cus), ncu), range(int(fill_cus))))
+    return _FILL_STREAMS[key]
 
 
 def lane_streams(device, lanes, cu_partition=False):
@@ -1087,27 +1116,14 @@ def lane_streams(device, lanes, cu_partition=False):
     cu_partition: every lane's stream confined to its own 1/lanes of the compute units (lrg_stream_create_cu_mask; measured:
     no gain -- lanes do not compete for CUs -- so off by default)."""
     device = torch.device(device)
-    dev_index = device.index if device.index is not None else torch.cuda.current_device()
-    key = (dev_index, lanes if cu_partition and lanes > 1 else 0)
-    streams, raw = _LANE_STREAMS.setdefault(key, ([], []))
+    key = (device.index if device.index is not None else torch.cuda.current_device(), lanes if cu_partition and lanes > 1 else 0)
+    streams = _LANE_STREAMS.setdefault(key, [])
     if key[1] == 0:
         while len(streams) < lanes:
             streams.append(torch.cuda.Stream(device=device))
-        return streams[:lanes]
-    if not streams:
-        lib = _lib.load()
+    elif not streams:
         ncu = torch.cuda.get_device_properties(device).multi_processor_count
-        words = (ncu + 31) // 32
-        with torch.cuda.device(device):
-            for k in range(lanes):
-                lo, hi = k * ncu // lanes, (k + 1) * ncu // lanes
-                mask = (ctypes.c_uint32 * words)()
-                for b in range(lo, hi):
-                    mask[b // 32] |= 1 << (b % 32)
-                h = ctypes.c_void_p()
-                _lib.check(lib.lrg_stream_create_cu_mask(mask, words, ctypes.byref(h)), 'lrg_stream_create_cu_mask')
-                raw.append(h)
-                streams.append(torch.cuda.ExternalStream(h.value, device=device))
+        streams.extend(_cu_masked_stream(device, range(k * ncu // lanes, (k + 1) * ncu // lanes)) for k in range(lanes))
     return streams[:lanes]
 
 
@@ -1140,11 +1156,14 @@ class LanedRegionGrower:
         arguments allow one, else auto_lanes)."""
         self._auto = None
         if lanes is None or int(lanes) <= 0:
-            lockstep_lanes = auto_lanes(int(rooms_in_flight) * int(kw.get('restarts', 1)))
-            lanes = lockstep_lanes
-            # free-running launches (RegionGrower's choice up to LRG_FREE_RUN_AUTO_SLOTS greedy slots) fill the chip by themselves: one lane
-            if (kw.get('free_run', None) is not False and int(kw.get('restarts', 1)) == 1 and int(rooms_in_flight) <= _lib.LRG_FREE_RUN_AUTO_SLOTS and
-                    kw.get('packed', None) is not False and os.environ.get('LRG_FREE_RUN', '1') != '0'):
+            lockstep_lanes = lanes = auto_lanes(int(rooms_in_flight) * int(kw.get('restarts', 1)))
+            # free-running launches (RegionGrower's choice up to LRG_FREE_RUN_AUTO_SLOTS greedy slots) fill the chip by themselves: one lane.
+            # Until rooms are seen only a wish of False, restarts, the rooms in flight and LRG_FREE_RUN count; the rest is load_rooms' to weigh
+            _, free = choose_formulation(mode='fused', lite=0, n_inlier=0, n_neighbor=0, room_points=(), have_pvox=True, S=int(rooms_in_flight),
+                                         G=1, restarts=int(kw.get('restarts', 1)), rng='counter', packed=False if kw.get('packed') is False else None,
+                                         free_run=False if kw.get('free_run') is False else None, skip_duplicate_rows=True, speculate=0,
+                                         packed_workspace=True, env_free_run=_env_overrides()['free_run'])
+            if free:
                 lanes = 1
                 if lockstep_lanes > 1:
                     self._auto = dict(rooms_in_flight=rooms_in_flight, lockstep_lanes=lockstep_lanes, cu_partition=cu_partition, kw=dict(kw))
@@ -1191,17 +1210,9 @@ class LanedRegionGrower:
             room = dict(rooms[i])
             room.setdefault('room_id', i)
             parts[k].append(room)
-        if L == 1 and rooms:
-            gr = self.growers[0]
-            with torch.cuda.stream(self.streams[0]):
-                gr.load_rooms(parts[0])
-            gr.room_index = list(order)
-            torch.cuda.synchronize()
-            return
         for k, gr in enumerate(self.growers):
             gr.n_rooms = 0
-            gr.room_index = [i for i in range(len(rooms)) if self.where[i][0] == k]      # input index of the lane's rooms,
-            gr.room_index.sort(key=lambda i: self.where[i][1])                            #   in the lane's order
+            gr.room_index = [i for i in order if self.where[i][0] == k]      # input index of the lane's rooms, in the lane's order
             if parts[k]:
                 with torch.cuda.stream(self.streams[k]):
                     gr.load_rooms(parts[k])
@@ -1224,32 +1235,19 @@ class LanedRegionGrower:
                 n = self.growers[0].grow_loaded(fill)
             torch.cuda.synchronize()
             return n
-        queues, finished = [], 0
+        queues = []
         for k, gr in enumerate(self.growers):
             with torch.cuda.stream(self.streams[k]):
-                q = list(range(gr.n_rooms))
+                queues.append(list(range(gr.n_rooms)))
                 if gr.n_rooms:
                     gr.reset_state()
-                    for g in range(gr.n_groups):
-                        gr.bind(g, q.pop(0) if q else -1)
-                queues.append(q)
-        total = sum(gr.n_rooms for gr in self.growers)
-        live = [gr.n_rooms > 0 for gr in self.growers]
-        done = [0] * len(self.growers)
-        while finished < total:
+                    gr.bind_first(queues[k])
+        total, done = sum(gr.n_rooms for gr in self.growers), [0] * len(self.growers)
+        while sum(done) < total:      # (round robin: one round of every lane with rooms left, each on its own stream)
             for k, gr in enumerate(self.growers):
-                if not live[k]:
-                    continue
-                with torch.cuda.stream(self.streams[k]):
-                    gr.enqueue()
-                    gs = gr.poll_done()
-                    if fill:
-                        gr.fill_many([gr.group_room[g] for g in gs])
-                    for g in gs:
-                        finished += 1
-                        done[k] += 1
-                        gr.bind(g, queues[k].pop(0) if queues[k] else -1)
-                    live[k] = done[k] < gr.n_rooms
+                if done[k] < gr.n_rooms:
+                    with torch.cuda.stream(self.streams[k]):
+                        done[k] += gr.lockstep_round(queues[k], fill)
         torch.cuda.synchronize()
         return total
 

@@ -361,3 +361,28 @@ def test_room_order_does_not_change_the_labels(net):
             np.testing.assert_array_equal(a.filled_label, b.filled_label)
     assert made[0].room_order() != list(range(len(rooms))) and sorted(made[0].room_order()) == list(range(len(rooms)))
     assert made[1].room_order() == list(range(len(rooms)))
+
+
+def _line_room(span, room_id):
+    """200 points on distinct voxel centres at 0.1 m along x, `span` voxels from the first to the last."""
+    p = np.zeros((200, 13), np.float32)
+    p[:, 0] = np.round(np.linspace(0, span, 200)) * np.float32(0.1)
+    return dict(points=p, obj_id=np.zeros(200, np.int32), order=np.arange(200, dtype=np.int32), room_id=room_id)
+
+
+def test_free_run_preview_agrees_with_load_rooms(net, cuda_device):
+    """RegionGrower.free_run_applies (from the host arrays) gives the formulation load_rooms picks from the device's voxel words, and
+    LanedRegionGrower's lanes follow it: one free-running lane, else auto_lanes lock-step lanes.  Rooms are loaded, not grown."""
+    from learn_region_grow_amd.lrgnet import LrgNetHIP
+    from learn_region_grow_amd.grow import LanedRegionGrower, RegionGrower, auto_lanes
+    lite1 = LrgNetHIP(1, 1, 512, 512, 13, 1, device=cuda_device).load_weights(synthetic.make_synthetic_weights(lite=1, **WEIGHT_KW))
+    small = _rooms()[:3]
+    cases = [(net, small, {}, True), (net, small, dict(restarts=4), False), (net, small, dict(free_run=False), False),
+             (net, [_line_room(2047, 1)], {}, True), (net, [_line_room(2048, 1)], {}, False),      # packed voxel words: 2047 voxels across at most
+             (lite1, small, {}, False)]
+    for nt, rooms, kw, want in cases:
+        assert RegionGrower.free_run_applies(nt, rooms, 68, **kw) == want, kw
+        assert RegionGrower(nt, rooms_in_flight=68, **kw).load_rooms(rooms).free_run == want, kw
+        lg = LanedRegionGrower(nt, rooms_in_flight=68, **kw)
+        lg.load_rooms(rooms)
+        assert [g.free_run for g in lg.growers] == ([True] if want else [False] * auto_lanes(68 * kw.get('restarts', 1))), kw

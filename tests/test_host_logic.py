@@ -42,6 +42,53 @@ def test_free_run_applies_matches_the_growers_rules():
     assert not RegionGrower.free_run_applies(net, [], 68)
 
 
+def test_choose_formulation_table():
+    """The one rule behind RegionGrower.load_rooms, free_run_applies and LanedRegionGrower's lanes: (packed, free_run) for each
+    change of the facts of 68 greedy slots over two small rooms, or the ValueError of a wish the facts rule out."""
+    from learn_region_grow_amd import _lib
+    from learn_region_grow_amd.grow import choose_formulation
+    base = dict(mode='fused', lite=0, n_inlier=512, n_neighbor=512, room_points=[2000, 3000], have_pvox=True, S=68, G=1, restarts=1,
+                rng='counter', packed=None, free_run=None, skip_duplicate_rows=True, speculate=0, packed_workspace=True, env_free_run=True)
+    big = _lib.LRG_PACKED_MAX_POINTS + 1
+    table = [({}, (True, True)),
+             (dict(free_run=False), (True, False)),
+             (dict(env_free_run=False), (True, False)),                                     # LRG_FREE_RUN=0: lock-step by default ...
+             (dict(env_free_run=False, free_run=True), (True, True)),                       # ... unless asked for
+             (dict(S=_lib.LRG_FREE_RUN_AUTO_SLOTS + 1), (True, False)),
+             (dict(S=_lib.LRG_FREE_RUN_AUTO_SLOTS + 1, free_run=True), (True, True)),
+             (dict(packed=False), (False, False)),
+             (dict(packed=False, free_run=True), (False, False)),                           # (not refused: no packed iterations, no free run)
+             (dict(packed=True), (True, True)),
+             (dict(restarts=16, G=16, S=68 * 16), (True, False)),
+             (dict(speculate=3, G=3, S=204, free_run=True), (True, True)),
+             (dict(have_pvox=False), (True, False)),
+             (dict(lite=1), (True, False)),
+             (dict(lite=2), (True, True)),
+             (dict(n_inlier=1024), (True, False)),
+             (dict(n_neighbor=2048), (False, False)),
+             (dict(room_points=[big]), (False, False)),
+             (dict(room_points=[]), (True, True)),                                          # no rooms known yet
+             (dict(mode='streamed'), (False, False)),
+             (dict(rng='legacy', skip_duplicate_rows=False), (False, False)),
+             (dict(skip_duplicate_rows=False), (False, False)),
+             (dict(packed_workspace=False), (False, False)),
+             (dict(mode='streamed', free_run=True), 'free-running launches need packed iterations'),
+             (dict(packed_workspace=False, free_run=True, packed=True), 'free-running launches need packed iterations'),
+             (dict(mode='streamed', packed=True), 'packed iterations need the counter stream'),
+             (dict(room_points=[big], packed=True), 'packed iterations need the counter stream'),
+             (dict(restarts=16, G=16, free_run=True), 'free-running launches need greedy growing'),
+             (dict(have_pvox=False, free_run=True), 'free-running launches need greedy growing'),
+             (dict(lite=1, free_run=True), 'free-running launches need greedy growing'),
+             (dict(n_inlier=1024, free_run=True), 'free-running launches need greedy growing')]
+    for change, want in table:
+        facts = dict(base, **change)
+        if isinstance(want, str):
+            with pytest.raises(ValueError, match=want):
+                choose_formulation(**facts)
+        else:
+            assert choose_formulation(**facts) == want, change
+
+
 def test_speculate_argument_checks():
     from learn_region_grow_amd.grow import RegionGrower
     with pytest.raises(ValueError):
