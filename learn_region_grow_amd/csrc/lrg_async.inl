@@ -152,7 +152,8 @@ struct LrgAsyncArgs {
     unsigned long long *dbg;     // nullable: [32] accumulators of wall-clock ticks (10 ns) for tools/free_run_perf.py --
                                  // 0 front busy, 1 front steps; per evaluation, since its tasks were published: 2 last branch tile in,
                                  // 3 last pooled-product block in, 4 last head tile in, 5 seen by the front workgroup, 6 evaluations;
-                                 // 8 + 2 t busy ticks of task type t, 9 + 2 t their number; 16 ticks teams waited for a task, 17 waits
+                                 // 8 + 2 t busy ticks of task type t, 9 + 2 t their number; 16 ticks teams waited for a task, 17 waits;
+                                 // the prepared mask update: 7 ticks spent making records, 19 records tried, 18 front steps that used one
 };
 #ifndef LRG_ASYNC_DEBUG
 #define LRG_ASYNC_DEBUG 0        // 1: the tick accumulators of LrgAsyncBuffers.debug_ticks are compiled in (tools/free_run_perf.py builds with it);
@@ -1496,13 +1497,23 @@ struct LrgAsyncFrontCtl {
 
 // ---- one slot's front step, a function of its own: the register allocation of lrg_front_greedy_kernel (no spills) instead of the
 //      ~230 spill instructions it had inlined into the serving loop below, for ~100 saved / restored registers per step ----
-template <bool SPEC>
-LRG_ASYNC_ROLE int lrg_async_front_step(lrg_kargs_ptr kp_, int s_) {
+// (the prepared mask update: the records of the first LRG_PREP_SLOTS served slots lie behind the loop's control words)
+#define LRG_ASYNC_FRONT_CTL_BYTES ((sizeof(LrgFrontShared) + 15) & ~(size_t)15)
+#define LRG_ASYNC_FRONT_PREP_BYTES (LRG_ASYNC_FRONT_CTL_BYTES + ((sizeof(LrgAsyncFrontCtl) + 15) & ~(size_t)15))
+__device__ __forceinline__ LrgPrepRecord *lrg_async_prep_record(int i) {
+    return reinterpret_cast<LrgPrepRecord *>(reinterpret_cast<char *>(lrg_async_smem) + LRG_ASYNC_FRONT_PREP_BYTES) + i;
+}
+
+// PREPD: served slot rec_'s record is valid -- this turn's mask update is the prepared one
+template <bool SPEC, bool PREPD = false>
+LRG_ASYNC_ROLE int lrg_async_front_step(lrg_kargs_ptr kp_, int s_, int rec_ = -1) {
     const lrg_kargs_ptr kp = lrg_uniform(kp_);
     const int s = lrg_uniform(s_);
     const LrgAsyncKArgs &K = LRG_ASYNC_KARGS();
     LrgFrontShared &SH = *reinterpret_cast<LrgFrontShared *>(lrg_async_smem);
-    const int r = lrg_front_greedy_slot<true, SPEC>(SH, K.slots, K.rooms, K.A.n_slots, K.prm, K.A.front, K.A.big, s);
+    int r;
+    if constexpr (PREPD) r = lrg_front_greedy_slot<true, false, true>(SH, K.slots, K.rooms, K.A.n_slots, K.prm, K.A.front, K.A.big, s, lrg_async_prep_record(lrg_uniform(rec_)));
+    else r = lrg_front_greedy_slot<true, SPEC>(SH, K.slots, K.rooms, K.A.n_slots, K.prm, K.A.front, K.A.big, s);
     lrg_exp_delay(LRG_EXP_DELAY_FRONT);
     // Every wavefront's stores of this turn are performed before anybody goes on: the slot's next turn -- and the serving loop right behind this call -- start with
     // loads of the slot's words by EVERY wavefront (status, list sizes, ...), and a word whose store is still on its way is read as old by some wavefronts and as
@@ -1511,6 +1522,17 @@ LRG_ASYNC_ROLE int lrg_async_front_step(lrg_kargs_ptr kp_, int s_) {
     lrg_drain_stores();
     __syncthreads();
     return r;
+}
+
+// ---- the record of served slot i's next mask update (lrg_front.inl, LrgPrepRecord), while its evaluation is in flight: a role of its own, like the step ----
+LRG_ASYNC_ROLE int lrg_async_front_prepare(lrg_kargs_ptr kp_, int s_, int i_) {
+    const lrg_kargs_ptr kp = lrg_uniform(kp_);
+    const int s = lrg_uniform(s_), i = lrg_uniform(i_);
+    const LrgAsyncKArgs &K = LRG_ASYNC_KARGS();
+    const int ok = lrg_front_prepare_record(lrg_async_prep_record(i), K.slots, K.rooms, K.prm, K.A.front, s);
+    lrg_drain_stores();
+    __syncthreads();
+    return ok;
 }
 
 // ---- a front workgroup: serves the slots f, f + n_front, ... ----
@@ -1553,6 +1575,11 @@ __device__ __forceinline__ void lrg_async_front(lrg_kargs_ptr kp, long long t_la
         }
     }
     __syncthreads();
+    // The prepared mask update: bit i of prep_want = served slot i's evaluation is in flight and its record not made yet, of prep_valid = its record is made.  Register
+    // state, the same in every thread: every branch of this loop is taken by the whole workgroup (thread 0's decisions go through LDS).  LDS does not outlive a launch:
+    // a slot's first update of every launch is unprepared.
+    int prep_want = 0, prep_valid = 0;
+    const bool prep_on = LRG_PREPARED_UPDATE && !spec_k;
     for (;;) {
         // a hand-over given up anywhere (or this launch far beyond any sane duration): everybody leaves, the host reports it
         // (Measured and dropped, profiles/r05_ab_front_wait.txt: wavefront 0 waiting HERE for the first of the evaluations in flight, lane k on slot k's counter,
@@ -1607,6 +1634,7 @@ __device__ __forceinline__ void lrg_async_front(lrg_kargs_ptr kp, long long t_la
                 continue;
             }
         }
+        int served = 0;
         for (int ii = 0; ii < (spec_k ? 1 : n_served); ++ii) {
             const int i = spec_k ? chosen : ii;
             const int s = s_first + i * s_step;
@@ -1668,6 +1696,9 @@ __device__ __forceinline__ void lrg_async_front(lrg_kargs_ptr kp, long long t_la
             __syncthreads();
             const int stop = C.bc[1];
             __syncthreads();
+            // (the slot's turn, or its leaving the launch: either way its record, if there is one, is used up)
+            const int rec = (prep_on && i < LRG_PREP_SLOTS && (prep_valid >> i & 1)) ? i : -1;
+            if (prep_on && i < LRG_PREP_SLOTS) { prep_want &= ~(1 << i); prep_valid &= ~(1 << i); }
             if (stop) {
                 // (shared tail tiles: the slot leaves the launch with the logits of its tail rows in rows that the NEXT launch hands out again from row 0 -- its
                 //  first turn there would read them while other slots' head tiles may already write into them.  They go home, to the slot's own rows, before it
@@ -1679,7 +1710,13 @@ __device__ __forceinline__ void lrg_async_front(lrg_kargs_ptr kp, long long t_la
                 continue;
             }
             const long long t_front = LRG_DBG(A) ? wall_clock64() : 0;
-            const int r = __builtin_amdgcn_readfirstlane(spec_k ? lrg_async_front_step<true>(kp, s) : lrg_async_front_step<false>(kp, s));
+            int r;
+            if (spec_k) r = lrg_async_front_step<true>(kp, s);
+            else if (LRG_PREPARED_UPDATE && rec >= 0) r = lrg_async_front_step<false, LRG_PREPARED_UPDATE != 0>(kp, s, rec);
+            else r = lrg_async_front_step<false>(kp, s);
+            r = __builtin_amdgcn_readfirstlane(r);
+            ++served;
+            if (LRG_DBG(A) && tid == 0 && rec >= 0) lrg_dbg_add(A, 18, 1);      // (front steps whose update was the prepared one)
             if (r == 0) {
                 // no evaluation: the slot is idle / its room finished (-> finished for this launch), or it stopped a region / goes on
                 // looking for a seed (-> served again at once)
@@ -1721,6 +1758,7 @@ __device__ __forceinline__ void lrg_async_front(lrg_kargs_ptr kp, long long t_la
             //  tiles, which arrive on the slot's counter like its own, and in one head tile of the slot's own on those rows)
             const LrgFrontShared &SHr = *reinterpret_cast<const LrgFrontShared *>(smem);
             const int rin = r >> 16, rnb = r & 0xFFFF;
+            if (prep_on && i < LRG_PREP_SLOTS) prep_want |= 1 << i;
             const int tb_in = A.tail ? SHr.tail[0] : -1, tb_nb = A.tail ? SHr.tail[1] : -1;
             const int nt_in = tb_in >= 0 ? rin >> 5 : (rin + 31) >> 5, nt_nb = tb_nb >= 0 ? rnb >> 5 : (rnb + 31) >> 5;
             const int sh_in = tb_in >= 0 ? 1 : 0, sh_nb = tb_nb >= 0 ? 1 : 0;
@@ -1783,6 +1821,15 @@ __device__ __forceinline__ void lrg_async_front(lrg_kargs_ptr kp, long long t_la
             __syncthreads();
         }
         if (!live) break;
+        if (prep_on && !served && prep_want) {
+            // nobody had a turn in this pass -- no finished evaluation is kept waiting: the record of one slot whose evaluation is in flight, then the next look
+            const int i = __builtin_ctz(prep_want);
+            prep_want &= ~(1 << i);
+            const long long t_prep = LRG_DBG(A) ? wall_clock64() : 0;
+            if (__builtin_amdgcn_readfirstlane(lrg_async_front_prepare(kp, s_first + i * s_step, i))) prep_valid |= 1 << i;
+            if (LRG_DBG(A) && tid == 0) { lrg_dbg_add(A, 7, wall_clock64() - t_prep); lrg_dbg_add(A, 19, 1); }      // (ticks in the records' making, records tried)
+            continue;
+        }
         __builtin_amdgcn_s_sleep(4);
     }
     lrg_drain_stores();

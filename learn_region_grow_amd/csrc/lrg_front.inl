@@ -41,7 +41,8 @@ struct LrgFrontArgs {
     int64_t *stats;
     int64_t *phase_ticks;    // nullable: [n_slots,2] wall-clock ticks per slot: (0) update / stop / commit, (1) query / median / gather
     int own_medians;         // greedy front kernel: 1 = every slot's workgroup computes its nine medians itself (no launch of their own)
-    unsigned long long *phase_dbg;   // nullable (free-running kernel): [8] accumulated wall-clock ticks of the front's phases
+    unsigned long long *phase_dbg;   // nullable (free-running kernel): [8] accumulated wall-clock ticks of the front's phases; [9 .. 11] inside the mask update: entry -> the
+                                     // slot's words in use, -> logits in registers, -> `take` known
     int row_stride;          // free-running kernel: slot s owns the rows [s * row_stride, (s + 1) * row_stride) of the row arrays
     int rows16;              // free-running kernel: 1 = the gathered rows are written at a 64-byte stride (16 floats, zero-padded) in 16-byte pieces
     int fill_in_launch;      // free-running kernel: finished rooms are filled in (:308-316) by tile teams of the same launch -- flagged in the done ring (bit 31 of the slot word)
@@ -787,6 +788,31 @@ struct LrgFrontShared {
                              // between two updates: cleared by whoever declares the struct, and again by every update after it has been read
 };
 
+// ---- the prepared mask update (free-running kernel, one region per room) ----
+// Of everything the mask update does, only the logits, `take` and what follows from `take` depend on the evaluation that has just arrived; the rest is a
+// function of state the slot had before the evaluation was published.  The front workgroup works that part out while the evaluation is in flight
+// (lrg_front_prepare_record, called from the serving loop of lrg_async.inl in a pass that served nobody) and keeps it in LDS of its own, one record for each of
+// the first LRG_PREP_SLOTS slots it serves: the update behind the arrival is then ONE trip (the logits, their row taken from the record, requested together with
+// the slot's and the room's words) and LDS work.  A record is dropped when it is used, and never made for a region above LRG_PREP_LIST members (its old list and
+// voxel words would not fit: such a step takes the update as it was).  -DLRG_PREPARED_UPDATE=0 compiles the update as it was throughout.
+#ifndef LRG_PREPARED_UPDATE
+#define LRG_PREPARED_UPDATE 1
+#endif
+#define LRG_PREP_SLOTS 2
+#define LRG_PREP_LIST 2048
+struct LrgPrepRecord {
+    int hdr[8];                              // [0] room, [1] nc, [2] ne, [3] seed, [4] restart, [5] step of the evaluation prepared for, [6] 1 = may be prepared (thread 0's look at the slot)
+    // per thread (half, j) of the update:
+    int own[LRG_FRONT_THREADS];              // the point its sample slot stands for
+    int row[LRG_FRONT_THREADS];              // the row of the logits arrays its two logits arrive in
+    uint32_t pvo[LRG_FRONT_THREADS];         // that point's voxel word
+    uint32_t pf[LRG_FRONT_THREADS];          // bits 0-8 source row, 9-19 position in the list the side was sampled from, 24 ground-truth flag, 25 taken, the re-derived voxel is not the point's own
+    uint32_t w[LRG_FRONT_THREADS];           // the Bernoulli word of its draw (:266-267)
+    // per entry of the old index list:
+    int id0[LRG_PREP_LIST];
+    uint32_t pv0[LRG_PREP_LIST];
+};
+
 // ---- speculation (LrgFrontArgs.spec_k = K > 1): several regions of ONE room in flight ----
 // The reference grows a room's regions one after the other: the seeds are visited in curvature order, a visited point is no seed and no
 // candidate (test_region_grow.py:186-188,:227-228), and a region marks its points visited when it stops (:210-217).  A room is a chain of
@@ -904,9 +930,14 @@ __device__ __noinline__ void lrg_spec_commit(LrgFrontShared &SH, LrgSlot *slots,
 // write-through, what they wrote (the logits) is read past the L1 (lrg_fused_tile.inl, COH).
 // SPEC (ASYNC only): the speculation protocol compiled in -- an instantiation of its own, so that the one-slot-per-room step keeps the register allocation it had
 // without it (with both in one function the step saved and restored 32 instead of 21 registers per call).
-template <bool ASYNC, bool SPEC = false>
+// PREPD (ASYNC without SPEC only): the turn's mask update is the prepared one, from the slot's record `rec` -- an instantiation of its own, so that the turn without a
+// record keeps the code it had (a run-time switch in one function cost it a wait for the logits before the slot's words were even requested: the two forms of the
+// room word met in one register).
+template <bool ASYNC, bool SPEC = false, bool PREPD = false>
 __device__ __forceinline__ int lrg_front_greedy_slot(LrgFrontShared &SH, LrgSlot *slots, LrgRoom *rooms, int n_slots, const LrgGrowParams &prm,
-                                                     const LrgFrontArgs &a, int32_t *big, const int s) {
+                                                     const LrgFrontArgs &a, int32_t *big, const int s, const LrgPrepRecord *rec = nullptr) {
+    static_assert(!PREPD || (ASYNC && !SPEC), "the prepared update: free-running, one region per room");
+    constexpr bool PREP = PREPD, prep = PREPD;           // this turn's update was prepared (the serving loop's decision)
     uint8_t *sh_flags = SH.flags;
     int *sh_tab = SH.tab, *sh_tabc = SH.tabc, *sh_tabe = SH.tabe;
     int (*sh_src)[512] = SH.src;
@@ -916,8 +947,15 @@ __device__ __forceinline__ int lrg_front_greedy_slot(LrgFrontShared &SH, LrgSlot
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     LrgSlot *S = &slots[s];
     const int F = prm.feature_size, Ni = prm.n_inlier, Nn = prm.n_neighbor;
+    const long long t_entry = (ASYNC && LRG_ASYNC_DEBUG && a.phase_dbg) ? wall_clock64() : 0;
+    // (prepared: the logits are requested first of all, ahead of round trip 1 -- the one trip the update then waits for.  A wavefront lies in one half: the
+    //  array's address is a scalar, not a load per lane)
+    float2 lg_pre = make_float2(0.f, 0.f);
+    if constexpr (PREP) if (prep) lg_pre = lrg_ld_coh2((__builtin_amdgcn_readfirstlane(tid >> 9) ? a.rmv_logits : a.add_logits) + 2 * (long)rec->row[tid]);
     // ---- round trip 1: everything addressed by the slot number alone ----
-    const int room = S->room;
+    int room;                                            // (prepared: from the record -- the room's words are requested with the slot's, not behind them)
+    if constexpr (PREP) room = rec->hdr[0];
+    else room = S->room;
     int status = S->status;
     const int nc0 = S->nc, ne0 = S->ne;
     // what the stop decision and the random stream need of the slot, requested with the rest of round trip 1 (thread 0 used to walk
@@ -1016,6 +1054,7 @@ __device__ __forceinline__ int lrg_front_greedy_slot(LrgFrontShared &SH, LrgSlot
     uint32_t pv0[4];
     int al0 = 0;                     // bit k: entry k is still a member after the update
     if (status == LRG_ACTIVE) {
+        if constexpr (ASYNC && LRG_ASYNC_DEBUG) if (a.phase_dbg && tid == 0) atomicAdd(&a.phase_dbg[9], (unsigned long long)(t_phase - t_entry));      // (entry -> the slot's words in use)
         // The update by the slot's own lists (round 6).  A sample slot's point is entry `pos` of the list its side was sampled from (:238-240,:250-252) -- known
         // before the evaluation, like the point's voxel word -- and the voxel the reference re-derives from the centred row, rint(((x - c) + c) / res) (:271-276),
         // is that point's own voxel unless the float32 round trip through the centre moves x across a voxel boundary.  So where no taken slot's voxel moved
@@ -1031,23 +1070,61 @@ __device__ __forceinline__ int lrg_front_greedy_slot(LrgFrontShared &SH, LrgSlot
             if (tid < 512) sh_tab[tid] = 0;                                // per neighbour row: its point was switched on (copies of a row draw for themselves, :266)
         }
         if (tid == 0) { sh_i[0] = 0; sh_i[1] = 0; sh_i[5] = 0; sh_i[6] = 0; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) id0[k] = spec ? lrg_ld_coh(&cur_idx[min(tid + k * LRG_FRONT_THREADS, nc0 - 1)]) : cur_idx[min(tid + k * LRG_FRONT_THREADS, nc0 - 1)];
         const int nside = half ? nc0 : ne0, Nside = half ? Ni : Nn;
-        if (mine && nside < Nside)
-            sj = (int)lrg_sample_position((uint32_t)j, (uint32_t)nside, (uint32_t)Nside, half ? LRG_PURPOSE_INLIER : LRG_PURPOSE_NEIGHBOR,
-                                          (uint32_t)seed0, (uint32_t)restart0, (uint32_t)step0, k0, k1);
-        const int srow = nside < Nside ? sj : j;                                              // a padded slot reads its source row
-        long row = (half ? rows_off_in : rows_off_nb) + srow;
-        if constexpr (ASYNC) {      // (a row of the side's tail: in the shared rows, where the evaluation's gather put it)
-            const int tb = half ? tail_b_in : tail_b_nb, first_tail = min(nside, Nside) & ~31;
-            if (tb >= 0 && srow >= first_tail) row = (long)a.tail_row0 + tb + (srow - first_tail);
-        }
+        int srow = 0;                                 // a padded slot reads its source row
         int idx = -1;
         int correct = 0;
         bool take = false;
         int pos = 0, own = -1;                        // the source row's position in the list it was sampled from (the gather's arithmetic), and the point there
         float px = 0.f, py = 0.f, pz = 0.f;
+        uint32_t pv_own = 0u;                         // (the slot's own point's voxel word: the test below, an added point's share of the new bounding box)
+        int vx = 0, vy = 0, vz = 0;
+        if constexpr (PREP) if (prep) {
+            // the prepared form: everything but the logits from the slot's record in LDS (lrg_front_prepare_record: the arithmetic below, done while the evaluation ran)
+            id0[0] = rec->id0[tid]; id0[1] = rec->id0[tid + LRG_FRONT_THREADS]; id0[2] = id0[3] = 0;      // (a record holds a list of up to 2048 entries)
+            pv0[0] = rec->pv0[tid]; pv0[1] = rec->pv0[tid + LRG_FRONT_THREADS]; pv0[2] = pv0[3] = 0u;
+            if (mine) {
+                const uint32_t pf = rec->pf[tid];
+                srow = (int)(pf & 511u); pos = (int)((pf >> 9) & 2047u); own = rec->own[tid]; pv_own = rec->pvo[tid];
+                const float lg[2] = {lg_pre.x, lg_pre.y};
+                long long t_lg = 0;
+                if constexpr (LRG_ASYNC_DEBUG) if (a.phase_dbg) {      // (-> logits in registers: the wait is forced here, for the stamp)
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    t_lg = wall_clock64();
+                    if (tid == 0) atomicAdd(&a.phase_dbg[10], (unsigned long long)(t_lg - t_phase));
+                }
+                const int gtf = (int)((pf >> 24) & 1u);
+                correct = (lg[1] > lg[0] ? 1 : 0) == gtf;                                    // add_acc / remove_acc (util:174-180)
+                if (prm.policy == 2) take = gtf != 0;                                        // :268-269
+                else {
+                    const float conf = lrg_conf(lg);                                         // :262-263
+                    if (prm.policy == 1) take = conf > 0.5f;                                 // :264-265
+                    else take = lrg_uniform01(rec->w[tid]) < conf;                           // :266-267
+                }
+#ifndef LRG_UPDATE_GENERAL
+                if (take && ((pf >> 25) & 1u)) SH.upd[0] = 1;      // (this step then takes the general form below, like an unprepared one)
+#else
+                if (take) SH.upd[0] = 1;
+#endif
+                if constexpr (LRG_ASYNC_DEBUG) if (a.phase_dbg) {      // (-> `take` known)
+                    asm volatile("" :: "v"((int)take) : "memory");
+                    const long long t_take = wall_clock64();
+                    if (tid == 0) atomicAdd(&a.phase_dbg[11], (unsigned long long)(t_take - t_lg));
+                }
+            }
+        }
+        if (!prep) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) id0[k] = spec ? lrg_ld_coh(&cur_idx[min(tid + k * LRG_FRONT_THREADS, nc0 - 1)]) : cur_idx[min(tid + k * LRG_FRONT_THREADS, nc0 - 1)];
+        if (mine && nside < Nside)
+            sj = (int)lrg_sample_position((uint32_t)j, (uint32_t)nside, (uint32_t)Nside, half ? LRG_PURPOSE_INLIER : LRG_PURPOSE_NEIGHBOR,
+                                          (uint32_t)seed0, (uint32_t)restart0, (uint32_t)step0, k0, k1);
+        srow = nside < Nside ? sj : j;
+        long row = (half ? rows_off_in : rows_off_nb) + srow;
+        if constexpr (ASYNC) {      // (a row of the side's tail: in the shared rows, where the evaluation's gather put it)
+            const int tb = half ? tail_b_in : tail_b_nb, first_tail = min(nside, Nside) & ~31;
+            if (tb >= 0 && srow >= first_tail) row = (long)a.tail_row0 + tb + (srow - first_tail);
+        }
         if (mine) {
             // (a padded set's rows are its members in order, a full set's the prefix of the permutation)
             pos = nside < Nside ? srow : (int)lrg_sample_position((uint32_t)srow, (uint32_t)nside, (uint32_t)Nside, half ? LRG_PURPOSE_INLIER : LRG_PURPOSE_NEIGHBOR,
@@ -1060,6 +1137,12 @@ __device__ __forceinline__ int lrg_front_greedy_slot(LrgFrontShared &SH, LrgSlot
             float lg[2];
             if constexpr (ASYNC) { const float2 t = lrg_ld_coh2(lgp); lg[0] = t.x; lg[1] = t.y; }      // (written by a tile team of this launch)
             else { lg[0] = lgp[0]; lg[1] = lgp[1]; }
+            long long t_lg = 0;
+            if constexpr (ASYNC && LRG_ASYNC_DEBUG) if (a.phase_dbg) {      // (-> logits in registers: the wait is forced here, for the stamp)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                t_lg = wall_clock64();
+                if (tid == 0) atomicAdd(&a.phase_dbg[10], (unsigned long long)(t_lg - t_phase));
+            }
             const int gtf = u.w != 0.f;
             correct = (lg[1] > lg[0] ? 1 : 0) == gtf;                                        // add_acc / remove_acc (util:174-180)
             if (prm.policy == 2) take = gtf != 0;                                            // :268-269
@@ -1069,15 +1152,19 @@ __device__ __forceinline__ int lrg_front_greedy_slot(LrgFrontShared &SH, LrgSlot
                 else take = lrg_uniform01(lrg_rng_word((uint32_t)j, half ? LRG_PURPOSE_RMV : LRG_PURPOSE_ADD, (uint32_t)seed0,
                                                        (uint32_t)restart0, (uint32_t)step0, k0, k1)) < conf;   // :266-267
             }
+            if constexpr (ASYNC && LRG_ASYNC_DEBUG) if (a.phase_dbg) {      // (-> `take` known)
+                asm volatile("" :: "v"((int)take) : "memory");
+                const long long t_take = wall_clock64();
+                if (tid == 0) atomicAdd(&a.phase_dbg[11], (unsigned long long)(t_take - t_lg));
+            }
 #ifdef LRG_SPEC_TRACE
             if (spec && j == 0) LRG_SPEC_EV(a, 5 + half, s, seed0, ((long long)__float_as_uint(lg[0]) << 32) | __float_as_uint(lg[1]), ((long long)take << 40) | ((long long)(row & 0xFFFFF) << 20) | (srow & 0xFFFFF));
 #endif
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) pv0[k] = pvox[id0[k]];
-        const uint32_t pv_own = mine ? pvox[max(own, 0)] : 0u;                                 // (the slot's own point's voxel word: the test below, an added point's share of the new bounding box)
+        pv_own = mine ? pvox[max(own, 0)] : 0u;
         // the voxel the reference looks up: the rows are stored uncentred, so (x - c) + c in float32, as it centres (:243,:246) and un-centres (:271,:275) the row
-        int vx = 0, vy = 0, vz = 0;
         if (mine && take) {
             vx = lrg_voxel_of(__fadd_rn(__fsub_rn(px, c0), c0), prm.resolution);              // :271-272 / :275-276
             vy = lrg_voxel_of(__fadd_rn(__fsub_rn(py, c1), c1), prm.resolution);
@@ -1088,6 +1175,7 @@ __device__ __forceinline__ int lrg_front_greedy_slot(LrgFrontShared &SH, LrgSlot
             SH.upd[0] = 1;
 #endif
         }
+        }      // (not prepared)
         {
             const int wsum = lrg_wave_sum_i32(correct);          // a wavefront lies in one half (512 = 8 wavefronts)
             __syncthreads();
@@ -1152,6 +1240,12 @@ __device__ __forceinline__ int lrg_front_greedy_slot(LrgFrontShared &SH, LrgSlot
             }
         } else {
         // ---- the general form: the voxel's point from the room's grid / hash, a word-wide atomicOr electing the slot that switches a point on, the mask read back ----
+        if constexpr (PREP) if (prep && mine && take) {      // (a record holds the outcome of the voxel test, not the voxel: worked out here, for the rare step that needs it)
+            const float4 u = (half ? a.upd_in : a.upd_nb)[(long)s * Nside + srow];
+            vx = lrg_voxel_of(__fadd_rn(__fsub_rn(u.x, c0), c0), prm.resolution);
+            vy = lrg_voxel_of(__fadd_rn(__fsub_rn(u.y, c1), c1), prm.resolution);
+            vz = lrg_voxel_of(u.z, prm.resolution);
+        }
         if (mine && take) idx = lrg_voxel_index(VI, vx, vy, vz);
         if (!half && idx >= 0) {                                                             // :283-285
             unsigned *w = reinterpret_cast<unsigned *>(cur + (idx & ~3));
@@ -1820,6 +1914,73 @@ __device__ __forceinline__ int lrg_front_greedy_slot(LrgFrontShared &SH, LrgSlot
     if (tid == 0 && g_lrg_trace2) { g_lrg_trace2[(long)s * 16 + 8] = nc; g_lrg_trace2[(long)s * 16 + 14] = lrg_is_stop(entry_status) || entry_status == LRG_WAIT || (entry_status == LRG_ACTIVE && S->step == 0); }
 #endif
     return (rin << 16) | rnb;
+}
+
+// The record of slot s's NEXT mask update (LrgPrepRecord), from the state the front turn that has just published the slot's evaluation left behind: the update's
+// own arithmetic and loads up to the logits, statement for statement (lrg_front_greedy_slot, "(1) mask update"), with their results stored instead of used.  Nothing
+// here waits for the evaluation and nothing it reads changes before the update: the slot's lists, its upd_* rows, its centre and its tail bases are written by
+// this workgroup's turns only.  All threads; returns 1 when the record was made (workgroup-uniform: thread 0's look at the slot, through LDS); the caller's barrier
+// follows.
+__device__ __forceinline__ int lrg_front_prepare_record(LrgPrepRecord *rec, const LrgSlot *slots, const LrgRoom *rooms, const LrgGrowParams &prm, const LrgFrontArgs &a,
+                                                        const int s) {
+    const int tid = threadIdx.x;
+    const LrgSlot *S = &slots[s];
+    if (tid == 0) {
+        const int room = S->room, nc = S->nc;
+        rec->hdr[0] = room; rec->hdr[1] = nc; rec->hdr[2] = S->ne; rec->hdr[3] = S->seed; rec->hdr[4] = S->restart; rec->hdr[5] = S->step;
+        rec->hdr[6] = (room >= 0 && S->status == LRG_ACTIVE && nc >= 1 && nc <= LRG_PREP_LIST) ? 1 : 0;
+    }
+    LRG_LDS_BARRIER();
+    if (!rec->hdr[6]) return 0;
+    const int Ni = prm.n_inlier, Nn = prm.n_neighbor;
+    const int room = rec->hdr[0], nc0 = rec->hdr[1], ne0 = rec->hdr[2], seed0 = rec->hdr[3], restart0 = rec->hdr[4], step0 = rec->hdr[5];
+    const LrgRoom *R = &rooms[room];
+    const uint32_t *pvox = R->pvox;
+    const int ox = R->vox_origin[0], oy = R->vox_origin[1], oz = R->vox_origin[2];
+    const uint32_t k0 = prm.rng_seed, k1 = (uint32_t)R->room_id;
+    const int32_t *cur_idx = S->cur_idx, *cand_idx = S->cand_idx;
+    const int rows_off_in = a.slot_rows[4 * s + 2], rows_off_nb = a.slot_rows[4 * s + 3];
+    const int tail_b_in = a.tail_base ? a.tail_base[2 * s] : -1, tail_b_nb = a.tail_base ? a.tail_base[2 * s + 1] : -1;
+    const float c0 = lrg_ld_coh(a.center + s * 16 + 0), c1 = lrg_ld_coh(a.center + s * 16 + 1);
+    const int half = tid >> 9, j = tid & 511;
+    const bool mine = j < (half ? Ni : Nn);
+    int id0[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) id0[k] = cur_idx[min(tid + k * LRG_FRONT_THREADS, nc0 - 1)];
+    const int nside = half ? nc0 : ne0, Nside = half ? Ni : Nn;
+    int sj = 0;
+    if (mine && nside < Nside)
+        sj = (int)lrg_sample_position((uint32_t)j, (uint32_t)nside, (uint32_t)Nside, half ? LRG_PURPOSE_INLIER : LRG_PURPOSE_NEIGHBOR,
+                                      (uint32_t)seed0, (uint32_t)restart0, (uint32_t)step0, k0, k1);
+    const int srow = nside < Nside ? sj : j;
+    long row = (half ? rows_off_in : rows_off_nb) + srow;
+    {
+        const int tb = half ? tail_b_in : tail_b_nb, first_tail = min(nside, Nside) & ~31;
+        if (tb >= 0 && srow >= first_tail) row = (long)a.tail_row0 + tb + (srow - first_tail);
+    }
+    int pos = 0, own = 0;
+    uint32_t pf = 0u, w = 0u, pv_own = 0u;
+    if (mine) {
+        pos = nside < Nside ? srow : (int)lrg_sample_position((uint32_t)srow, (uint32_t)nside, (uint32_t)Nside, half ? LRG_PURPOSE_INLIER : LRG_PURPOSE_NEIGHBOR,
+                                                              (uint32_t)seed0, (uint32_t)restart0, (uint32_t)step0, k0, k1);
+        own = (half ? cur_idx : cand_idx)[pos];
+        const float4 u = (half ? a.upd_in : a.upd_nb)[(long)s * Nside + srow];
+        if (prm.policy != 1 && prm.policy != 2)
+            w = lrg_rng_word((uint32_t)j, half ? LRG_PURPOSE_RMV : LRG_PURPOSE_ADD, (uint32_t)seed0, (uint32_t)restart0, (uint32_t)step0, k0, k1);
+        pv_own = pvox[max(own, 0)];
+        const int vx = lrg_voxel_of(__fadd_rn(__fsub_rn(u.x, c0), c0), prm.resolution);
+        const int vy = lrg_voxel_of(__fadd_rn(__fsub_rn(u.y, c1), c1), prm.resolution);
+        const int vz = lrg_voxel_of(u.z, prm.resolution);
+        const bool mv = vx - ox != LRG_PVX(pv_own) || vy - oy != LRG_PVY(pv_own) || vz - oz != LRG_PVZ(pv_own);
+        // (pos < 2048 on the inlier side: the list is capped; on the neighbour side only a full set's positions can lie above, and an add uses the source row alone)
+        pf = (uint32_t)srow | (((uint32_t)pos & 2047u) << 9) | (u.w != 0.f ? 1u << 24 : 0u) | (mv ? 1u << 25 : 0u);
+    } else {
+        row = 0;
+    }
+    rec->own[tid] = own; rec->row[tid] = (int)row; rec->pvo[tid] = pv_own; rec->pf[tid] = pf; rec->w[tid] = w;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) { rec->id0[tid + k * LRG_FRONT_THREADS] = id0[k]; rec->pv0[tid + k * LRG_FRONT_THREADS] = pvox[id0[k]]; }
+    return 1;
 }
 
 // The greedy front as a launch of its own (lrg_grow_step_packed): one workgroup per slot.

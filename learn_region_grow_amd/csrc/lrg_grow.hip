@@ -1957,7 +1957,10 @@ static int async_plan(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_point
     A.abort_ticks = (budget_us > 0 ? (long long)budget_us * 100 : 0) + 400000000LL;  // ... + 4 s without an end: something is broken
     A.start_ticks = ab->start_wait_us > 0 ? (long long)ab->start_wait_us * 100 : (budget_us > 0 ? (long long)budget_us * 100 : 0) + LRG_ASYNC_START_TICKS;
     static_assert(sizeof(LrgAsyncKArgs) <= 4096, "kernel arguments");
-    const size_t front_lds = ((sizeof(LrgFrontShared) + 15) & ~(size_t)15) + sizeof(LrgAsyncFrontCtl);
+    // (+ the records of the prepared mask update, lrg_front.inl: with the pooled-product units on, less than the sixteen unit workgroups need anyway)
+    const size_t front_lds = LRG_PREPARED_UPDATE ? LRG_ASYNC_FRONT_PREP_BYTES + LRG_PREP_SLOTS * sizeof(LrgPrepRecord)
+                                                 : ((sizeof(LrgFrontShared) + 15) & ~(size_t)15) + sizeof(LrgAsyncFrontCtl);
+    static_assert(LRG_ASYNC_FRONT_PREP_BYTES + LRG_PREP_SLOTS * sizeof(LrgPrepRecord) <= 160 * 1024, "a front workgroup with its records");
     // (small_alt: the odd workgroups have one small team more and one big team less -- the even ones' layout is the larger)
     const size_t team_lds = ((size_t)A.small_teams * LRG_ASYNC_SMALL_TEAM_FLOATS + (size_t)(teams - A.small_teams) * LRG_ASYNC_TEAM_FLOATS +
                              (size_t)A.fill_extra * LRG_ASYNC_FILL_TEAM_FLOATS) * sizeof(float);
