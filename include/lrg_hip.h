@@ -765,7 +765,8 @@ int lrg_gemm_f32(int M, int N, int K, const float *A, int lda, int transA, const
 /* d(loss)/d(logits) of a sparse softmax cross entropy over `rows` two-class slots with per-class weights
  * (add head :174: w_pos = w_neg = 1 / rows; remove head :166-172: 1 / #positive and 1 / #negative slots of the batch).
  * stats (device double[8], ACCUMULATED): 0 weighted loss, 1 slots with argmax == label, 2 true positives, 3 predicted
- * positives, 4 labelled positives, 5 rows (the numerators of add_acc, add_prc, add_rcl ... at :175-184). */
+ * positives, 4 labelled positives, 5 rows (the numerators of add_acc, add_prc, add_rcl ... at :175-184).  The weighted loss
+ * of a call is summed in a fixed order: the same inputs add the same bits. */
 int lrg_ce_grad(const float *logits, const int32_t *labels, long rows, float w_pos, float w_neg, float *dlogits, double *stats,
                 void *stream);
 /* Gradient of the column max over each instance's rows (:122-123) followed by the pooled layer's ReLU: y [B,rows,C] is that

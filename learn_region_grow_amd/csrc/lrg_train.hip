@@ -102,13 +102,37 @@ __global__ __launch_bounds__(256) void lrg_gemm_f32_kernel(LrgGemmArgs a) {
 // dlogits[r] = (softmax(logits[r]) - onehot(label[r])) * (label[r] ? w_pos : w_neg).  add head: w_pos = w_neg = 1 / rows
 // (:174); remove head: 1 / #positive, 1 / #negative of the batch (:166-172; an empty class contributes nothing).
 // stats (double[8], accumulated): 0 sum of weighted ce, 1 argmax == label, 2 true positives, 3 predicted positives,
-// 4 labelled positives, 5 rows.
+// 4 labelled positives, 5 rows.  The counters are integers, so the order of their atomic additions does not matter; the
+// sum of the weighted ce is a sum of roundings, and is taken in a FIXED order (lrg_ce_loss_kernel), so that two calls on the
+// same data -- backward() and evaluate() of one batch -- return the same bits.
+
+// stats[0] += sum over the rows of the weighted ce: ONE workgroup; thread t sums rows t, t + 1024, ... in that order, the
+// 1024 partial sums meet in a fixed tree.  (51 200 rows of the real step: 50 rows a thread.)
+__global__ __launch_bounds__(1024) void lrg_ce_loss_kernel(const float *logits, const int32_t *labels, long rows, float w_pos, float w_neg,
+                                                            double *stats) {
+    __shared__ double sh[1024];
+    double ce = 0.0;
+    for (long r = threadIdx.x; r < rows; r += 1024) {
+        const float l0 = logits[2 * r], l1 = logits[2 * r + 1];
+        const int y = labels[r] != 0;
+        const float m = fmaxf(l0, l1);
+        const float s = expf(l0 - m) + expf(l1 - m);
+        ce += (double)((y ? w_pos : w_neg) * (logf(s) + m - (y ? l1 : l0)));
+    }
+    sh[threadIdx.x] = ce;
+    __syncthreads();
+    for (int half = 512; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) sh[threadIdx.x] += sh[threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicAdd(&stats[0], sh[0]);
+}
+
 __global__ __launch_bounds__(256) void lrg_ce_grad_kernel(const float *logits, const int32_t *labels, long rows, float w_pos, float w_neg,
                                                            float *dlogits, double *stats) {
     __shared__ double sh[6];
     if (threadIdx.x < 6) sh[threadIdx.x] = 0.0;
     __syncthreads();
-    double ce = 0.0;
     int ok = 0, tp = 0, pp = 0, lp = 0, nr = 0;
     for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (long)gridDim.x * blockDim.x) {
         const float l0 = logits[2 * r], l1 = logits[2 * r + 1];
@@ -120,14 +144,13 @@ __global__ __launch_bounds__(256) void lrg_ce_grad_kernel(const float *logits, c
         const float w = y ? w_pos : w_neg;
         dlogits[2 * r] = (p0 - (y ? 0.f : 1.f)) * w;
         dlogits[2 * r + 1] = (p1 - (y ? 1.f : 0.f)) * w;
-        ce += (double)(w * (logf(s) + m - (y ? l1 : l0)));
         const int pred = l1 > l0;
         ok += pred == y; tp += pred & y; pp += pred; lp += y; ++nr;
     }
-    atomicAdd(&sh[0], ce); atomicAdd(&sh[1], (double)ok); atomicAdd(&sh[2], (double)tp);
+    atomicAdd(&sh[1], (double)ok); atomicAdd(&sh[2], (double)tp);
     atomicAdd(&sh[3], (double)pp); atomicAdd(&sh[4], (double)lp); atomicAdd(&sh[5], (double)nr);
     __syncthreads();
-    if (threadIdx.x < 6 && sh[threadIdx.x] != 0.0) atomicAdd(&stats[threadIdx.x], sh[threadIdx.x]);
+    if (threadIdx.x >= 1 && threadIdx.x < 6 && sh[threadIdx.x] != 0.0) atomicAdd(&stats[threadIdx.x], sh[threadIdx.x]);
 }
 
 // ---- gradient of the max-pool (:122-123) followed by the pooled layer's ReLU ----
@@ -194,6 +217,8 @@ int lrg_ce_grad(const float *logits, const int32_t *labels, long rows, float w_p
     const long blocks = (rows + 255) / 256;
     hipLaunchKernelGGL(lrg_ce_grad_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)stream, logits, labels,
                        rows, w_pos, w_neg, dlogits, stats);
+    LRG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lrg_ce_loss_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, logits, labels, rows, w_pos, w_neg, stats);
     LRG_LAUNCH_CHECK();
     return 0;
 }

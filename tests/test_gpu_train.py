@@ -19,7 +19,7 @@ def batch(rs, B, N, F):
 
 
 def test_gemm_transposes_epilogue_and_split(cuda_device, hip_lib):
-    """lrg_gemm_f32: the four operand layouts, odd sizes, addend + ReLU-mask epilogue, split reduction."""
+    """lrg_gemm_f32: three of the four operand layouts (all four, with padded strides: test_gpu_train_kernels.py), odd sizes, addend + ReLU-mask epilogue, split reduction."""
     import ctypes
     import torch
     from learn_region_grow_amd.lrgnet import _ptr, _stream_ptr
