@@ -8,7 +8,9 @@ metric lines and its aggregate line, optional PLY export.
 
 The rooms of a file go to the GPU in batches (--batch-rooms per lrg_baseline_segment call); features are computed per room
 (device equalisation and covariances, host numpy.linalg.svd: learn_region_grow_amd.baselines.room_features).  The timing line
-of a room is its feature time plus its share, by equalised points, of its batch's segmentation time.  The other modes of
+of a room is its feature time plus its share, by equalised points, of its batch's segmentation time.  --features verified solves
+the 3x3 decompositions on the GPU too and sends only the points whose labels or rank could depend on the solver through LAPACK: the
+same lines, several times faster in the modes that read normals.  The other modes of
 benchmarks.py (edge, fpfh, pointnet, pointnet2) are not ported.
 """
 import argparse
@@ -37,6 +39,9 @@ def parse(argv=None):
     ap.add_argument('--max-rooms', type=int, default=0)
     ap.add_argument('--batch-rooms', type=int, default=68, help='rooms per segmentation call')
     ap.add_argument('--device', default=None, help='default: cuda:0')
+    ap.add_argument('--features', default='lapack', choices=('lapack', 'verified'),
+                    help="3x3 decompositions: 'lapack' = numpy.linalg.svd for every point on the host; 'verified' = on the GPU, LAPACK only "
+                         'for the points the certificate names (same labels)')
     return ap.parse_args(argv)
 
 
@@ -72,7 +77,8 @@ def main(argv=None):
             feats, ftime = [], []
             for r in batch:
                 t0 = time.time()
-                feats.append(baselines.room_features(rooms[r], resolution=args.resolution, need_normals=need_normals, device=args.device))
+                feats.append(baselines.room_features(rooms[r], resolution=args.resolution, need_normals=need_normals, device=args.device,
+                                                     eig=args.features))
                 ftime.append(time.time() - t0)
             t0 = time.time()
             labels = baselines.segment(feats, args.mode, resolution=args.resolution, device=args.device, thresholds=t)

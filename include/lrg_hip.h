@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 10
+#define LRG_ABI_VERSION 11
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -702,6 +702,26 @@ int lrg_baseline_segment(const float *pts, int ld, const int32_t *room_start, in
  * 2 two points of one room in one voxel (the room is not equalised), 4 a rank outside [0, room size), 8 a replay stack
  * overflow (not reachable by the bound of DESIGN.md §3.8).  Labels are not valid when it is non-zero. */
 int lrg_baseline_status(const void *ws, int n_points, int n_rooms, int min_cluster_size, int32_t *host_status, void *stream);
+/* ABI 11.  The features of benchmarks.py:242-246 solved on the device, with a bound on their distance from numpy.linalg.svd's (DESIGN.md
+ * §3.8 "verified").  cov [n, 9] float64 as lrg_preprocess eig_mode 0 writes it, any number of rooms one after the other; one lane
+ * per point runs the Jacobi solve of lrg_preprocess eig_mode 1 (same code, same selection and tie rules).  All pointers on the device:
+ * normals [n, 3] = |V[smallest]|, curvatures [n] = |s2 / (s0 + s1 + s2)| (not divided by a maximum),
+ * normal_slack [n] = 256 eps s0 / (s1 - s2): LAPACK's normal lies within it in every component; curv_slack [n] = 256 eps likewise.
+ * Both are +inf where !(s1 - s2 > 1e-6 s0) or the curvature is NaN: no bound, the point has to go through LAPACK. */
+int lrg_baseline_eig(const double *cov, int n, double *normals, double *curvatures, double *normal_slack, double *curv_slack, void *stream);
+/* ABI 11.  Which points could change an edge of lrg_baseline_segment(mode, t1, t2, t3) if LAPACK's features replaced the device's?
+ * The inputs of lrg_baseline_segment (rank is not read and labels are not written, so neither is passed) plus the slacks of
+ * lrg_baseline_eig (0 = the value is LAPACK's own).  Every edge candidate (k < i on the 26-neighbour graph) is evaluated with the
+ * segmentation's own arithmetic; a normal conjunct is certain iff |d - t| > 2 E_n, E_n = 2 (s_i + s_k) + 3 s_i s_k + 8 eps, a
+ * curvature conjunct iff ||c_k - c_i| - t| > 2 E_c, E_c = sc_i + sc_k + 2 eps (NaN and infinity: uncertain), the colour conjunct
+ * always.  flags [n] int32 (device) = 1 for both ends of every edge with an uncertain conjunct and none certainly false, else 0;
+ * n_flagged [1] int32 (device) = their number.  After the flagged points' features are replaced by LAPACK's (slack 0) no edge can
+ * differ from the all-LAPACK outcome: one pass is enough.  normal_slack / curv_slack may be NULL when the mode does not read them.
+ * LRG_BASELINE_COLOR: flags and n_flagged are cleared, no kernel is launched.  Same workspace as lrg_baseline_segment (which may
+ * follow on it), same lrg_baseline_status. */
+int lrg_baseline_certify(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode, const double *normals,
+                         const double *curvatures, const double *normal_slack, const double *curv_slack, double t1, double t2, double t3,
+                         int min_cluster_size, void *ws, size_t ws_bytes, int32_t *flags, int32_t *n_flagged, void *stream);
 /* The edges of test_mcpnet.py:122-145 (MCPNet): emb[k].dot(emb[i]) > t on the 26-neighbour voxel graph, the dot a float64 sum of the
  * exact products double(emb[k][d]) * double(emb[i][d]) taken in order d = 0, 1, ..., dim - 1 ((p0 + p1) + p2 ...: what OpenBLAS's ddot
  * gives for n = 10).  emb [n, dim] float32 on the device, 1 <= dim <= 64.  Components of more than min_cluster_size

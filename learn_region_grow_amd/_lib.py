@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
            'lrg_baselines.hip', 'lrg_mcpnet.hip']
 
-LRG_ABI_VERSION = 10      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 11      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -260,6 +260,10 @@ _SIGS = {
                                             ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, _fp, ctypes.c_size_t,
                                             _fp, _fp, _fp]),
     'lrg_baseline_status': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp]),
+    'lrg_baseline_eig': (ctypes.c_int, [_fp, ctypes.c_int, _fp, _fp, _fp, _fp, _fp]),
+    'lrg_baseline_certify': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_float, ctypes.c_int, _fp, _fp, _fp, _fp,
+                                            ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, _fp, ctypes.c_size_t,
+                                            _fp, _fp, _fp]),
     'lrg_baseline_segment_embedding': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_float, _fp, ctypes.c_int, ctypes.c_double,
                                                       ctypes.c_int, _fp, ctypes.c_size_t, _fp, _fp, _fp]),
     'lrg_mcp_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),

@@ -6,7 +6,12 @@ Modes ``normal``, ``curvature``, ``color``, ``feature`` and ``smoothness`` (benc
 
 ``room_features``  equalisation and float64 covariances on the GPU (``lrg_preprocess`` eig_mode 0), then the reference's own
                    ``numpy.linalg.svd`` on the host (benchmarks.py:199-249): normals and UNnormalised curvatures bit for bit.
-``segment``        the labels of a batch of rooms from one call.
+                   With ``eig='verified'`` the 3x3 decompositions run on the GPU too (``lrg_baseline_eig``) with a bound on every
+                   value's distance from LAPACK's; the host redoes only the points without a bound and those whose place in
+                   ``numpy.argsort(curvatures)`` is not certain, so ``rank`` is the ``lapack`` route's.
+``segment``        the labels of a batch of rooms from one call.  Rooms from ``eig='verified'`` first go through
+                   ``lrg_baseline_certify`` with this call's mode and thresholds: the points of every edge whose outcome could differ
+                   under LAPACK get LAPACK's features, so the labels are the ``lapack`` route's.
 
 There is no CPU fallback: without the library or a GPU, ``_lib.LrgHipError`` is raised.
 """
@@ -50,10 +55,54 @@ def _device(device):
     return torch.device(device if device is not None else 'cuda:0')
 
 
-def room_features(unequalized_points, resolution=0.1, need_normals=True, device=None):
+EIG_ROUTES = ('lapack', 'verified')
+
+
+def _lapack(cov):
+    """The reference's own calls (benchmarks.py:242-246) on covariances [m, 9]: |V[2]| and |S[2] / sum(S)|, exactly the
+    expressions of the 'lapack' route (numpy.linalg.svd decomposes every matrix of a stack by itself)."""
+    _, S, V = np.linalg.svd(np.asarray(cov, dtype=np.float64).reshape(-1, 3, 3))
+    return np.fabs(V[:, 2, :]), np.fabs(S[:, 2] / (S[:, 0] + S[:, 1] + S[:, 2]))
+
+
+def _verified_finish(cov_h, normals, c, ns, cs):
+    """eig='verified' on the host: LAPACK for the points without a bound, then for both members of every neighbouring pair of the
+    sorted curvatures closer than twice the sum of their slacks (a redone point moves by at most its slack and an untouched
+    neighbour's true value lies within its own, so what is left of the gap keeps every pair's order: DESIGN.md §3.6), then
+    numpy.argsort -- a function of the comparisons' outcomes only -- of the final curvatures.  Arrays are changed in place."""
+    N = len(c)
+
+    def redo(mask):
+        idx = np.nonzero(mask)[0]
+        if len(idx):
+            normals[idx], c[idx] = _lapack(cov_h[idx])
+            ns[idx] = 0.0
+            cs[idx] = 0.0
+        return len(idx)
+    degenerate = redo(~(np.isfinite(ns) & np.isfinite(cs)))
+    s = np.argsort(c)
+    cs_s = cs[s]
+    close = np.diff(c[s]) <= 2.0 * (cs_s[1:] + cs_s[:-1])
+    near = np.zeros(N, dtype=bool)
+    near[s[1:][close]] = True
+    near[s[:-1][close]] = True
+    rank_redone = redo(near & (cs > 0.0))
+    rank = np.empty(N, dtype=np.int32)
+    rank[np.argsort(c)] = np.arange(N, dtype=np.int32)                        # :383, numpy's default (unstable) sort
+    return rank, dict(points=N, rank_redone=rank_redone, degenerate=degenerate)
+
+
+def room_features(unequalized_points, resolution=0.1, need_normals=True, device=None, eig='lapack'):
     """benchmarks.py:199-249 for one room: returns dict(points [N,6] float32 xyzrgb, normals [N,3] float64, curvatures [N] float64
     (not divided by their maximum), rank [N] int32 (position in numpy.argsort(curvatures)), equalized_idx, unequalized_idx).
-    With need_normals=False (mode 'color') normals, curvatures and rank are None."""
+    With need_normals=False (mode 'color') normals, curvatures and rank are None.
+
+    eig='lapack' (default): every decomposition by numpy.linalg.svd on the host.  eig='verified': lrg_baseline_eig on the device; the
+    dict gains cov [N,9] float64, normal_slack and curv_slack [N] float64 (how far LAPACK's value can lie from the one stored; 0
+    where LAPACK made it) and verify_stats = dict(points, rank_redone, degenerate).  rank equals the 'lapack' route's; normals and
+    curvatures are LAPACK's only where redone, and ``segment`` completes them for the mode and thresholds it is called with."""
+    if eig not in EIG_ROUTES:
+        raise ValueError('unknown eig route %r (one of %s)' % (eig, ', '.join(EIG_ROUTES)))
     lib = _lib.load()
     dev = _device(device)
     raw_np = np.ascontiguousarray(np.asarray(unequalized_points)[:, :6], dtype=np.float32)
@@ -81,6 +130,17 @@ def room_features(unequalized_points, resolution=0.1, need_normals=True, device=
                    normals=None, curvatures=None, rank=None)
         if not need_normals:
             return out
+        if eig == 'verified':
+            nrm_d = torch.empty((N, 3), dtype=torch.float64, device=dev)
+            sol = torch.empty((3, N), dtype=torch.float64, device=dev)                # curvatures, normal_slack, curv_slack
+            _lib.check(lib.lrg_baseline_eig(_ptr(cov), N, _ptr(nrm_d), _ptr(sol[0]), _ptr(sol[1]), _ptr(sol[2]), st), 'lrg_baseline_eig')
+            cov_h = cov[:N].cpu().numpy()
+            normals = nrm_d.cpu().numpy()
+            c, ns, cs = sol.cpu().numpy()
+            c, ns, cs = c.copy(), ns.copy(), cs.copy()
+            rank, stats = _verified_finish(cov_h, normals, c, ns, cs)
+            out.update(normals=normals, curvatures=c, rank=rank, cov=cov_h, normal_slack=ns, curv_slack=cs, verify_stats=stats)
+            return out
         cov_h = cov[:N].cpu().numpy().reshape(N, 3, 3)
     _, S, V = np.linalg.svd(cov_h)                                             # :242-246, the reference's own call
     out['normals'] = np.fabs(V[:, 2, :])
@@ -92,12 +152,49 @@ def room_features(unequalized_points, resolution=0.1, need_normals=True, device=
     return out
 
 
-def segment(rooms, mode, threshold=None, resolution=0.1, min_cluster_size=10, device=None, thresholds=None, return_counts=False):
+def _certify(lib, dev, rooms, room_start, n, mode, t, resolution, min_cluster_size, pts, normals, curv, ws, st, cat):
+    """lrg_baseline_certify with THIS call's mode and thresholds, then LAPACK's normals and curvatures (from room['cov']) for the
+    flagged points, written into the rooms' arrays with slack 0.  Returns the device normals / curvatures to segment with, the flags
+    per room and their counts."""
+    ns = cat('normal_slack', np.float64, 1)
+    cs = cat('curv_slack', np.float64, 1)
+    flags = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    n_flagged = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.lrg_baseline_certify(_ptr(pts), 6, room_start.ctypes.data_as(ctypes.c_void_p), len(rooms), ctypes.c_float(resolution),
+                                        _MODE_ID[mode], _ptr(normals), _ptr(curv), _ptr(ns), _ptr(cs), t[0], t[1], t[2], min_cluster_size,
+                                        _ptr(ws), ws.numel(), _ptr(flags), _ptr(n_flagged), st), 'lrg_baseline_certify')
+    total = int(n_flagged.item())
+    per_room = [np.zeros(room_start[r + 1] - room_start[r], dtype=bool) for r in range(len(rooms))]
+    if total:
+        fl = flags[:n].cpu().numpy().astype(bool)
+        assert int(fl.sum()) == total
+        for r, room in enumerate(rooms):
+            per_room[r] = fl[room_start[r]:room_start[r + 1]]
+            idx = np.nonzero(per_room[r])[0]
+            if len(idx):
+                room['normals'][idx], room['curvatures'][idx] = _lapack(np.asarray(room['cov']).reshape(-1, 9)[idx])
+                room['normal_slack'][idx] = 0.0
+                room['curv_slack'][idx] = 0.0
+        if normals is not None:
+            normals = cat('normals', np.float64, 3)
+        if curv is not None:
+            curv = cat('curvatures', np.float64, 1)
+    return normals, curv, per_room, np.array([int(f.sum()) for f in per_room], dtype=np.int64)
+
+
+def segment(rooms, mode, threshold=None, resolution=0.1, min_cluster_size=10, device=None, thresholds=None, return_counts=False,
+            return_stats=False):
     """Labels of every room in ONE lrg_baseline_segment call.
 
     rooms: list of dicts as ``room_features`` returns them (points; normals / curvatures / rank where the mode reads them).
     threshold overrides the mode's first threshold as --threshold does (:119); thresholds=(t1, t2, t3) sets all three.
-    Returns a list of int32 label arrays (0 = no cluster), and the per-room cluster counts with return_counts=True."""
+    Returns a list of int32 label arrays (0 = no cluster), and the per-room cluster counts with return_counts=True.
+
+    When EVERY room carries 'normal_slack' (room_features(..., eig='verified')), lrg_baseline_certify runs first with this mode and
+    these thresholds, and the points it flags get LAPACK's normals and curvatures from room['cov'] IN PLACE (room['normals'],
+    room['curvatures'], slacks set to 0; 'rank' is left alone: no certified pair changes order), so the labels are those of the
+    'lapack' route.  return_stats=True appends dict(flagged=[per-room count], flags=[per-room bool array]) to the result, or None
+    for rooms without the key, which take the path they always took."""
     if mode not in _MODE_ID:
         raise ValueError('unknown baseline mode %r (one of %s)' % (mode, ', '.join(MODES)))
     lib = _lib.load()
@@ -107,8 +204,11 @@ def segment(rooms, mode, threshold=None, resolution=0.1, min_cluster_size=10, de
         t[0] = float(threshold)
     if not 1 <= min_cluster_size <= MAX_MIN_CLUSTER_SIZE:
         raise ValueError('min_cluster_size must be in [1, %d]' % MAX_MIN_CLUSTER_SIZE)
+    verified = len(rooms) > 0 and all(r.get('normal_slack') is not None for r in rooms)
+    stats = None
     if len(rooms) == 0:
-        return ([], np.zeros(0, np.int32)) if return_counts else []
+        res = ([], np.zeros(0, np.int32)) if return_counts else ([],)
+        return res + (None,) if return_stats else (res if return_counts else [])
     sizes = [len(r['points']) for r in rooms]
     room_start = np.zeros(len(rooms) + 1, dtype=np.int32)
     room_start[1:] = np.cumsum(sizes)
@@ -127,9 +227,17 @@ def segment(rooms, mode, threshold=None, resolution=0.1, min_cluster_size=10, de
         curv = cat('curvatures', np.float64, 1) if need_c else None
         rank = cat('rank', np.int32, 1) if mode == 'smoothness' else None
         ws = torch.empty(max(1, lib.lrg_baseline_workspace_bytes(n, len(rooms), min_cluster_size)), dtype=torch.uint8, device=dev)
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if verified:
+            if need_n or need_c:
+                normals, curv, per_room, flagged = _certify(lib, dev, rooms, room_start, n, mode, t, resolution, min_cluster_size, pts,
+                                                            normals, curv, ws, st, cat)
+            else:                                                   # 'color' reads no solved value: nothing to certify
+                per_room = [np.zeros(k, dtype=bool) for k in sizes]
+                flagged = np.zeros(len(rooms), dtype=np.int64)
+            stats = dict(flagged=flagged, flags=per_room)
         labels = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         counts = torch.empty(len(rooms), dtype=torch.int32, device=dev)
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         _lib.check(lib.lrg_baseline_segment(_ptr(pts), 6, room_start.ctypes.data_as(ctypes.c_void_p), len(rooms), ctypes.c_float(resolution),
                                             _MODE_ID[mode], _ptr(normals), _ptr(curv), _ptr(rank), t[0], t[1], t[2], min_cluster_size,
                                             _ptr(ws), ws.numel(), _ptr(labels), _ptr(counts), st), 'lrg_baseline_segment')
@@ -140,4 +248,7 @@ def segment(rooms, mode, threshold=None, resolution=0.1, min_cluster_size=10, de
         lab = labels[:n].cpu().numpy()
         cnt = counts.cpu().numpy()
     out = [lab[room_start[r]:room_start[r + 1]] for r in range(len(rooms))]
-    return (out, cnt) if return_counts else out
+    res = (out, cnt) if return_counts else (out,)
+    if return_stats:
+        return res + (stats,)
+    return res if return_counts else out

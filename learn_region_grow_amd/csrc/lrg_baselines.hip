@@ -15,6 +15,10 @@
 //   scan     exclusive scan of the flags (three launches); per-room ids are differences of the global scan
 //   label    label[i] = scan[key of i's component] - scan[room start] + 1 if kept, else 0; n_clusters per room
 //
+// Features solved on the device (DESIGN §3.8 "verified"): lrg_baseline_eig is prep_jacobi3 on every covariance with a bound on each
+// value's distance from LAPACK's, and lrg_baseline_certify (init, insert, certify, tally) flags both ends of every edge whose
+// predicate could come out differently within those bounds, so that only they go through LAPACK on the host.
+//
 // Visibility (MI355X: per-XCD L2s are not coherent).  Inside the union launch every parent word is read with an agent-scope
 // relaxed atomic load (global_load sc1: never from a stale L1) and changed only by agent-scope CAS, which is performed at the
 // device's coherence point.  Correctness needs only that CAS: parents only ever decrease, so a value read late is still an
@@ -22,6 +26,7 @@
 // continues from the value the CAS returned.  Every other cross-workgroup read (hash values, final parents, sizes, keys,
 // flags, scans) is separated from its writes by a launch boundary.
 #include "lrg_common.h"
+#include "lrg_eig3.h"
 
 #define BL_THREADS 256
 #define BL_SCAN_ITEMS 8                       // per thread: 2048 elements per block
@@ -78,6 +83,7 @@ struct BlArgs {
     int32_t *ckey, *visited, *flag, *scan, *bsum, *stack, *scal;
     long hslots, stack_cap;
     int32_t *labels, *n_clusters;
+    const double *nslack, *cslack; int32_t *cflags, *n_flagged;       // lrg_baseline_certify only (NULL otherwise)
 };
 
 // Bounds of room r (room_start was checked on the host: this only keeps a bad word from turning into an address)
@@ -97,14 +103,15 @@ __device__ __forceinline__ void bl_segment(const BlArgs &a, int r, int s, int e,
 }
 
 // normals[k].dot(normals[i]) as OpenBLAS's ddot computes it for n = 3: fma(a2, b2, fma(a1, b1, a0 * b0))
-__device__ __forceinline__ bool bl_normal_edge(const double *nrm, int i, int k, double t) {
+__device__ __forceinline__ double bl_normal_dot(const double *nrm, int i, int k) {
     const double *a = nrm + 3L * k, *b = nrm + 3L * i;
-    const double d = __fma_rn(a[2], b[2], __fma_rn(a[1], b[1], __dmul_rn(a[0], b[0])));
-    return d > t;
+    return __fma_rn(a[2], b[2], __fma_rn(a[1], b[1], __dmul_rn(a[0], b[0])));
 }
+__device__ __forceinline__ bool bl_normal_edge(const double *nrm, int i, int k, double t) { return bl_normal_dot(nrm, i, k) > t; }
 
 // abs(curvatures[k] - curvatures[i]) < t in float64
-__device__ __forceinline__ bool bl_curv_edge(const double *c, int i, int k, double t) { return fabs(__dsub_rn(c[k], c[i])) < t; }
+__device__ __forceinline__ double bl_curv_diff(const double *c, int i, int k) { return fabs(__dsub_rn(c[k], c[i])); }
+__device__ __forceinline__ bool bl_curv_edge(const double *c, int i, int k, double t) { return bl_curv_diff(c, i, k) < t; }
 
 // numpy.sum((p[k,3:6] - p[i,3:6])**2) < t on float32 rows: squares rounded to float32, summed (d0 + d1) + d2, compared with
 // float32(t) (NumPy 2 casts the Python float to the array's dtype).  No contraction.
@@ -170,6 +177,10 @@ __global__ __launch_bounds__(BL_THREADS) void bl_init_kernel(BlArgs a) {
     if (t < a.hslots) { a.keys[t] = LRG_HASH_EMPTY; a.vals[t] = -1; }
     if (t < 64) a.scal[t] = 0;
     if (t <= a.n) a.flag[t] = 0;
+    if (a.cflags) {
+        if (t < a.n) a.cflags[t] = 0;
+        if (t == 0) *a.n_flagged = 0;
+    }
     if (t >= a.n) return;
     const int i = (int)t;
     int lo = 0, hi = a.n_rooms - 1;                // the last r with room_start[r] <= i
@@ -229,6 +240,95 @@ __global__ __launch_bounds__(BL_THREADS) void bl_union_kernel(BlArgs a) {
                 if (k < 0 || k >= i) continue;
                 if (bl_edge(a, i, k)) bl_union(a.parent, i, k);
             }
+}
+
+// ---- the edge certificate (lrg_baseline_certify) ----
+#define BL_EPS 2.220446049250313e-16
+enum { BL_CERT_FALSE = 0, BL_CERT_TRUE = 1, BL_UNCERTAIN = 2 };
+
+// The device's normals lie within s_i, s_k (per component) of LAPACK's, components in [0, 1]: the dot products differ by at most
+// sqrt 3 (s_i + s_k) + 3 s_i s_k plus the FMA chain's own rounding, below E_n = 2 (s_i + s_k) + 3 s_i s_k + 8 eps.  The outcome
+// d > t is certain when d is further than 2 E_n from t: one E_n for the solver, one for an edge whose other end has been replaced by
+// LAPACK's value since.  Infinite slack or a NaN anywhere fails the comparison: uncertain.
+__device__ __forceinline__ int bl_normal_conjunct(const BlArgs &a, int i, int k, double t) {
+    const double d = bl_normal_dot(a.normals, i, k), si = a.nslack[i], sk = a.nslack[k];
+    const double e = __dadd_rn(__dadd_rn(__dmul_rn(2.0, __dadd_rn(si, sk)), __dmul_rn(__dmul_rn(3.0, si), sk)), 8.0 * BL_EPS);
+    if (!(fabs(__dsub_rn(d, t)) > __dmul_rn(2.0, e))) return BL_UNCERTAIN;
+    return d > t ? BL_CERT_TRUE : BL_CERT_FALSE;
+}
+
+// | |c_k - c_i| - t | > 2 E_c, E_c = sc_i + sc_k + 2 eps
+__device__ __forceinline__ int bl_curv_conjunct(const BlArgs &a, int i, int k, double t) {
+    const double v = bl_curv_diff(a.curv, i, k);
+    const double e = __dadd_rn(__dadd_rn(a.cslack[i], a.cslack[k]), 2.0 * BL_EPS);
+    if (!(fabs(__dsub_rn(v, t)) > __dmul_rn(2.0, e))) return BL_UNCERTAIN;
+    return v < t ? BL_CERT_TRUE : BL_CERT_FALSE;
+}
+
+// could the edge (i, k) come out differently under LAPACK?  At least one conjunct uncertain and none certainly false.
+__device__ __forceinline__ bool bl_edge_uncertain(const BlArgs &a, int i, int k) {
+    switch (a.mode) {
+    case BL_NORMAL: case BL_SMOOTHNESS: return bl_normal_conjunct(a, i, k, a.t1) == BL_UNCERTAIN;
+    case BL_CURVATURE: return bl_curv_conjunct(a, i, k, a.t1) == BL_UNCERTAIN;
+    default: {                                                 // BL_FEATURE; the colour conjunct is float32 arithmetic on the raw data: certain
+        const int cn = bl_normal_conjunct(a, i, k, a.t1), cc = bl_curv_conjunct(a, i, k, a.t2);
+        if (cn == BL_CERT_FALSE || cc == BL_CERT_FALSE || !bl_color_edge(a.pts, a.ld, i, k, (float)a.t3)) return false;
+        return cn == BL_UNCERTAIN || cc == BL_UNCERTAIN;
+    }
+    }
+}
+
+// the walk of bl_union_kernel; both ends of an uncertain edge get a 1 (every writer of a word writes the same value)
+__global__ __launch_bounds__(BL_THREADS) void bl_certify_kernel(BlArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const int r = a.room_of[i];
+    if (r < 0) return;
+    int s, e;
+    if (!bl_room(a, r, &s, &e)) return;
+    uint64_t *keys; int32_t *vals; int mask;
+    bl_segment(a, r, s, e, &keys, &vals, &mask);
+    const float *p = a.pts + (long)i * a.ld;
+    const int vx = lrg_voxel_of(p[0], a.res), vy = lrg_voxel_of(p[1], a.res), vz = lrg_voxel_of(p[2], a.res);
+    for (int dx = -1; dx <= 1; ++dx)
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dz = -1; dz <= 1; ++dz) {
+                if (!dx && !dy && !dz) continue;
+                const int k = lrg_hash_lookup(keys, vals, mask, lrg_pack_voxel(vx + dx, vy + dy, vz + dz));
+                if (k < 0 || k >= i) continue;
+                if (bl_edge_uncertain(a, i, k)) { a.cflags[i] = 1; a.cflags[k] = 1; }
+            }
+}
+
+// n_flagged = the number of flagged points (the flags are final: a launch boundary lies between)
+__global__ __launch_bounds__(BL_THREADS) void bl_tally_kernel(BlArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int f = i < a.n ? a.cflags[i] != 0 : 0;
+    const int c = __popcll(__ballot(f));
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(a.n_flagged, c);
+}
+
+// One lane per covariance: prep_jacobi3, the selection of prep_cov_kernel, and how far LAPACK's values can lie from these.
+__global__ __launch_bounds__(BL_THREADS) void bl_eig_kernel(const double *cov, int n, double *normals, double *curv, double *nslack,
+                                                            double *cslack) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    double C[9], w[3], V[3][3];
+    for (int k = 0; k < 9; ++k) C[k] = cov[(long)e * 9 + k];
+    prep_jacobi3(C, w, V);
+    const double s[3] = {fabs(w[0]), fabs(w[1]), fabs(w[2])};
+    int i0, i1, i2;
+    prep_eig_order(s, &i0, &i1, &i2);
+    for (int k = 0; k < 3; ++k) normals[(long)e * 3 + k] = fabs(V[i2][k]);
+    const double cv = fabs(s[i2] / (s[i0] + s[i1] + s[i2]));
+    curv[e] = cv;
+    // the vector of the smallest singular value moves by the perturbation over the gap to the next one; a (near-)degenerate pair or
+    // a NaN curvature has no bound
+    const double gap = s[i1] - s[i2];
+    const bool bounded = gap > 1e-6 * s[i0] && cv == cv;
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    nslack[e] = bounded ? PREP_EIG_SLACK * s[i0] / gap : inf;
+    cslack[e] = bounded ? PREP_EIG_SLACK : inf;
 }
 
 // every point's root (written back: the parents are final after the union launch), sizes, smoothness keys
@@ -374,12 +474,12 @@ size_t lrg_baseline_workspace_bytes(int n_points, int n_rooms, int min_cluster_s
 
 }  // extern "C"
 
-// lrg_baseline_segment and lrg_baseline_segment_embedding: the same checks and the same nine launches
-static int bl_segment_impl(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode,
-                           const double *normals, const double *curvatures, const int32_t *rank, const float *emb, int dim, double t1,
-                           double t2, double t3, int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters,
-                           void *stream) {
-    LrgBaselineLayout L;
+// The checks and the argument block that lrg_baseline_segment, lrg_baseline_segment_embedding and lrg_baseline_certify share
+// (room_start is copied to the workspace on the stream)
+static int bl_setup(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode, const double *normals,
+                    const double *curvatures, const int32_t *rank, const float *emb, int dim, double t1, double t2, double t3,
+                    int min_cluster_size, void *ws, size_t ws_bytes, bool need_rank, bool have_outputs, hipStream_t st, LrgBaselineLayout *Lout, BlArgs *out) {
+    LrgBaselineLayout &L = *Lout;
     if (n_rooms < 1 || n_rooms > (1 << 20) || !room_start || room_start[0] != 0) return LRG_EINVAL - 73;
     for (int r = 0; r < n_rooms; ++r)
         if (room_start[r + 1] < room_start[r]) return LRG_EINVAL - 73;
@@ -388,14 +488,13 @@ static int bl_segment_impl(const float *pts, int ld, const int32_t *room_start, 
     if (rc) return rc;
     if (mode < BL_NORMAL || mode > BL_EMBEDDING) return LRG_EINVAL - 72;
     if (mode == BL_EMBEDDING && (!emb || dim < 1 || dim > 64)) return LRG_EINVAL - 74;
-    if (!ws || !labels || !n_clusters) return LRG_EINVAL - 73;
+    if (!ws || !have_outputs) return LRG_EINVAL - 73;
     if (n_points > 0 && (!pts || ld < 6)) return LRG_EINVAL - 73;
     const bool need_n = mode == BL_NORMAL || mode == BL_FEATURE || mode == BL_SMOOTHNESS;
     const bool need_c = mode == BL_CURVATURE || mode == BL_FEATURE;
-    if ((need_n && !normals) || (need_c && !curvatures) || (mode == BL_SMOOTHNESS && !rank)) return LRG_EINVAL - 74;
+    if ((need_n && !normals) || (need_c && !curvatures) || (need_rank && mode == BL_SMOOTHNESS && !rank)) return LRG_EINVAL - 74;
     if (ws_bytes < L.total || ((uintptr_t)ws & 255)) return LRG_EINVAL - 75;
     if (!(resolution > 0.f)) return LRG_EINVAL - 76;
-    hipStream_t st = (hipStream_t)stream;
     char *w = static_cast<char *>(ws);
     BlArgs a;
     int32_t *rooms = reinterpret_cast<int32_t *>(w + L.rooms);     // a device copy of room_start (the caller's is host memory)
@@ -409,9 +508,31 @@ static int bl_segment_impl(const float *pts, int ld, const int32_t *room_start, 
     a.flag = reinterpret_cast<int32_t *>(w + L.flag); a.scan = reinterpret_cast<int32_t *>(w + L.scan);
     a.bsum = reinterpret_cast<int32_t *>(w + L.bsum); a.stack = reinterpret_cast<int32_t *>(w + L.stack);
     a.scal = reinterpret_cast<int32_t *>(w + L.scal); a.hslots = L.hslots; a.stack_cap = L.stack_cap;
-    a.labels = labels; a.n_clusters = n_clusters;
+    a.labels = nullptr; a.n_clusters = nullptr;
+    a.nslack = nullptr; a.cslack = nullptr; a.cflags = nullptr; a.n_flagged = nullptr;
+    *out = a;
+    return 0;
+}
+
+static inline int bl_init_grid(const LrgBaselineLayout &L, int n_points) {
     const long init_n = L.hslots > (long)n_points + 64 ? L.hslots : (long)n_points + 64;
-    const int gi = (int)((init_n + BL_THREADS - 1) / BL_THREADS);
+    return (int)((init_n + BL_THREADS - 1) / BL_THREADS);
+}
+
+// lrg_baseline_segment and lrg_baseline_segment_embedding: the same checks and the same nine launches
+static int bl_segment_impl(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode,
+                           const double *normals, const double *curvatures, const int32_t *rank, const float *emb, int dim, double t1,
+                           double t2, double t3, int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters,
+                           void *stream) {
+    LrgBaselineLayout L;
+    BlArgs a;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = bl_setup(pts, ld, room_start, n_rooms, resolution, mode, normals, curvatures, rank, emb, dim, t1, t2, t3, min_cluster_size, ws,
+                      ws_bytes, true, labels && n_clusters, st, &L, &a);
+    if (rc) return rc;
+    const int n_points = a.n;
+    a.labels = labels; a.n_clusters = n_clusters;
+    const int gi = bl_init_grid(L, n_points);
     const int gn = (int)(((long)(n_points > n_rooms ? n_points : n_rooms) + BL_THREADS - 1) / BL_THREADS);
     hipLaunchKernelGGL(bl_init_kernel, dim3(gi), dim3(BL_THREADS), 0, st, a);
     if (n_points > 0) {
@@ -443,6 +564,47 @@ int lrg_baseline_segment_embedding(const float *pts, int ld, const int32_t *room
                                    int32_t *n_clusters, void *stream) {
     return bl_segment_impl(pts, ld, room_start, n_rooms, resolution, BL_EMBEDDING, nullptr, nullptr, nullptr, emb, dim, t, 0.0, 0.0,
                            min_cluster_size, ws, ws_bytes, labels, n_clusters, stream);
+}
+
+int lrg_baseline_eig(const double *cov, int n, double *normals, double *curvatures, double *normal_slack, double *curv_slack, void *stream) {
+    if (n < 0 || n > (1 << 26)) return LRG_EINVAL - 77;
+    if (n == 0) return 0;
+    if (!cov || !normals || !curvatures || !normal_slack || !curv_slack) return LRG_EINVAL - 77;
+    hipLaunchKernelGGL(bl_eig_kernel, dim3((n + BL_THREADS - 1) / BL_THREADS), dim3(BL_THREADS), 0, (hipStream_t)stream, cov, n, normals,
+                       curvatures, normal_slack, curv_slack);
+    LRG_LAUNCH_CHECK();
+    return 0;
+}
+
+int lrg_baseline_certify(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode, const double *normals,
+                         const double *curvatures, const double *normal_slack, const double *curv_slack, double t1, double t2, double t3,
+                         int min_cluster_size, void *ws, size_t ws_bytes, int32_t *flags, int32_t *n_flagged, void *stream) {
+    LrgBaselineLayout L;
+    BlArgs a;
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == BL_EMBEDDING) return LRG_EINVAL - 72;
+    int rc = bl_setup(pts, ld, room_start, n_rooms, resolution, mode, normals, curvatures, nullptr, nullptr, 0, t1, t2, t3, min_cluster_size,
+                      ws, ws_bytes, false, flags && n_flagged, st, &L, &a);
+    if (rc) return rc;
+    const int n_points = a.n;
+    if (mode == BL_COLOR) {                                        // float32 arithmetic on the raw data: nothing to certify, nothing launched
+        if (n_points > 0) LRG_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)n_points * sizeof(int32_t), st));
+        LRG_HIP_CHECK(hipMemsetAsync(n_flagged, 0, sizeof(int32_t), st));
+        LRG_HIP_CHECK(hipMemsetAsync(a.scal, 0, sizeof(int32_t), st));
+        return 0;
+    }
+    const bool need_n = mode != BL_CURVATURE, need_c = mode == BL_CURVATURE || mode == BL_FEATURE;
+    if ((need_n && !normal_slack) || (need_c && !curv_slack)) return LRG_EINVAL - 74;
+    a.nslack = normal_slack; a.cslack = curv_slack; a.cflags = flags; a.n_flagged = n_flagged;
+    const int gn = (n_points + BL_THREADS - 1) / BL_THREADS;
+    hipLaunchKernelGGL(bl_init_kernel, dim3(bl_init_grid(L, n_points)), dim3(BL_THREADS), 0, st, a);
+    if (n_points > 0) {
+        hipLaunchKernelGGL(bl_insert_kernel, dim3(gn), dim3(BL_THREADS), 0, st, a);
+        hipLaunchKernelGGL(bl_certify_kernel, dim3(gn), dim3(BL_THREADS), 0, st, a);
+        hipLaunchKernelGGL(bl_tally_kernel, dim3(gn), dim3(BL_THREADS), 0, st, a);
+    }
+    LRG_LAUNCH_CHECK();
+    return 0;
 }
 
 int lrg_baseline_status(const void *ws, int n_points, int n_rooms, int min_cluster_size, int32_t *host_status, void *stream) {

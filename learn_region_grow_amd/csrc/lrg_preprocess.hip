@@ -9,6 +9,7 @@
 // bit-exact features), eig_mode 1 solves them here with a cyclic Jacobi iteration in float64 (|error| ~ 1e-16 |cov|:
 // features agree to float32 rounding, documented tolerance in tests/test_gpu_preprocess.py).
 #include "lrg_common.h"
+#include "lrg_eig3.h"
 
 #define PREP_THREADS 256
 #define PREP_SCAN_ITEMS 8                      // per thread: 2048 elements per block
@@ -188,39 +189,6 @@ __global__ void prep_sort_lists_kernel(const int32_t *hash_off, const int32_t *c
     }
 }
 
-#define PREP_EIG_SLACK (256.0 * 2.220446049250313e-16)
-// Eigen-decomposition of a symmetric 3x3 matrix, cyclic Jacobi in float64.  w: eigenvalues, V[k][:]: eigenvector k.
-__device__ void prep_jacobi3(const double *c, double *w, double (*V)[3]) {
-    double a[3][3] = {{c[0], c[1], c[2]}, {c[1], c[4], c[5]}, {c[2], c[5], c[8]}};
-    double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};             // columns = eigenvectors
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        const double off = fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[1][2]);
-        const double diag = fabs(a[0][0]) + fabs(a[1][1]) + fabs(a[2][2]);
-        if (off == 0.0 || off <= 1e-300 || off < 1e-22 * diag) break;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                const double apq = a[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-                const int r = 3 - p - q;
-                const double app = a[p][p], aqq = a[q][q], arp = a[r][p], arq = a[r][q];
-                a[p][p] = app - t * apq;
-                a[q][q] = aqq + t * apq;
-                a[p][q] = a[q][p] = 0.0;
-                a[r][p] = a[p][r] = cs * arp - sn * arq;
-                a[r][q] = a[q][r] = sn * arp + cs * arq;
-                for (int k = 0; k < 3; ++k) {
-                    const double vkp = v[k][p], vkq = v[k][q];
-                    v[k][p] = cs * vkp - sn * vkq;
-                    v[k][q] = sn * vkp + cs * vkq;
-                }
-            }
-    }
-    for (int k = 0; k < 3; ++k) { w[k] = a[k][k]; V[k][0] = v[0][k]; V[k][1] = v[1][k]; V[k][2] = v[2][k]; }
-}
-
 // covariance of the raw points in the 27 voxels around every equalised point (:144-157), then normal and curvature (:158-161)
 __global__ __launch_bounds__(PREP_THREADS) void prep_cov_kernel(const float *raw, int ld, float res, const int32_t *equalized_idx,
                                                               const int32_t *scal_n, const uint64_t *keys, const int32_t *hash_off,
@@ -272,13 +240,8 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_cov_kernel(const float *raw
     prep_jacobi3(C, w, V);
     // singular values of a symmetric matrix = |eigenvalues|, descending; V[2] belongs to the smallest (:158-159)
     double s[3] = {fabs(w[0]), fabs(w[1]), fabs(w[2])};
-    int i0 = 0, i2 = 0;
-    if (s[1] > s[i0]) i0 = 1;
-    if (s[2] > s[i0]) i0 = 2;
-    if (s[1] < s[i2]) i2 = 1;
-    if (s[2] <= s[i2]) i2 = 2;
-    if (i0 == i2) { i0 = 0; i2 = 2; }                                                               // all equal
-    const int i1 = 3 - i0 - i2;
+    int i0, i1, i2;
+    prep_eig_order(s, &i0, &i1, &i2);
     normal[(long)e * 3 + 0] = fabs(V[i2][0]); normal[(long)e * 3 + 1] = fabs(V[i2][1]); normal[(long)e * 3 + 2] = fabs(V[i2][2]);
     const double cv = fabs(s[i2] / (s[i0] + s[i1] + s[i2]));                                         // S[2]/(S[0]+S[1]+S[2]) (:160-161)
     curv[e] = cv;
