@@ -132,6 +132,15 @@ class LrgHipError(RuntimeError):
     pass
 
 
+def hipcc_and_flags():
+    """The compiler and the flags of every translation unit (and of tools/async_plan_table.hip, which tests/test_async_plan.py builds)."""
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    # -ffp-contract=off: no implicit FMA fusion, so the kernels that restate NumPy float32 arithmetic (voxel keys,
+    # fill-in distances, ball query) round exactly like the reference; hot loops use explicit fmaf / MFMA.
+    flags = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC'] + os.environ.get('LRG_HIPCC_FLAGS', '').split()
+    return hipcc, flags
+
+
 def build(verbose=False):
     """hipcc --offload-arch=gfx950 -> learn_region_grow_amd/liblrg_hip.so (cross-compiles without a GPU).
     One object per translation unit (csrc/build/, compiled side by side, only the stale ones), then one link."""
@@ -140,10 +149,7 @@ def build(verbose=False):
     headers = sorted(glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(CSRC, '*.inl'))) + \
         [os.path.join(os.path.dirname(HERE), 'include', 'lrg_hip.h')]
     hnew = max(os.path.getmtime(h) for h in headers)
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    # -ffp-contract=off: no implicit FMA fusion, so the kernels that restate NumPy float32 arithmetic (voxel keys,
-    # fill-in distances, ball query) round exactly like the reference; hot loops use explicit fmaf / MFMA.
-    flags = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC'] + os.environ.get('LRG_HIPCC_FLAGS', '').split()
+    hipcc, flags = hipcc_and_flags()
     bdir = os.path.join(CSRC, 'build')
     os.makedirs(bdir, exist_ok=True)
     stamp = os.path.join(bdir, 'flags.txt')

@@ -42,23 +42,7 @@
 #ifndef LRG_ASYNC_FD
 #define LRG_ASYNC_FD 4              // depth of the tile teams' weight ring (k-groups in flight)
 #endif
-#define LRG_AQ_TAIL 0            // control words of the queue (ints), one 64-byte line each; ring 1 (pooled blocks and head tiles when
-#define LRG_AQ_HEAD 16           // the workgroups run more than one team): + LRG_AQ_SECOND
-#define LRG_AQ_FRONTS_DONE 32
-#define LRG_AQ_ABORT 48
-#define LRG_AQ_SECOND 64
-#define LRG_AQ_GTAIL 96          // entries written to the pooled-product units' ring so far
-#define LRG_AQ_ARRIVED 112       // workgroups of this launch that have started (the start rendezvous of the front workgroups)
-#ifndef LRG_ASYNC_START_TICKS
-#define LRG_ASYNC_START_TICKS 2000000LL      // 20 ms (wall_clock64: 100 MHz): by then every workgroup of the launch has started, or never will while the others wait
-#endif
-#define LRG_AQ_FTAIL 128         // the fill-in ring (tasks of the in-launch 1-NN fill-in, test_region_grow.py:308-316): entries reserved / taken
-#define LRG_AQ_FHEAD 144
-#define LRG_AQ_RING 192          // ring 0, then ring 1 (qmask + 1 entries each), then the units' ring (gmask + 1 entries), then the fill-in ring (fmask + 1)
-#define LRG_ASYNC_FILL_RING 8192 // entries of the fill-in ring: one per 256 candidate points of a finished room (a 131 072-point scene: 512)
-// behind the fill-in ring: the wave rings' control words (ring t = side * 4 + quarter: [32 t] entries reserved, [32 t + 16] tickets taken) and the eight rings
-#define LRG_AQ_WAVE(A) (LRG_AQ_RING + 2 * ((A).qmask + 1) + ((A).gmask + 1) + LRG_ASYNC_FILL_RING)
-#define LRG_AQ_WAVE_RING(A, t) (LRG_AQ_WAVE(A) + 256 + (t) * ((A).wmask + 1))
+// (the queue's control words and rings, LRG_AQ_*, and LrgAsyncArgs: lrg_async_plan.h)
 #define LRG_WORKER_THREADS 512   // workgroup of lrg_grow_async_worker_kernel
 #define LRG_TASK_FILL 4
 #define LRG_ASYNC_SYNC_WORDS 16  // per slot: 0 branch tiles done, 1 pooled-product blocks done, 2 head tiles done (arrival counters); 4 .. 7 one 16-byte word written by
@@ -80,81 +64,6 @@
 // (lrg_async_fill_chunk: 256 x 13 + 256 + 4 x 64 x 2 floats): three tile teams and it are 150 KB
 #define LRG_ASYNC_FILL_TEAM_FLOATS (LRG_NN1_C * 13 + LRG_NN1_C + 4 * 64 * 2 + 8 + LRG_ASYNC_CTL_FLOATS)
 
-struct LrgAsyncArgs {
-    LrgFusedProb prob[4];        // 0 inlier branch, 1 neighbour branch, 2 add head (neighbour rows), 3 remove head (inlier rows)
-    LrgGemvArgs gemv;
-    LrgFrontArgs front;
-    int32_t *queue;              // control words + ring
-    int32_t *sync;               // [n_slots, LRG_ASYNC_SYNC_WORDS]
-    int32_t *big;
-    int32_t *room_queue;         // nullable: [0] rooms handed out so far, [1] rooms queued, [2 + k] = room index | reset << 30
-    int qmask;                   // ring entries - 1 (power of two)
-    int gmask;                   // entries of the pooled-product units' ring - 1 (power of two, at least 2 n_slots)
-    int gemv_batch;              // > 1 (without the units): pooled products in batches of up to so many slots (LRG_GEMV_BATCH) -- the slots whose branch tiles are all in
-                                 // queue up in the (otherwise unused) units' ring; a batch's blocks stream the kernels' 128 columns ONCE for all its slots
-    long long gemv_batch_ticks;  // a batch that is not full that long after its leader task was taken is closed with the slots it has
-    int gemv_units;              // workgroups n_front .. n_front + gemv_units - 1 hold 32 columns each of the heads' pooled kernels in LDS (0: the
-                                 // pooled product is a task of the tile teams, 128 columns each)
-    int n_slots, n_front, teams;
-    int head_ring;               // the ring pooled blocks and head tiles are published to: 1, or 0 = one ring for all tasks and all teams
-    int ring0_halves;            // more than one team per workgroup: team t of worker workgroup w runs branch tiles (ring 0) if 2 t + (w & 1) < ring0_halves,
-                                 // else pooled blocks and head tiles (ring 1) -- 2: the first team everywhere, 3: one and a half teams on average, ...
-    // in-launch fill-in (nullable: fill_list == nullptr -> the host fills finished rooms in between launches)
-    int32_t *fill_list;          // [points of all rooms] per room (at the room's offset in the arenas): indices of its unlabeled points
-    unsigned long long *fill_best;   // [points of all rooms] best (distance bits << 32 | index) per point
-    int32_t *fill_sync;          // [n_rooms, 4]: unlabeled points, candidate chunks done, chunks in all, filled
-    const int32_t *fill_label_base;  // the label arena (LrgRoom.label points into it) and the filled-label arena of the same layout
-    int32_t *fill_out_base;
-    int fill_wgs;                // the last team of the first fill_wgs worker workgroups serves the fill-in ring only
-    int small_teams;             // the first so many teams of a worker workgroup run branch tiles only, on the smaller LDS region (four teams per workgroup)
-    int small_alt;               // 1: ... and one more of them on the odd workgroups
-    int fill_extra;              // 1: ... and that team is one more than the other workgroups have (where LDS and threads allow: up to three tile teams)
-    int fill_hybrid;             // 1: four tile teams per CU, the fill-in team is one of them: it takes a fill-in task when one is waiting and ring 1's next task otherwise
-    // Shared tail tiles (nullable: tail == nullptr -> every slot pads its own last tile).  A slot's rows beyond its last full 32-row tile -- 16 of 91 rows per side
-    // on average: 18 % of all tile rows were such padding -- are reserved from a cursor per side in rows that all slots share (LrgFrontArgs.tail_*), so that the
-    // tails of several slots fill one BRANCH tile: the tile code's packed form (runs of rows of one slot each: per-run max-pool, lrg_forward_packed's arithmetic bit
-    // for bit).  A tile is published by whoever brings its count of written rows to 32; a slot whose last tile stays open longer than tail_ticks closes it (the
-    // cursor is moved to the tile's end, the missing rows count as dead).  The HEAD stack of a tail stays a tile of the slot's own: it reads the slot's conv[1] rows
-    // where the shared tile left them and stores the logits of the slot's rows only (lrg_fused_tile: nrows_out).
-    int32_t *tail;               // [0] / [16] the sides' row cursors (= LrgFrontArgs.tail_cur); [32 + side * tail_tiles + tile] rows accounted for | dead rows << 16
-    int tail_tiles;              // shared tiles per side
-    int tail_heads;              // 1 (without the units): the HEAD stacks of the tails run on the shared tiles too -- a shared tile's head task is published when the
-                                 // pooled products of ALL slots with rows in it are complete ([32 + 2 * tail_tiles + side * tail_tiles + tile]: slots ready | the
-                                 // tile's slots << 16); 0: a head tile of the slot's own per tail, storing its rows only
-    long long tail_ticks;        // (wall_clock64: 100 MHz)
-    float *pool_rows;            // nullable (with the units): [n_slots][2 sides][16 tiles][P / 2] column maxima by branch tile, instead of atomicMax on the pooled feature
-    int pool_rows_stride;        // 2 * 16 * (P / 2)
-    int poll_sleep;              // s_sleep(8) repeats between two polls of an idle team (1 = ~0.25 us)
-    int branch_parts;            // tasks per branch tile (1, 2, 4): they share the column blocks of the pooled layer (lrg_fused_tile)
-    // Wave-branch mode (round 6; lrg_wave_tile.inl): the launch is TWO kernels resident together -- lrg_grow_async_kernel with the front workgroups and the
-    // pooled-product units only, and lrg_grow_async_worker_kernel (512 threads, up to 256 VGPRs) with `wave_wgs` wave-branch CUs and the head teams' CUs behind them.
-    // A branch tile is a PREFIX task (layers 0 - 3, by one wavefront of a CU that holds those kernels of both branches in LDS) that publishes the tile's POOL tasks
-    // (a quarter of the pooled layer each -- or half a quarter: wave_split 4 / 8 -- by one wavefront of a CU that holds its (side, half) of that kernel in LDS).
-    // Rings of their own: 0 .. 3 = POOL tasks of (side, half), 4 = PREFIX tasks.  0: off -- one kernel, branch tiles by the tile teams.
-    int wave_wgs;                // wave-branch CUs: workgroups 0 .. wave_a_wgs - 1 of the worker kernel run PREFIX tasks, wave_a_wgs .. wave_wgs - 1 POOL tasks of
-    int wave_a_wgs;              //   (side, half) = (w - wave_a_wgs) & 3
-    int wave_waves;              // wavefronts per wave-branch CU that run branch tasks (4: one per SIMD)
-    int wave_split;              // POOL tasks per tile: 4 (a quarter = two pairs of column blocks each) or 8 (one pair each)
-    int wave_fill;               // 1: wavefronts 4 .. 7 of the first fill_wgs wave-branch CUs are a fill-in team (VALU work beside the MFMA-bound branch waves)
-    int wmask;                   // entries of one wave ring - 1 (power of two)
-    float *h3[2];                // [row_cap, 128] per side: layer 3's output rows, from the PREFIX to the POOL tasks
-    int rt_bb_every;             // register tiles: every so-manyth worker CU runs branch tiles on BOTH its teams (0: none)
-    int unit_pairs;              // 1: the pooled-product units run their tasks on half-teams of two wavefronts (lrg_async_gemv_unit2)
-    int reg_tiles;               // 1: the worker kernel's workgroups are all alike -- team 0 runs the branch tiles of ring 0 as REGISTER TILES (lrg_team_branch_tile_reg: a team
-                                 // of four wavefronts per tile, layers 0 - 2 per wavefront in registers, one barrier), team 1 the pooled blocks and head tiles of ring 1
-    int worker_base;             // blockIdx.x of the first worker workgroup in the kernel that runs the tile teams (n_front + gemv_units, or wave_wgs in the worker kernel)
-    int total_wgs;               // workgroups of the launch in all (both kernels): what the start rendezvous waits for
-    int max_steps;               // evaluations per slot in this launch
-    long long start_ticks;       // ... the front workgroups wait at most this long for all workgroups of the launch to have started (reason 6)
-    long long budget_ticks;      // wall_clock64 ticks (100 MHz) after which no new evaluation is started
-    long long abort_ticks;       // ... after which a waiting workgroup gives up
-    unsigned long long *work;    // nullable: [4] evaluations, distinct inlier rows, distinct neighbour rows, 32-row tiles (x 2 stacks) of this buffer's launches
-    unsigned long long *dbg;     // nullable: [32] accumulators of wall-clock ticks (10 ns) for tools/free_run_perf.py --
-                                 // 0 front busy, 1 front steps; per evaluation, since its tasks were published: 2 last branch tile in,
-                                 // 3 last pooled-product block in, 4 last head tile in, 5 seen by the front workgroup, 6 evaluations;
-                                 // 8 + 2 t busy ticks of task type t, 9 + 2 t their number; 16 ticks teams waited for a task, 17 waits;
-                                 // the prepared mask update: 7 ticks spent making records, 19 records tried, 18 front steps that used one
-};
 #ifndef LRG_ASYNC_DEBUG
 #define LRG_ASYNC_DEBUG 0        // 1: the tick accumulators of LrgAsyncBuffers.debug_ticks are compiled in (tools/free_run_perf.py builds with it);
 #endif                           // off by default: the stamps keep 64-bit values alive through the front and cost it registers
@@ -287,16 +196,7 @@ __device__ __forceinline__ void lrg_async_gemv(const LrgGemvArgs &g, int slot, i
 __device__ __forceinline__ int lrg_gemv_ring_tag(int i, int gmask) { return (((unsigned)i / (unsigned)(gmask + 1)) % 2047u) + 1; }
 
 // ---- the launch's arguments ----
-// ONE kernel parameter, so that every role below can be a function of its own (own register allocation: the tile code needs 112
-// VGPRs, a 1024-thread workgroup has 128 per lane -- inlined into one kernel body, the three task types and the front spilled
-// ~150 dwords per lane, some of them inside the tiles' passes) and still reads the arguments the way a kernel does: scalar loads
-// from the kernarg segment, nothing passed on, nothing copied to the stack.
-struct LrgAsyncKArgs {
-    LrgSlot *slots;
-    LrgRoom *rooms;
-    LrgGrowParams prm;
-    LrgAsyncArgs A;
-};
+// ONE kernel parameter, LrgAsyncKArgs (lrg_async_plan.h, where the reasons are)
 // (inside a non-kernel function __builtin_amdgcn_kernarg_segment_ptr() folds to null: the kernel takes the pointer and hands it on,
 //  typed as constant address space, so that the roles' loads of the arguments stay scalar loads)
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -23,40 +23,7 @@
 #define LRG_FRONT_MAXCHUNK 32                         // 32 x 4096 points: rooms up to 131072 points (KITTI scenes: ~100 k)
 #define LRG_FRONT_MAXSAMPLE 1024                      // n_inlier, n_neighbor <= 1024
 
-struct LrgFrontArgs {
-    float *center;
-    int32_t *sample_in, *sample_nb;
-    float *x_in, *x_nb;
-    int32_t *row_slot_in, *row_slot_nb;
-    float4 *upd_in, *upd_nb; // [n_slots, n_inlier] / [n_slots, n_neighbor]: (x, y, z as stored in the packed row, ground-truth flag) of the
-                             // slot's distinct rows -- what the NEXT mask update needs of them, in storage of the slot's own.  The packed
-                             // arrays are re-allocated from row 0 by every launch: a workgroup that starts late (the chip busy with
-                             // another lane's kernels) would find its rows of the last iteration overwritten by the slots that are
-                             // already gathering.
-    const float *rmv_logits, *add_logits;
-    int32_t *slot_rows;      // [n_slots,4]: rows_in, rows_nb, first packed inlier row, first packed neighbour row
-    int32_t *counters;       // [0] packed inlier rows, [1] packed neighbour rows allocated so far in this iteration
-    float *pooled;           // [n_slots, pooled_stride] pooled features of the network workspace (zeroed here per slot)
-    int pooled_stride;
-    int64_t *stats;
-    int64_t *phase_ticks;    // nullable: [n_slots,2] wall-clock ticks per slot: (0) update / stop / commit, (1) query / median / gather
-    int own_medians;         // greedy front kernel: 1 = every slot's workgroup computes its nine medians itself (no launch of their own)
-    unsigned long long *phase_dbg;   // nullable (free-running kernel): [8] accumulated wall-clock ticks of the front's phases; [9 .. 11] inside the mask update: entry -> the
-                                     // slot's words in use, -> logits in registers, -> `take` known
-    int row_stride;          // free-running kernel: slot s owns the rows [s * row_stride, (s + 1) * row_stride) of the row arrays
-    int rows16;              // free-running kernel: 1 = the gathered rows are written at a 64-byte stride (16 floats, zero-padded) in 16-byte pieces
-    int fill_in_launch;      // free-running kernel: finished rooms are filled in (:308-316) by tile teams of the same launch -- flagged in the done ring (bit 31 of the slot word)
-    // free-running kernel, shared tail tiles (lrg_async.inl): a slot's rows beyond its last FULL 32-row tile go to rows that the slots share, reserved from a cursor
-    // per side -- several slots' tails fill one tile instead of each padding a tile of its own.  nullable (then every slot pads its own tail, as before).
-    int32_t *tail_cur;       // [0] / [16]: rows reserved so far on the inlier / neighbour side (one 64-byte line each)
-    int32_t *tail_base;      // [n_slots][2]: where the slot's tail rows of its evaluation in flight start in the shared rows (-1: in its own place)
-    int tail_rows;           // shared rows per side (a multiple of 32)
-    int tail_row0;           // first shared row in the row arrays (= n_slots * row_stride)
-    unsigned long long *spec_stats;      // nullable: [0] regions voided by an earlier commit, [1] evaluations those regions had taken, [2] of them: mask updates done, i.e. steps the
-                                         // device's step counter holds that no committed region keeps (LrgAsyncBuffers.work + 4)
-    int spec_k;              // free-running kernel: K > 1 = speculation -- the slots g K .. g K + K - 1 grow the regions of the next K unvisited seeds of ONE room
-                             // side by side (LrgAsyncBuffers.speculate; see "speculation" below); 0 / 1 = one slot, one room
-};
+// (LrgFrontArgs: lrg_async_plan.h)
 
 // ---- (1) mask update of the evaluation just finished + count / bounding box of the new mask + stop decision ----
 // The new mask is (old members that survive the removes) + (newly added points that survive them): both sets are at
