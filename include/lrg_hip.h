@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 11
+#define LRG_ABI_VERSION 12
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -827,6 +827,25 @@ int lrg_preprocess(const float *raw, int raw_stride, const int32_t *obj_id, cons
 int lrg_preprocess_status(const void *workspace, int n_raw, int32_t *host_status, void *stream);
 /* after lrg_preprocess(..., eig_mode 2, ...) on this workspace: flags_out [n_equalized] int32 (device), 1 = redo this point's decomposition with LAPACK */
 int lrg_preprocess_unsafe_normals(const void *workspace, int n_raw, int n_equalized, int32_t *flags_out, void *stream);
+/* ABI 12.  The same block (test_region_grow.py:119-173) for all rooms of a file in one pass: a fixed number of launches whatever n_rooms
+ * is.  raw [sum M, raw_stride] holds the rooms' rows one after the other, obj_id / cls_id likewise; raw_start [n_rooms + 1] is HOST memory
+ * (raw_start[0] = 0, strictly increasing: an empty room is refused), copied to the workspace on the stream.  Every room has a hash table
+ * and scalars of its own -- equal voxel coordinates in two rooms never meet -- and every per-room result has the bits lrg_preprocess gives
+ * for that room alone.  Outputs as lrg_preprocess's, concatenated in room order: the equalised rows of room r are
+ * eq_start[r] .. eq_start[r + 1] (eq_start [n_rooms + 1] int32, device) of points / obj_out / cls_out / curvatures / cov / equalized_idx /
+ * unsafe_flags, all sized for sum M rows; equalized_idx and unequalized_idx [sum M] are room-relative.  unsafe_flags (eig_mode 2: what
+ * lrg_preprocess_unsafe_normals copies out; may be NULL otherwise).  Refused with a code of their own: n_rooms < 1 or a bad raw_start[0]
+ * (LRG_EINVAL - 60), a decreasing raw_start (- 61), an empty room (- 62), sum M >= 2^30 (- 63), 4 sum M + 64 n_rooms >= 2^31 (- 64: the
+ * rooms' hash segments, an upper bound of their summed capacities, are numbered in int32), a NULL among raw / workspace / equalized_idx /
+ * unequalized_idx / eq_start (- 65), a short or unaligned workspace (- 66), eig_mode 2 without unsafe_flags (- 67); nothing is launched. */
+size_t lrg_preprocess_batch_workspace_bytes(const int32_t *raw_start, int n_rooms);     /* test_region_grow.py:119-173; 0 = bad raw_start */
+int lrg_preprocess_batch(const float *raw, int raw_stride, const int32_t *obj_id, const int32_t *cls_id, const int32_t *raw_start,
+                         int n_rooms, float resolution, int feature_size, int eig_mode, void *workspace, size_t workspace_bytes,
+                         float *points, int32_t *obj_out, int32_t *cls_out, double *curvatures, int32_t *equalized_idx,
+                         int32_t *unequalized_idx, double *cov, int32_t *eq_start, int32_t *unsafe_flags, void *stream);
+/* test_region_grow.py:119-173, the batch's lrg_preprocess_status: host_status_per_room [n_rooms] (host), 1 = a point of that room lies
+ * outside the voxel window (it was left out; the room's outputs are not valid).  Synchronises the stream. */
+int lrg_preprocess_batch_status(const void *workspace, const int32_t *raw_start, int n_rooms, int32_t *host_status_per_room, void *stream);
 
 #ifdef __cplusplus
 }

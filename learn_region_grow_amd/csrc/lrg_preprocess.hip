@@ -189,14 +189,11 @@ __global__ void prep_sort_lists_kernel(const int32_t *hash_off, const int32_t *c
     }
 }
 
-// covariance of the raw points in the 27 voxels around every equalised point (:144-157), then normal and curvature (:158-161)
-__global__ __launch_bounds__(PREP_THREADS) void prep_cov_kernel(const float *raw, int ld, float res, const int32_t *equalized_idx,
-                                                              const int32_t *scal_n, const uint64_t *keys, const int32_t *hash_off,
-                                                              const int32_t *count, int mask, const int32_t *list, double *cov_out,
-                                                              int eig_mode, double *normal, double *curv, int32_t *scal, int32_t *nflag) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= *scal_n) return;
-    const float *pe = raw + (long)equalized_idx[e] * ld;
+// The arithmetic of one equalised point, shared by the single-room kernels and the batched ones below (one definition, one order of
+// operations): covariance of the raw points in the 27 voxels around pe (:144-157).  keys / hash_off / count are the room's hash
+// segment; list and raw are indexed as hash_off says (room-relative in lrg_preprocess, file-wide in lrg_preprocess_batch).
+__device__ __forceinline__ void prep_cov_point(const float *raw, int ld, float res, const float *pe, const uint64_t *keys,
+                                               const int32_t *hash_off, const int32_t *count, int mask, const int32_t *list, double *C) {
     const int vx = lrg_voxel_of(pe[0], res), vy = lrg_voxel_of(pe[1], res), vz = lrg_voxel_of(pe[2], res);
     double A[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, B[3] = {0, 0, 0};
     int n = 0;
@@ -227,24 +224,27 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_cov_kernel(const float *raw
                 n += c;
             }
     const double dn = (double)n, dn2 = dn * dn;
-    double C[9];
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) C[3 * i + j] = A[3 * i + j] / dn - (B[i] * B[j]) / dn2;          // (:157)
-    if (cov_out)
-        for (int k = 0; k < 9; ++k) cov_out[(long)e * 9 + k] = C[k];
-    // room extent for the normalised coordinates (:139)
+}
+
+// room extent for the normalised coordinates (:139); scal is the room's scalar block
+__device__ __forceinline__ void prep_extent_point(const float *pe, int32_t *scal) {
     atomicMin(&scal[2], prep_ord(pe[0])); atomicMin(&scal[3], prep_ord(pe[1])); atomicMin(&scal[4], prep_ord(pe[2]));
     atomicMax(&scal[5], prep_ord(pe[0])); atomicMax(&scal[6], prep_ord(pe[1])); atomicMax(&scal[7], prep_ord(pe[2]));
-    if (!eig_mode) return;
+}
+
+// normal and curvature of one covariance (:158-161): normal [3], curv and nflag (eig_mode 2, nullable) are the point's own elements
+__device__ __forceinline__ void prep_eig_point(const double *C, int eig_mode, double *normal, double *curv, int32_t *scal, int32_t *nflag) {
     double w[3], V[3][3];
     prep_jacobi3(C, w, V);
     // singular values of a symmetric matrix = |eigenvalues|, descending; V[2] belongs to the smallest (:158-159)
     double s[3] = {fabs(w[0]), fabs(w[1]), fabs(w[2])};
     int i0, i1, i2;
     prep_eig_order(s, &i0, &i1, &i2);
-    normal[(long)e * 3 + 0] = fabs(V[i2][0]); normal[(long)e * 3 + 1] = fabs(V[i2][1]); normal[(long)e * 3 + 2] = fabs(V[i2][2]);
+    normal[0] = fabs(V[i2][0]); normal[1] = fabs(V[i2][1]); normal[2] = fabs(V[i2][2]);
     const double cv = fabs(s[i2] / (s[i0] + s[i1] + s[i2]));                                         // S[2]/(S[0]+S[1]+S[2]) (:160-161)
-    curv[e] = cv;
+    *curv = cv;
     if (eig_mode == 2 && nflag) {
         // Would LAPACK's decomposition of the same matrix round to the same float32 normal?  Both solvers are backward stable: their
         // eigenvectors of the smallest eigenvalue differ by at most ~p eps |A| / (gap to the next eigenvalue) with a small p; with
@@ -260,10 +260,46 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_cov_kernel(const float *raw
                 if ((float)(x - dv) != (float)(x + dv) || x < dv) unsafe = 1;
             }
         }
-        nflag[e] = unsafe;
+        *nflag = unsafe;
     }
     if (cv != cv) scal[10] = 1;                                                                     // numpy's max() propagates NaN
     else atomicMax(reinterpret_cast<unsigned long long *>(&scal[8]), (unsigned long long)__double_as_longlong(cv));
+}
+
+// one row of the feature stack (:163-172): p the raw row, o the output row, normal / curv the point's own elements
+__device__ __forceinline__ void prep_feature_row(const float *p, const int32_t *scal, const double *normal, double *curv, int F, float *o,
+                                                 int keep_raw_curv) {
+    for (int k = 0; k < 3; ++k) {
+        const float mn = prep_unord(scal[2 + k]), mx = prep_unord(scal[5 + k]);
+        o[k] = p[k];
+        o[3 + k] = __fdiv_rn(__fsub_rn(p[k], mn), __fsub_rn(mx, mn));
+    }
+    if (F >= 9)
+        for (int k = 0; k < 3; ++k) o[6 + k] = p[3 + k];
+    if (F >= 12)
+        for (int k = 0; k < 3; ++k) o[9 + k] = (float)normal[k];
+    const double cmax = scal[10] ? __longlong_as_double(0x7ff8000000000000LL)
+                                 : __longlong_as_double(*reinterpret_cast<const long long *>(&scal[8]));
+    const double c = *curv / cmax;                                                                   // (:163)
+    if (!keep_raw_curv) *curv = c;        // (eig_mode 2: the host normalises with LAPACK's own maximum)
+    if (F >= 13) o[12] = (float)c;
+}
+
+// covariance of the raw points in the 27 voxels around every equalised point (:144-157), then normal and curvature (:158-161)
+__global__ __launch_bounds__(PREP_THREADS) void prep_cov_kernel(const float *raw, int ld, float res, const int32_t *equalized_idx,
+                                                              const int32_t *scal_n, const uint64_t *keys, const int32_t *hash_off,
+                                                              const int32_t *count, int mask, const int32_t *list, double *cov_out,
+                                                              int eig_mode, double *normal, double *curv, int32_t *scal, int32_t *nflag) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= *scal_n) return;
+    const float *pe = raw + (long)equalized_idx[e] * ld;
+    double C[9];
+    prep_cov_point(raw, ld, res, pe, keys, hash_off, count, mask, list, C);
+    if (cov_out)
+        for (int k = 0; k < 9; ++k) cov_out[(long)e * 9 + k] = C[k];
+    prep_extent_point(pe, scal);
+    if (!eig_mode) return;
+    prep_eig_point(C, eig_mode, normal + (long)e * 3, curv + e, scal, nflag ? nflag + e : nullptr);
 }
 
 // the feature stack (:163-172)
@@ -273,24 +309,204 @@ __global__ void prep_features_kernel(const float *raw, int ld, const int32_t *ob
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= scal[0]) return;
     const int i = equalized_idx[e];
-    const float *p = raw + (long)i * ld;
-    float *o = points + (long)e * F;
-    for (int k = 0; k < 3; ++k) {
-        const float mn = prep_unord(scal[2 + k]), mx = prep_unord(scal[5 + k]);
-        o[k] = p[k];
-        o[3 + k] = __fdiv_rn(__fsub_rn(p[k], mn), __fsub_rn(mx, mn));
-    }
-    if (F >= 9)
-        for (int k = 0; k < 3; ++k) o[6 + k] = p[3 + k];
-    if (F >= 12)
-        for (int k = 0; k < 3; ++k) o[9 + k] = (float)normal[(long)e * 3 + k];
-    const double cmax = scal[10] ? __longlong_as_double(0x7ff8000000000000LL)
-                                 : __longlong_as_double(*reinterpret_cast<const long long *>(&scal[8]));
-    const double c = curv[e] / cmax;                                                                 // (:163)
-    if (!keep_raw_curv) curv[e] = c;      // (eig_mode 2: the host normalises with LAPACK's own maximum)
-    if (F >= 13) o[12] = (float)c;
+    prep_feature_row(raw + (long)i * ld, scal, normal + (long)e * 3, curv + e, F, points + (long)e * F, keep_raw_curv);
     if (obj_out) obj_out[e] = obj ? obj[i] : 0;
     if (cls_out) cls_out[e] = cls ? cls[i] : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// All rooms of a file in one pass (lrg_preprocess_batch).  The rooms' raw rows lie one after the other ([sum M, ld], room r =
+// rows raw_start[r] .. raw_start[r + 1]); every kernel runs over the whole array (or over all hash slots), so the launch count does
+// not depend on the number of rooms.  Room r owns the hash segment at slot 4 raw_start[r] + 64 r, capacity the single-room rule (the
+// smallest power of two >= max(64, 2 M_r), which is < 4 M_r + 64): equal voxel coordinates in two rooms are keys in two tables and
+// never meet.  first / list / hash_off hold file-wide raw indices; ONE scan of the first-point flags ranks the equalised points of
+// all rooms back to back in room order, eq_start[r] = its value at raw_start[r]; equalized_idx / unequalized_idx are written
+// room-relative.  Every room has its own 16-word scalar block (the layout of LrgPrepLayout.scal) and its own status word.
+#define PB_SCAL 16
+
+struct PbLayout {
+    size_t keys, first, count, off, rank, cursor;     // per hash slot (all rooms' segments)
+    size_t slot, flag, list, room_of, eglob;          // per raw point (eglob: per equalised point, its file-wide raw index)
+    size_t rooms, status, bsum, scal, normal, curv;
+    size_t total;
+    long hslots;
+    int n;
+};
+
+struct PbArgs {
+    const float *raw; int ld;
+    const int32_t *obj, *cls, *raw_start;
+    int n_rooms, n; float res; int F, eig_mode;
+    uint64_t *keys; int32_t *first, *count, *off, *rank, *cursor; long hslots;
+    int32_t *slot, *flag, *list, *room_of, *eglob, *bsum, *scal, *status;
+    double *normal, *curv, *cov;
+    float *points; int32_t *obj_out, *cls_out, *equalized_idx, *unequalized_idx, *eq_start, *unsafe;
+};
+
+// raw_start is host memory: checked here, before anything is launched
+static int pb_layout(const int32_t *raw_start, int n_rooms, PbLayout *L) {
+    if (n_rooms < 1 || n_rooms > (1 << 20) || !raw_start || raw_start[0] != 0) return LRG_EINVAL - 60;
+    for (int r = 0; r < n_rooms; ++r) {
+        if (raw_start[r + 1] < raw_start[r]) return LRG_EINVAL - 61;
+        if (raw_start[r + 1] == raw_start[r]) return LRG_EINVAL - 62;              // an empty room
+    }
+    const long n = raw_start[n_rooms];
+    if (n >= (1L << 30)) return LRG_EINVAL - 63;
+    // the segments' space (an upper bound of the summed capacities): slot numbers and list offsets stay in int32
+    const long hslots = 4L * n + 64L * n_rooms;
+    if (hslots >= (1L << 31)) return LRG_EINVAL - 64;
+    L->hslots = hslots;
+    L->n = (int)n;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t at = o; o = lrg_align_up(o + bytes, 256); return at; };
+    L->keys = take((size_t)hslots * 8);
+    L->first = take((size_t)hslots * 4);
+    L->count = take((size_t)hslots * 4);
+    L->off = take((size_t)hslots * 4);
+    L->rank = take((size_t)hslots * 4);
+    L->cursor = take((size_t)hslots * 4);
+    L->slot = take((size_t)n * 4);
+    L->flag = take((size_t)n * 4);
+    L->list = take((size_t)n * 4);
+    L->room_of = take((size_t)n * 4);
+    L->eglob = take((size_t)n * 4);
+    L->rooms = take((size_t)(n_rooms + 1) * 4);
+    L->status = take((size_t)n_rooms * 4);
+    const long per_block = PREP_THREADS * PREP_SCAN_ITEMS;
+    L->bsum = take((size_t)((hslots + per_block - 1) / per_block + 1) * 4);
+    L->scal = take((size_t)n_rooms * PB_SCAL * 4);
+    L->normal = take((size_t)n * 3 * 8);
+    L->curv = take((size_t)n * 8);
+    L->total = o;
+    return 0;
+}
+
+// Bounds of room r (raw_start was checked on the host: this only keeps a bad word from turning into an address)
+__device__ __forceinline__ bool pb_room(const PbArgs &a, int r, int *s, int *e) {
+    if (r < 0 || r >= a.n_rooms) return false;
+    const int s0 = a.raw_start[r], e0 = a.raw_start[r + 1];
+    if (s0 < 0 || e0 <= s0 || e0 > a.n) return false;
+    *s = s0; *e = e0;
+    return true;
+}
+
+// the room's hash segment: first slot and mask
+__device__ __forceinline__ void pb_segment(int r, int s, int e, long *off, int *mask) {
+    int cap = 64;
+    while (cap < 2 * (e - s)) cap <<= 1;
+    *off = 4L * s + 64L * r;
+    *mask = cap - 1;
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void pb_init_kernel(PbArgs a) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < a.hslots) { a.keys[t] = LRG_HASH_EMPTY; a.first[t] = INT_MAX; a.count[t] = 0; a.cursor[t] = 0; }
+    if (t < (long)a.n_rooms * PB_SCAL) {
+        const int k = (int)(t % PB_SCAL);
+        a.scal[t] = (k >= 2 && k <= 4) ? INT_MAX : (k >= 5 && k <= 7) ? INT_MIN : 0;
+    }
+    if (t < a.n_rooms) a.status[t] = 0;
+    if (t >= a.n) return;
+    const int i = (int)t;
+    int lo = 0, hi = a.n_rooms - 1;                // the last r with raw_start[r] <= i
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.raw_start[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    a.room_of[i] = lo;
+}
+
+// voxel -> slot of the room's own segment (insert), first raw index and population of every voxel          (:125-133)
+__global__ __launch_bounds__(PREP_THREADS) void pb_insert_kernel(PbArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const int r = a.room_of[i];
+    int s, e;
+    a.slot[i] = -1;
+    if (!pb_room(a, r, &s, &e)) return;
+    const float *p = a.raw + (long)i * a.ld;
+    const uint64_t key = lrg_pack_voxel(lrg_voxel_of(p[0], a.res), lrg_voxel_of(p[1], a.res), lrg_voxel_of(p[2], a.res));
+    if (key == LRG_HASH_EMPTY) { a.scal[r * PB_SCAL + 1] = 1; a.status[r] = 1; return; }     // outside the 21-bit voxel window
+    long off; int mask;
+    pb_segment(r, s, e, &off, &mask);
+    uint64_t *keys = a.keys + off;
+    unsigned h = (unsigned)lrg_fmix64(key) & (unsigned)mask;
+    for (int probe = 0; probe <= mask; ++probe) {      // (capacity >= 2 M_r: a free slot exists)
+        unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&keys[h]), (unsigned long long)LRG_HASH_EMPTY,
+                                            (unsigned long long)key);
+        if (prev == LRG_HASH_EMPTY || prev == key) {
+            atomicMin(&a.first[off + h], i);
+            atomicAdd(&a.count[off + h], 1);
+            a.slot[i] = (int)(off + h);
+            return;
+        }
+        h = (h + 1) & (unsigned)mask;
+    }
+}
+
+// equalised order = raw order of the first point of each voxel, rooms back to back (:127-129,:134); eq_start and the rooms' N
+__global__ __launch_bounds__(PREP_THREADS) void pb_equalize_kernel(PbArgs a, const int32_t *rank_of_raw, const int32_t *bsum_total) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= a.n_rooms) {
+        int s, e;
+        int v = *bsum_total;
+        if (i < a.n_rooms) v = pb_room(a, i, &s, &e) ? rank_of_raw[s] : 0;
+        a.eq_start[i] = v;
+        if (i < a.n_rooms) {
+            const int nxt = i + 1 < a.n_rooms ? (pb_room(a, i + 1, &s, &e) ? rank_of_raw[s] : v) : *bsum_total;
+            a.scal[i * PB_SCAL] = nxt - v;
+        }
+    }
+    if (i >= a.n || !a.flag[i]) return;
+    int s, e;
+    if (!pb_room(a, a.room_of[i], &s, &e)) return;
+    const int g = rank_of_raw[i];
+    a.eglob[g] = i;
+    a.equalized_idx[g] = i - s;
+    a.rank[a.slot[i]] = g - rank_of_raw[s];
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void pb_fill_kernel(PbArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const int s = a.slot[i];
+    if (s < 0) { a.unequalized_idx[i] = -1; return; }
+    a.list[a.off[s] + atomicAdd(&a.cursor[s], 1)] = i;
+    a.unequalized_idx[i] = a.rank[s];
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void pb_cov_kernel(PbArgs a) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= a.n || g >= a.eq_start[a.n_rooms]) return;
+    const int i = a.eglob[g];
+    if (i < 0 || i >= a.n) return;
+    const int r = a.room_of[i];
+    int s, e;
+    if (!pb_room(a, r, &s, &e)) return;
+    long off; int mask;
+    pb_segment(r, s, e, &off, &mask);
+    const float *pe = a.raw + (long)i * a.ld;
+    double C[9];
+    prep_cov_point(a.raw, a.ld, a.res, pe, a.keys + off, a.off + off, a.count + off, mask, a.list, C);
+    if (a.cov)
+        for (int k = 0; k < 9; ++k) a.cov[(long)g * 9 + k] = C[k];
+    int32_t *scal = a.scal + r * PB_SCAL;
+    prep_extent_point(pe, scal);
+    if (!a.eig_mode) return;
+    prep_eig_point(C, a.eig_mode, a.normal + (long)g * 3, a.curv + g, scal, a.unsafe ? a.unsafe + g : nullptr);
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void pb_features_kernel(PbArgs a) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= a.n || g >= a.eq_start[a.n_rooms]) return;
+    const int i = a.eglob[g];
+    if (i < 0 || i >= a.n) return;
+    const int r = a.room_of[i];
+    if (r < 0 || r >= a.n_rooms) return;
+    prep_feature_row(a.raw + (long)i * a.ld, a.scal + r * PB_SCAL, a.normal + (long)g * 3, a.curv + g, a.F, a.points + (long)g * a.F,
+                     a.eig_mode == 2 ? 1 : 0);
+    if (a.obj_out) a.obj_out[g] = a.obj ? a.obj[i] : 0;
+    if (a.cls_out) a.cls_out[g] = a.cls ? a.cls[i] : 0;
 }
 
 extern "C" {
@@ -371,6 +587,79 @@ int lrg_preprocess_status(const void *workspace, int n_raw, int32_t *host_status
     if (!workspace || !host_status) return LRG_EINVAL - 52;
     LRG_HIP_CHECK(hipMemcpyAsync(host_status, static_cast<const char *>(workspace) + L.scal + 4, sizeof(int32_t), hipMemcpyDeviceToHost,
                                  (hipStream_t)stream));
+    LRG_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+}
+
+/* ---- all rooms of a file in one pass ---- */
+size_t lrg_preprocess_batch_workspace_bytes(const int32_t *raw_start, int n_rooms) {
+    PbLayout L;
+    if (pb_layout(raw_start, n_rooms, &L) != 0) return 0;
+    return L.total;
+}
+
+int lrg_preprocess_batch(const float *raw, int raw_stride, const int32_t *obj_id, const int32_t *cls_id, const int32_t *raw_start,
+                         int n_rooms, float resolution, int feature_size, int eig_mode, void *workspace, size_t workspace_bytes,
+                         float *points, int32_t *obj_out, int32_t *cls_out, double *curvatures, int32_t *equalized_idx,
+                         int32_t *unequalized_idx, double *cov, int32_t *eq_start, int32_t *unsafe_flags, void *stream) {
+    PbLayout L;
+    int rc = pb_layout(raw_start, n_rooms, &L);
+    if (rc) return rc;
+    if (!raw || raw_stride < 6 || !workspace || !equalized_idx || !unequalized_idx || !eq_start) return LRG_EINVAL - 65;
+    if (workspace_bytes < L.total || ((uintptr_t)workspace & 255)) return LRG_EINVAL - 66;
+    if (!(resolution > 0.f)) return LRG_EINVAL - 54;
+    if (feature_size != 6 && feature_size != 9 && feature_size != 12 && feature_size != 13) return LRG_EINVAL - 55;
+    if (eig_mode != 0 && eig_mode != 1 && eig_mode != 2) return LRG_EINVAL - 56;
+    if (eig_mode >= 1 && (!points || !curvatures)) return LRG_EINVAL - 57;
+    if ((eig_mode == 0 || eig_mode == 2) && !cov) return LRG_EINVAL - 58;
+    if (eig_mode == 2 && !unsafe_flags) return LRG_EINVAL - 67;
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = static_cast<char *>(workspace);
+    auto i32 = [&](size_t at) { return reinterpret_cast<int32_t *>(ws + at); };
+    PbArgs a;
+    int32_t *rooms = i32(L.rooms);                                    // a device copy of raw_start (the caller's is host memory)
+    LRG_HIP_CHECK(hipMemcpyAsync(rooms, raw_start, (size_t)(n_rooms + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    a.raw = raw; a.ld = raw_stride; a.obj = obj_id; a.cls = cls_id; a.raw_start = rooms; a.n_rooms = n_rooms; a.n = L.n;
+    a.res = resolution; a.F = feature_size; a.eig_mode = eig_mode;
+    a.keys = reinterpret_cast<uint64_t *>(ws + L.keys); a.first = i32(L.first); a.count = i32(L.count); a.off = i32(L.off);
+    a.rank = i32(L.rank); a.cursor = i32(L.cursor); a.hslots = L.hslots;
+    a.slot = i32(L.slot); a.flag = i32(L.flag); a.list = i32(L.list); a.room_of = i32(L.room_of); a.eglob = i32(L.eglob);
+    a.bsum = i32(L.bsum); a.scal = i32(L.scal); a.status = i32(L.status);
+    a.normal = reinterpret_cast<double *>(ws + L.normal);
+    a.curv = curvatures ? curvatures : reinterpret_cast<double *>(ws + L.curv);
+    a.cov = cov; a.points = points; a.obj_out = obj_out; a.cls_out = cls_out; a.equalized_idx = equalized_idx;
+    a.unequalized_idx = unequalized_idx; a.eq_start = eq_start; a.unsafe = eig_mode == 2 ? unsafe_flags : nullptr;
+    const int n = L.n;
+    const long init_n = L.hslots > (long)n ? L.hslots : (long)n;            // (hslots >= 64 n_rooms covers the scalar blocks too)
+    const int gi = (int)((init_n + PREP_THREADS - 1) / PREP_THREADS), gh = (int)((L.hslots + PREP_THREADS - 1) / PREP_THREADS);
+    const int gm = (n + PREP_THREADS - 1) / PREP_THREADS, ge = (n + 1 + PREP_THREADS - 1) / PREP_THREADS;      // (n + 1 > n_rooms)
+    hipLaunchKernelGGL(pb_init_kernel, dim3(gi), dim3(PREP_THREADS), 0, st, a);
+    hipLaunchKernelGGL(pb_insert_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
+    hipLaunchKernelGGL(prep_flag_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a.slot, a.first, n, a.flag);
+    LRG_LAUNCH_CHECK();
+    // file-wide rank of every first point (scanned into `list`, which is filled only afterwards)
+    if ((rc = prep_exscan(a.flag, n, a.bsum, a.list, st))) return rc;
+    const long per_block = PREP_THREADS * PREP_SCAN_ITEMS;
+    const int nb_m = (int)((n + per_block - 1) / per_block);
+    hipLaunchKernelGGL(pb_equalize_kernel, dim3(ge), dim3(PREP_THREADS), 0, st, a, a.list, a.bsum + nb_m);
+    LRG_LAUNCH_CHECK();
+    if ((rc = prep_exscan(a.count, L.hslots, a.bsum, a.off, st))) return rc;
+    hipLaunchKernelGGL(pb_fill_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
+    hipLaunchKernelGGL(prep_sort_lists_kernel, dim3(gh), dim3(PREP_THREADS), 0, st, a.off, a.count, (int)L.hslots, a.list);
+    hipLaunchKernelGGL(pb_cov_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
+    if (eig_mode >= 1) hipLaunchKernelGGL(pb_features_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
+    LRG_LAUNCH_CHECK();
+    return 0;
+}
+
+/* error flags of the last lrg_preprocess_batch on this workspace, one per room: 1 = a point of the room fell outside the voxel window */
+int lrg_preprocess_batch_status(const void *workspace, const int32_t *raw_start, int n_rooms, int32_t *host_status_per_room, void *stream) {
+    PbLayout L;
+    int rc = pb_layout(raw_start, n_rooms, &L);
+    if (rc) return rc;
+    if (!workspace || !host_status_per_room) return LRG_EINVAL - 65;
+    LRG_HIP_CHECK(hipMemcpyAsync(host_status_per_room, static_cast<const char *>(workspace) + L.status, (size_t)n_rooms * sizeof(int32_t),
+                                 hipMemcpyDeviceToHost, (hipStream_t)stream));
     LRG_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return 0;
 }

@@ -38,6 +38,11 @@ CLASSES_S3DIS = ['clutter', 'board', 'bookcase', 'beam', 'chair', 'column', 'doo
                  'wall']          # class names are data (the reference's class_util.classes_s3dis); only the region lines use them
 
 
+# --preprocess modes (by their eig name) that go through preprocess_gpu.preprocess_rooms, all rooms of the rank in one device pass: the modes whose
+# batch beat the room-by-room loop beyond the spread (profiles/prep_batch.json, DESIGN.md 3.6 "Batched"); the others keep the loop, same bits either way
+BATCHED_PREPROCESS = ('exact',)
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--area', default=None, help="comma list; 'scannet', 's3dis', 'kitti_train', 'kitti_val' or an S3DIS area number")
@@ -220,16 +225,25 @@ def main(argv=None):
         mine = lrg_dist.shard_rooms_lpt(sizes, world)[rank] if world > 1 else list(range(len(room_ids)))
         my_rooms = [room_ids[i] for i in mine]
         pre, t_feat = [], []
-        for r in my_rooms:
+        eig = {'gpu-lapack': 'lapack', 'gpu-exact': 'exact', 'gpu': 'jacobi'}.get(args.preprocess)
+        if eig in BATCHED_PREPROCESS and my_rooms:
+            # all of the rank's rooms in one device pass (preprocess_gpu.preprocess_rooms: the same bits as room by room); a room's share of
+            # the batch's time goes by its raw-point count
             t0 = time.time()
-            if args.preprocess == 'host':
-                pre.append(preprocess.preprocess_room(all_points[r], all_obj_id[r], all_cls_id[r], resolution=args.resolution,
-                                                      feature_size=args.feature_size))
-            else:
-                pre.append(preprocess_gpu.preprocess_room(all_points[r], all_obj_id[r], all_cls_id[r], resolution=args.resolution,
-                                                          feature_size=args.feature_size, device=device,
-                                                          eig={'gpu-lapack': 'lapack', 'gpu-exact': 'exact'}.get(args.preprocess, 'jacobi')))
-            t_feat.append(time.time() - t0)
+            pre = preprocess_gpu.preprocess_rooms([(all_points[r], all_obj_id[r], all_cls_id[r]) for r in my_rooms], resolution=args.resolution,
+                                                  feature_size=args.feature_size, eig=eig, device=device)
+            dt, raw_total = time.time() - t0, float(sum(len(all_points[r]) for r in my_rooms))
+            t_feat = [dt * len(all_points[r]) / raw_total for r in my_rooms]
+        else:
+            for r in my_rooms:
+                t0 = time.time()
+                if args.preprocess == 'host':
+                    pre.append(preprocess.preprocess_room(all_points[r], all_obj_id[r], all_cls_id[r], resolution=args.resolution,
+                                                          feature_size=args.feature_size))
+                else:
+                    pre.append(preprocess_gpu.preprocess_room(all_points[r], all_obj_id[r], all_cls_id[r], resolution=args.resolution,
+                                                              feature_size=args.feature_size, device=device, eig=eig))
+                t_feat.append(time.time() - t0)
         rooms = [dict(points=p['points'], obj_id=p['obj_id'], order=p['order'].astype(np.int32), room_id=r) for r, p in zip(my_rooms, pre)]
         in_flight = max(1, min(args.rooms_in_flight, len(rooms)))
         kw = dict(rooms_in_flight=in_flight, restarts=max(1, args.restarts), rng=args.rng, seed=args.seed, policy=args.policy,
