@@ -818,7 +818,11 @@ int lrg_adam_step(float *params, const float *grads, float *m, float *v, long n,
  *             numpy.linalg.svd would give (near-degenerate eigenvalue pairs, components next to a float32 rounding boundary): the host
  *             redoes those few with LAPACK and gets the reference's features and seed order bit for bit at the all-GPU rate.
  * workspace: lrg_preprocess_workspace_bytes(n_raw) bytes, 256-byte aligned.  Points whose voxel falls outside a 21-bit
- * window per axis are reported by lrg_preprocess_status (1) and left out. */
+ * window per axis are reported by lrg_preprocess_status (1) and left out.
+ * These entries are lrg_preprocess_batch (below) with one room: the same launches, nothing copied from host memory, everything on the
+ * stream.  Always size the workspace with lrg_preprocess_workspace_bytes: it is the batch's for one room (4 n_raw + 64 hash slots, the
+ * batch's per-point arrays), 0 for n_raw <= 0 and for a room past the batch's limits (n_raw >= 2^30 or 4 n_raw + 64 >= 2^31:
+ * lrg_preprocess then returns LRG_EINVAL - 51). */
 size_t lrg_preprocess_workspace_bytes(int n_raw);
 int lrg_preprocess(const float *raw, int raw_stride, const int32_t *obj_id, const int32_t *cls_id, int n_raw, float resolution,
                    int feature_size, int eig_mode, void *workspace, size_t workspace_bytes, float *points, int32_t *obj_out,
@@ -830,8 +834,8 @@ int lrg_preprocess_unsafe_normals(const void *workspace, int n_raw, int n_equali
 /* ABI 12.  The same block (test_region_grow.py:119-173) for all rooms of a file in one pass: a fixed number of launches whatever n_rooms
  * is.  raw [sum M, raw_stride] holds the rooms' rows one after the other, obj_id / cls_id likewise; raw_start [n_rooms + 1] is HOST memory
  * (raw_start[0] = 0, strictly increasing: an empty room is refused), copied to the workspace on the stream.  Every room has a hash table
- * and scalars of its own -- equal voxel coordinates in two rooms never meet -- and every per-room result has the bits lrg_preprocess gives
- * for that room alone.  Outputs as lrg_preprocess's, concatenated in room order: the equalised rows of room r are
+ * and scalars of its own -- equal voxel coordinates in two rooms never meet -- and every per-room result has the bits of that room
+ * alone.  Outputs as lrg_preprocess's, concatenated in room order: the equalised rows of room r are
  * eq_start[r] .. eq_start[r + 1] (eq_start [n_rooms + 1] int32, device) of points / obj_out / cls_out / curvatures / cov / equalized_idx /
  * unsafe_flags, all sized for sum M rows; equalized_idx and unequalized_idx [sum M] are room-relative.  unsafe_flags (eig_mode 2: what
  * lrg_preprocess_unsafe_normals copies out; may be NULL otherwise).  Refused with a code of their own: n_rooms < 1 or a bad raw_start[0]

@@ -308,7 +308,7 @@ __global__ __launch_bounds__(BL_THREADS) void bl_tally_kernel(BlArgs a) {
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(a.n_flagged, c);
 }
 
-// One lane per covariance: prep_jacobi3, the selection of prep_cov_kernel, and how far LAPACK's values can lie from these.
+// One lane per covariance: prep_jacobi3, the selection of prep_eig_point, and how far LAPACK's values can lie from these.
 __global__ __launch_bounds__(BL_THREADS) void bl_eig_kernel(const double *cov, int n, double *normals, double *curv, double *nslack,
                                                             double *cslack) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;

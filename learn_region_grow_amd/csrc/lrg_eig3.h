@@ -38,7 +38,7 @@ __device__ void prep_jacobi3(const double *c, double *w, double (*V)[3]) {
 }
 
 // singular values of a symmetric matrix = |eigenvalues|: which is the largest (i0), the middle (i1) and the smallest (i2), with the
-// tie rules of numpy.linalg.svd's descending order as prep_cov_kernel has always applied them
+// tie rules of numpy.linalg.svd's descending order as prep_eig_point has always applied them
 __device__ __forceinline__ void prep_eig_order(const double *s, int *i0_out, int *i1_out, int *i2_out) {
     int i0 = 0, i2 = 0;
     if (s[1] > s[i0]) i0 = 1;

@@ -8,78 +8,18 @@
 // (LAPACK dgesdd inside numpy.linalg.svd): eig_mode 0 stops after the covariances (the host runs the same LAPACK call:
 // bit-exact features), eig_mode 1 solves them here with a cyclic Jacobi iteration in float64 (|error| ~ 1e-16 |cov|:
 // features agree to float32 rounding, documented tolerance in tests/test_gpu_preprocess.py).
+//
+// ONE pipeline: all rooms of a file in one pass (lrg_preprocess_batch); lrg_preprocess and its companions are that pass
+// with one room.
 #include "lrg_common.h"
 #include "lrg_eig3.h"
 
 #define PREP_THREADS 256
 #define PREP_SCAN_ITEMS 8                      // per thread: 2048 elements per block
 
-struct LrgPrepLayout {
-    size_t keys, first, count, off, rank, cursor;     // per hash slot
-    size_t slot, flag, list;                          // per raw point
-    size_t bsum;                                      // block sums of the scans
-    size_t scal;                                      // scalars: [0] N, [1] error, [2..7] xyz min/max (ordered ints), [8,9] max curvature (u64), [10] any-NaN
-    size_t normal, curv;                              // per equalised point: float64 [3], float64
-    size_t total;
-    int cap;
-};
-
-static int prep_layout(int M, LrgPrepLayout *L) {
-    if (M <= 0) return LRG_EINVAL - 50;
-    long cap = 64;
-    while (cap < 2L * M) cap <<= 1;
-    if (cap > (1L << 30)) return LRG_EINVAL - 51;
-    L->cap = (int)cap;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = lrg_align_up(o + bytes, 256); return at; };
-    L->keys = take((size_t)cap * 8);
-    L->first = take((size_t)cap * 4);
-    L->count = take((size_t)cap * 4);
-    L->off = take((size_t)cap * 4);
-    L->rank = take((size_t)cap * 4);
-    L->cursor = take((size_t)cap * 4);
-    L->slot = take((size_t)M * 4);
-    L->flag = take((size_t)M * 4);
-    L->list = take((size_t)M * 4);
-    const long per_block = PREP_THREADS * PREP_SCAN_ITEMS;
-    const long nb = ((cap > M ? cap : M) + per_block - 1) / per_block;
-    L->bsum = take((size_t)(nb + 1) * 4);
-    L->scal = take(64 * 4);
-    L->normal = take((size_t)M * 3 * 8);
-    L->curv = take((size_t)M * 8);
-    L->total = o;
-    return 0;
-}
-
 // ---- order-preserving integer images of floats / doubles (for atomicMin / atomicMax) ----
 __device__ __forceinline__ int prep_ord(float f) { int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
 __device__ __forceinline__ float prep_unord(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
-
-__global__ void prep_init_kernel(uint64_t *keys, int32_t *first, int32_t *count, int32_t *cursor, int cap, int32_t *scal) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cap) { keys[i] = LRG_HASH_EMPTY; first[i] = INT_MAX; count[i] = 0; cursor[i] = 0; }
-    if (i < 64) scal[i] = (i >= 2 && i <= 4) ? INT_MAX : (i >= 5 && i <= 7) ? INT_MIN : 0;
-}
-
-// voxel -> slot (insert), first raw index and population of every voxel          (:125-133)
-__global__ void prep_insert_kernel(const float *raw, int ld, int M, float res, uint64_t *keys, int32_t *first, int32_t *count,
-                                   int mask, int32_t *slot_of, int32_t *scal) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
-    const float *p = raw + (long)i * ld;
-    const uint64_t key = lrg_pack_voxel(lrg_voxel_of(p[0], res), lrg_voxel_of(p[1], res), lrg_voxel_of(p[2], res));
-    if (key == LRG_HASH_EMPTY) { scal[1] = 1; slot_of[i] = -1; return; }     // outside the 21-bit voxel window
-    unsigned h = (unsigned)lrg_fmix64(key) & (unsigned)mask;
-    while (true) {
-        unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&keys[h]), (unsigned long long)LRG_HASH_EMPTY,
-                                            (unsigned long long)key);
-        if (prev == LRG_HASH_EMPTY || prev == key) break;
-        h = (h + 1) & (unsigned)mask;
-    }
-    atomicMin(&first[h], i);
-    atomicAdd(&count[h], 1);
-    slot_of[i] = (int)h;
-}
 
 __global__ void prep_flag_kernel(const int32_t *slot_of, const int32_t *first, int M, int32_t *flag) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -154,26 +94,6 @@ static int prep_exscan(const int32_t *x, long n, int32_t *bsum, int32_t *out, hi
     return 0;
 }
 
-// equalised order = raw order of the first point of each voxel (:127-129,:134); every raw point learns its voxel's rank (:130)
-__global__ void prep_equalize_kernel(const int32_t *flag, const int32_t *rank_of_raw, const int32_t *slot_of, int M,
-                                     int32_t *equalized_idx, int32_t *hash_rank, const int32_t *bsum_total, int32_t *scal) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) scal[0] = *bsum_total;
-    if (i >= M || !flag[i]) return;
-    equalized_idx[rank_of_raw[i]] = i;
-    hash_rank[slot_of[i]] = rank_of_raw[i];
-}
-
-__global__ void prep_fill_kernel(const int32_t *slot_of, const int32_t *hash_off, const int32_t *hash_rank, int32_t *cursor, int M,
-                                 int32_t *list, int32_t *unequalized_idx) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
-    const int s = slot_of[i];
-    if (s < 0) { unequalized_idx[i] = -1; return; }
-    list[hash_off[s] + atomicAdd(&cursor[s], 1)] = i;
-    unequalized_idx[i] = hash_rank[s];
-}
-
 // raw points of a voxel in file order (normal_grid[k].append(i), :131-133)
 __global__ void prep_sort_lists_kernel(const int32_t *hash_off, const int32_t *count, int cap, int32_t *list) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -189,9 +109,8 @@ __global__ void prep_sort_lists_kernel(const int32_t *hash_off, const int32_t *c
     }
 }
 
-// The arithmetic of one equalised point, shared by the single-room kernels and the batched ones below (one definition, one order of
-// operations): covariance of the raw points in the 27 voxels around pe (:144-157).  keys / hash_off / count are the room's hash
-// segment; list and raw are indexed as hash_off says (room-relative in lrg_preprocess, file-wide in lrg_preprocess_batch).
+// The arithmetic of one equalised point: covariance of the raw points in the 27 voxels around pe (:144-157).  keys / hash_off /
+// count are the room's hash segment; list and raw are indexed as hash_off says (file-wide).
 __device__ __forceinline__ void prep_cov_point(const float *raw, int ld, float res, const float *pe, const uint64_t *keys,
                                                const int32_t *hash_off, const int32_t *count, int mask, const int32_t *list, double *C) {
     const int vx = lrg_voxel_of(pe[0], res), vy = lrg_voxel_of(pe[1], res), vz = lrg_voxel_of(pe[2], res);
@@ -285,49 +204,21 @@ __device__ __forceinline__ void prep_feature_row(const float *p, const int32_t *
     if (F >= 13) o[12] = (float)c;
 }
 
-// covariance of the raw points in the 27 voxels around every equalised point (:144-157), then normal and curvature (:158-161)
-__global__ __launch_bounds__(PREP_THREADS) void prep_cov_kernel(const float *raw, int ld, float res, const int32_t *equalized_idx,
-                                                              const int32_t *scal_n, const uint64_t *keys, const int32_t *hash_off,
-                                                              const int32_t *count, int mask, const int32_t *list, double *cov_out,
-                                                              int eig_mode, double *normal, double *curv, int32_t *scal, int32_t *nflag) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= *scal_n) return;
-    const float *pe = raw + (long)equalized_idx[e] * ld;
-    double C[9];
-    prep_cov_point(raw, ld, res, pe, keys, hash_off, count, mask, list, C);
-    if (cov_out)
-        for (int k = 0; k < 9; ++k) cov_out[(long)e * 9 + k] = C[k];
-    prep_extent_point(pe, scal);
-    if (!eig_mode) return;
-    prep_eig_point(C, eig_mode, normal + (long)e * 3, curv + e, scal, nflag ? nflag + e : nullptr);
-}
-
-// the feature stack (:163-172)
-__global__ void prep_features_kernel(const float *raw, int ld, const int32_t *obj, const int32_t *cls, const int32_t *equalized_idx,
-                                     const int32_t *scal, const double *normal, double *curv, int F, float *points, int32_t *obj_out,
-                                     int32_t *cls_out, int keep_raw_curv) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= scal[0]) return;
-    const int i = equalized_idx[e];
-    prep_feature_row(raw + (long)i * ld, scal, normal + (long)e * 3, curv + e, F, points + (long)e * F, keep_raw_curv);
-    if (obj_out) obj_out[e] = obj ? obj[i] : 0;
-    if (cls_out) cls_out[e] = cls ? cls[i] : 0;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
-// All rooms of a file in one pass (lrg_preprocess_batch).  The rooms' raw rows lie one after the other ([sum M, ld], room r =
+// All rooms of a file in one pass.  The rooms' raw rows lie one after the other ([sum M, ld], room r =
 // rows raw_start[r] .. raw_start[r + 1]); every kernel runs over the whole array (or over all hash slots), so the launch count does
-// not depend on the number of rooms.  Room r owns the hash segment at slot 4 raw_start[r] + 64 r, capacity the single-room rule (the
-// smallest power of two >= max(64, 2 M_r), which is < 4 M_r + 64): equal voxel coordinates in two rooms are keys in two tables and
+// not depend on the number of rooms.  Room r owns the hash segment at slot 4 raw_start[r] + 64 r, capacity the
+// smallest power of two >= max(64, 2 M_r) (which is < 4 M_r + 64): equal voxel coordinates in two rooms are keys in two tables and
 // never meet.  first / list / hash_off hold file-wide raw indices; ONE scan of the first-point flags ranks the equalised points of
 // all rooms back to back in room order, eq_start[r] = its value at raw_start[r]; equalized_idx / unequalized_idx are written
-// room-relative.  Every room has its own 16-word scalar block (the layout of LrgPrepLayout.scal) and its own status word.
+// room-relative.  Every room has its own status word and its own 16-word scalar block: [0] N, [1] error, [2..7] xyz min/max (ordered
+// ints), [8,9] max curvature (u64), [10] any-NaN, [14,15] eq_start of a one-room call.
 #define PB_SCAL 16
 
 struct PbLayout {
     size_t keys, first, count, off, rank, cursor;     // per hash slot (all rooms' segments)
     size_t slot, flag, list, room_of, eglob;          // per raw point (eglob: per equalised point, its file-wide raw index)
-    size_t rooms, status, bsum, scal, normal, curv;
+    size_t rooms, status, bsum, scal, normal, curv;        // rooms: the device's raw_start
     size_t total;
     long hslots;
     int n;
@@ -335,7 +226,7 @@ struct PbLayout {
 
 struct PbArgs {
     const float *raw; int ld;
-    const int32_t *obj, *cls, *raw_start;
+    const int32_t *obj, *cls; int32_t *raw_start;
     int n_rooms, n; float res; int F, eig_mode;
     uint64_t *keys; int32_t *first, *count, *off, *rank, *cursor; long hslots;
     int32_t *slot, *flag, *list, *room_of, *eglob, *bsum, *scal, *status;
@@ -398,8 +289,11 @@ __device__ __forceinline__ void pb_segment(int r, int s, int e, long *off, int *
     *mask = cap - 1;
 }
 
-__global__ __launch_bounds__(PREP_THREADS) void pb_init_kernel(PbArgs a) {
+// single_n > 0: the call is one room of single_n rows, and this kernel writes its bounds to a.raw_start itself -- no copy from the
+// host; with n_rooms = 1 the search below reads no bound, and every later kernel runs after this one
+__global__ __launch_bounds__(PREP_THREADS) void pb_init_kernel(PbArgs a, int single_n) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (single_n > 0 && t == 0) { a.raw_start[0] = 0; a.raw_start[1] = single_n; }
     if (t < a.hslots) { a.keys[t] = LRG_HASH_EMPTY; a.first[t] = INT_MAX; a.count[t] = 0; a.cursor[t] = 0; }
     if (t < (long)a.n_rooms * PB_SCAL) {
         const int k = (int)(t % PB_SCAL);
@@ -490,10 +384,16 @@ __global__ __launch_bounds__(PREP_THREADS) void pb_cov_kernel(PbArgs a) {
     prep_cov_point(a.raw, a.ld, a.res, pe, a.keys + off, a.off + off, a.count + off, mask, a.list, C);
     if (a.cov)
         for (int k = 0; k < 9; ++k) a.cov[(long)g * 9 + k] = C[k];
-    int32_t *scal = a.scal + r * PB_SCAL;
-    prep_extent_point(pe, scal);
-    if (!a.eig_mode) return;
-    prep_eig_point(C, a.eig_mode, a.normal + (long)g * 3, a.curv + g, scal, a.unsafe ? a.unsafe + g : nullptr);
+    // Every point sends min / max atomics to its room's scalars.  With a per-lane address all lanes of a room queue at the same seven
+    // words (a room alone: 3x the kernel's time, profiles/prep_one_pipeline_kernels_*.csv); with a wave-uniform address the compiler
+    // folds a wavefront's atomics into one each.  A wavefront lies in one room except at a room's edge: there the per-lane address.
+    auto finish = [&](int32_t *scal) {
+        prep_extent_point(pe, scal);
+        if (a.eig_mode) prep_eig_point(C, a.eig_mode, a.normal + (long)g * 3, a.curv + g, scal, a.unsafe ? a.unsafe + g : nullptr);
+    };
+    const int r0 = __builtin_amdgcn_readfirstlane(r);
+    if (__builtin_amdgcn_ballot_w64(r != r0) == 0) finish(a.scal + r0 * PB_SCAL);
+    else finish(a.scal + r * PB_SCAL);
 }
 
 __global__ __launch_bounds__(PREP_THREADS) void pb_features_kernel(PbArgs a) {
@@ -509,11 +409,69 @@ __global__ __launch_bounds__(PREP_THREADS) void pb_features_kernel(PbArgs a) {
     if (a.cls_out) a.cls_out[g] = a.cls ? a.cls[i] : 0;
 }
 
+// The caller's arguments that both entries check alike
+static int pb_check_modes(float resolution, int feature_size, int eig_mode, const float *points, const double *curvatures, const double *cov) {
+    if (!(resolution > 0.f)) return LRG_EINVAL - 54;
+    if (feature_size != 6 && feature_size != 9 && feature_size != 12 && feature_size != 13) return LRG_EINVAL - 55;
+    if (eig_mode != 0 && eig_mode != 1 && eig_mode != 2) return LRG_EINVAL - 56;
+    if (eig_mode >= 1 && (!points || !curvatures)) return LRG_EINVAL - 57;
+    if ((eig_mode == 0 || eig_mode == 2) && !cov) return LRG_EINVAL - 58;
+    return 0;
+}
+
+// The workspace's regions as kernel arguments; the entries add the caller's own pointers
+static PbArgs pb_carve(const PbLayout &L, void *workspace, int n_rooms) {
+    char *ws = static_cast<char *>(workspace);
+    auto i32 = [&](size_t at) { return reinterpret_cast<int32_t *>(ws + at); };
+    PbArgs a = {};
+    a.raw_start = i32(L.rooms); a.n_rooms = n_rooms; a.n = L.n;
+    a.keys = reinterpret_cast<uint64_t *>(ws + L.keys); a.first = i32(L.first); a.count = i32(L.count); a.off = i32(L.off);
+    a.rank = i32(L.rank); a.cursor = i32(L.cursor); a.hslots = L.hslots;
+    a.slot = i32(L.slot); a.flag = i32(L.flag); a.list = i32(L.list); a.room_of = i32(L.room_of); a.eglob = i32(L.eglob);
+    a.bsum = i32(L.bsum); a.scal = i32(L.scal); a.status = i32(L.status);
+    a.normal = reinterpret_cast<double *>(ws + L.normal);
+    a.curv = reinterpret_cast<double *>(ws + L.curv);
+    return a;
+}
+
+// The launches.  single_n = 0: a.raw_start already holds the rooms' bounds (copied on st); > 0: one room of single_n rows (pb_init_kernel)
+static int pb_run(const PbLayout &L, const PbArgs &a, int single_n, hipStream_t st) {
+    int rc;
+    const int n = L.n;
+    const long init_n = L.hslots > (long)n ? L.hslots : (long)n;            // (hslots >= 64 n_rooms covers the scalar blocks too)
+    const int gi = (int)((init_n + PREP_THREADS - 1) / PREP_THREADS), gh = (int)((L.hslots + PREP_THREADS - 1) / PREP_THREADS);
+    const int gm = (n + PREP_THREADS - 1) / PREP_THREADS, ge = (n + 1 + PREP_THREADS - 1) / PREP_THREADS;      // (n + 1 > n_rooms)
+    hipLaunchKernelGGL(pb_init_kernel, dim3(gi), dim3(PREP_THREADS), 0, st, a, single_n);
+    hipLaunchKernelGGL(pb_insert_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
+    hipLaunchKernelGGL(prep_flag_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a.slot, a.first, n, a.flag);
+    LRG_LAUNCH_CHECK();
+    // file-wide rank of every first point (scanned into `list`, which is filled only afterwards)
+    if ((rc = prep_exscan(a.flag, n, a.bsum, a.list, st))) return rc;
+    const long per_block = PREP_THREADS * PREP_SCAN_ITEMS;
+    const int nb_m = (int)((n + per_block - 1) / per_block);
+    hipLaunchKernelGGL(pb_equalize_kernel, dim3(ge), dim3(PREP_THREADS), 0, st, a, a.list, a.bsum + nb_m);
+    LRG_LAUNCH_CHECK();
+    if ((rc = prep_exscan(a.count, L.hslots, a.bsum, a.off, st))) return rc;
+    hipLaunchKernelGGL(pb_fill_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
+    hipLaunchKernelGGL(prep_sort_lists_kernel, dim3(gh), dim3(PREP_THREADS), 0, st, a.off, a.count, (int)L.hslots, a.list);
+    hipLaunchKernelGGL(pb_cov_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
+    if (a.eig_mode >= 1) hipLaunchKernelGGL(pb_features_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
+    LRG_LAUNCH_CHECK();
+    return 0;
+}
+
+// The one-room entries' layout: the batch's with raw_start = {0, n_raw}
+static int prep_single_layout(int n_raw, PbLayout *L) {
+    if (n_raw <= 0) return LRG_EINVAL - 50;
+    const int32_t raw_start[2] = {0, n_raw};
+    return pb_layout(raw_start, 1, L) ? LRG_EINVAL - 51 : 0;
+}
+
 extern "C" {
 
 size_t lrg_preprocess_workspace_bytes(int n_raw) {
-    LrgPrepLayout L;
-    if (prep_layout(n_raw, &L) != 0) return 0;
+    PbLayout L;
+    if (prep_single_layout(n_raw, &L) != 0) return 0;
     return L.total;
 }
 
@@ -521,56 +479,29 @@ int lrg_preprocess(const float *raw, int raw_stride, const int32_t *obj_id, cons
                    int feature_size, int eig_mode, void *workspace, size_t workspace_bytes, float *points, int32_t *obj_out,
                    int32_t *cls_out, double *curvatures, int32_t *equalized_idx, int32_t *unequalized_idx, double *cov,
                    int32_t *n_equalized, void *stream) {
-    LrgPrepLayout L;
-    int rc = prep_layout(n_raw, &L);
+    PbLayout L;
+    int rc = prep_single_layout(n_raw, &L);
     if (rc) return rc;
     if (!raw || raw_stride < 6 || !workspace || !equalized_idx || !unequalized_idx || !n_equalized) return LRG_EINVAL - 52;
     if (workspace_bytes < L.total || ((uintptr_t)workspace & 255)) return LRG_EINVAL - 53;
-    if (!(resolution > 0.f)) return LRG_EINVAL - 54;
-    if (feature_size != 6 && feature_size != 9 && feature_size != 12 && feature_size != 13) return LRG_EINVAL - 55;
-    if (eig_mode != 0 && eig_mode != 1 && eig_mode != 2) return LRG_EINVAL - 56;
-    if (eig_mode >= 1 && (!points || !curvatures)) return LRG_EINVAL - 57;
-    if ((eig_mode == 0 || eig_mode == 2) && !cov) return LRG_EINVAL - 58;
+    if ((rc = pb_check_modes(resolution, feature_size, eig_mode, points, curvatures, cov))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = static_cast<char *>(workspace);
-    uint64_t *keys = reinterpret_cast<uint64_t *>(ws + L.keys);
-    int32_t *first = reinterpret_cast<int32_t *>(ws + L.first), *count = reinterpret_cast<int32_t *>(ws + L.count);
-    int32_t *hoff = reinterpret_cast<int32_t *>(ws + L.off), *hrank = reinterpret_cast<int32_t *>(ws + L.rank);
-    int32_t *cursor = reinterpret_cast<int32_t *>(ws + L.cursor), *slot = reinterpret_cast<int32_t *>(ws + L.slot);
-    int32_t *flag = reinterpret_cast<int32_t *>(ws + L.flag), *list = reinterpret_cast<int32_t *>(ws + L.list);
-    int32_t *bsum = reinterpret_cast<int32_t *>(ws + L.bsum), *scal = reinterpret_cast<int32_t *>(ws + L.scal);
-    double *normal = reinterpret_cast<double *>(ws + L.normal);
-    double *curv = curvatures ? curvatures : reinterpret_cast<double *>(ws + L.curv);
-    const int cap = L.cap, mask = cap - 1;
-    const int gm = (n_raw + PREP_THREADS - 1) / PREP_THREADS, gc = (cap + PREP_THREADS - 1) / PREP_THREADS;
-    hipLaunchKernelGGL(prep_init_kernel, dim3(gc), dim3(PREP_THREADS), 0, st, keys, first, count, cursor, cap, scal);
-    hipLaunchKernelGGL(prep_insert_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, raw, raw_stride, n_raw, resolution, keys, first, count,
-                       mask, slot, scal);
-    hipLaunchKernelGGL(prep_flag_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, slot, first, n_raw, flag);
-    LRG_LAUNCH_CHECK();
-    // rank of every first point (in place over the flags' scan output: the flag is needed afterwards, so scan into `list`)
-    if ((rc = prep_exscan(flag, n_raw, bsum, list, st))) return rc;
-    const long per_block = PREP_THREADS * PREP_SCAN_ITEMS;
-    const int nb_m = (int)((n_raw + per_block - 1) / per_block);
-    hipLaunchKernelGGL(prep_equalize_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, flag, list, slot, n_raw, equalized_idx, hrank,
-                       bsum + nb_m, scal);
-    LRG_HIP_CHECK(hipMemcpyAsync(n_equalized, scal, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    if ((rc = prep_exscan(count, cap, bsum, hoff, st))) return rc;
-    hipLaunchKernelGGL(prep_fill_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, slot, hoff, hrank, cursor, n_raw, list, unequalized_idx);
-    hipLaunchKernelGGL(prep_sort_lists_kernel, dim3(gc), dim3(PREP_THREADS), 0, st, hoff, count, cap, list);
-    hipLaunchKernelGGL(prep_cov_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, raw, raw_stride, resolution, equalized_idx, scal, keys,
-                       hoff, count, mask, list, cov, eig_mode, normal, curv, scal, flag);
-    if (eig_mode >= 1)
-        hipLaunchKernelGGL(prep_features_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, raw, raw_stride, obj_id, cls_id, equalized_idx, scal,
-                           normal, curv, feature_size, points, obj_out, cls_out, eig_mode == 2 ? 1 : 0);
-    LRG_LAUNCH_CHECK();
+    PbArgs a = pb_carve(L, workspace, 1);
+    a.raw = raw; a.ld = raw_stride; a.obj = obj_id; a.cls = cls_id; a.res = resolution; a.F = feature_size; a.eig_mode = eig_mode;
+    if (curvatures) a.curv = curvatures;
+    a.cov = cov; a.points = points; a.obj_out = obj_out; a.cls_out = cls_out; a.equalized_idx = equalized_idx;
+    a.unequalized_idx = unequalized_idx;
+    a.eq_start = a.scal + PB_SCAL - 2;                  // (the two spare words at the end of the room's scalar block)
+    a.unsafe = eig_mode == 2 ? a.flag : nullptr;        // (the first-point flags are read for the last time before the covariances)
+    if ((rc = pb_run(L, a, n_raw, st))) return rc;
+    LRG_HIP_CHECK(hipMemcpyAsync(n_equalized, a.eq_start + 1, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
 /* eig_mode 2: which equalised points' float32 normals are not certain to equal LAPACK's (1) -- copied out of the workspace */
 int lrg_preprocess_unsafe_normals(const void *workspace, int n_raw, int n_equalized, int32_t *flags_out, void *stream) {
-    LrgPrepLayout L;
-    int rc = prep_layout(n_raw, &L);
+    PbLayout L;
+    int rc = prep_single_layout(n_raw, &L);
     if (rc) return rc;
     if (!workspace || !flags_out || n_equalized < 0 || n_equalized > n_raw) return LRG_EINVAL - 52;
     if (n_equalized == 0) return 0;
@@ -581,11 +512,11 @@ int lrg_preprocess_unsafe_normals(const void *workspace, int n_raw, int n_equali
 
 /* error flag of the last lrg_preprocess on this workspace: 1 = a point fell outside the 21-bit voxel window */
 int lrg_preprocess_status(const void *workspace, int n_raw, int32_t *host_status, void *stream) {
-    LrgPrepLayout L;
-    int rc = prep_layout(n_raw, &L);
+    PbLayout L;
+    int rc = prep_single_layout(n_raw, &L);
     if (rc) return rc;
     if (!workspace || !host_status) return LRG_EINVAL - 52;
-    LRG_HIP_CHECK(hipMemcpyAsync(host_status, static_cast<const char *>(workspace) + L.scal + 4, sizeof(int32_t), hipMemcpyDeviceToHost,
+    LRG_HIP_CHECK(hipMemcpyAsync(host_status, static_cast<const char *>(workspace) + L.status, sizeof(int32_t), hipMemcpyDeviceToHost,
                                  (hipStream_t)stream));
     LRG_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return 0;
@@ -607,49 +538,17 @@ int lrg_preprocess_batch(const float *raw, int raw_stride, const int32_t *obj_id
     if (rc) return rc;
     if (!raw || raw_stride < 6 || !workspace || !equalized_idx || !unequalized_idx || !eq_start) return LRG_EINVAL - 65;
     if (workspace_bytes < L.total || ((uintptr_t)workspace & 255)) return LRG_EINVAL - 66;
-    if (!(resolution > 0.f)) return LRG_EINVAL - 54;
-    if (feature_size != 6 && feature_size != 9 && feature_size != 12 && feature_size != 13) return LRG_EINVAL - 55;
-    if (eig_mode != 0 && eig_mode != 1 && eig_mode != 2) return LRG_EINVAL - 56;
-    if (eig_mode >= 1 && (!points || !curvatures)) return LRG_EINVAL - 57;
-    if ((eig_mode == 0 || eig_mode == 2) && !cov) return LRG_EINVAL - 58;
+    if ((rc = pb_check_modes(resolution, feature_size, eig_mode, points, curvatures, cov))) return rc;
     if (eig_mode == 2 && !unsafe_flags) return LRG_EINVAL - 67;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = static_cast<char *>(workspace);
-    auto i32 = [&](size_t at) { return reinterpret_cast<int32_t *>(ws + at); };
-    PbArgs a;
-    int32_t *rooms = i32(L.rooms);                                    // a device copy of raw_start (the caller's is host memory)
-    LRG_HIP_CHECK(hipMemcpyAsync(rooms, raw_start, (size_t)(n_rooms + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    a.raw = raw; a.ld = raw_stride; a.obj = obj_id; a.cls = cls_id; a.raw_start = rooms; a.n_rooms = n_rooms; a.n = L.n;
-    a.res = resolution; a.F = feature_size; a.eig_mode = eig_mode;
-    a.keys = reinterpret_cast<uint64_t *>(ws + L.keys); a.first = i32(L.first); a.count = i32(L.count); a.off = i32(L.off);
-    a.rank = i32(L.rank); a.cursor = i32(L.cursor); a.hslots = L.hslots;
-    a.slot = i32(L.slot); a.flag = i32(L.flag); a.list = i32(L.list); a.room_of = i32(L.room_of); a.eglob = i32(L.eglob);
-    a.bsum = i32(L.bsum); a.scal = i32(L.scal); a.status = i32(L.status);
-    a.normal = reinterpret_cast<double *>(ws + L.normal);
-    a.curv = curvatures ? curvatures : reinterpret_cast<double *>(ws + L.curv);
+    PbArgs a = pb_carve(L, workspace, n_rooms);
+    // a device copy of raw_start (the caller's is host memory)
+    LRG_HIP_CHECK(hipMemcpyAsync(a.raw_start, raw_start, (size_t)(n_rooms + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    a.raw = raw; a.ld = raw_stride; a.obj = obj_id; a.cls = cls_id; a.res = resolution; a.F = feature_size; a.eig_mode = eig_mode;
+    if (curvatures) a.curv = curvatures;
     a.cov = cov; a.points = points; a.obj_out = obj_out; a.cls_out = cls_out; a.equalized_idx = equalized_idx;
     a.unequalized_idx = unequalized_idx; a.eq_start = eq_start; a.unsafe = eig_mode == 2 ? unsafe_flags : nullptr;
-    const int n = L.n;
-    const long init_n = L.hslots > (long)n ? L.hslots : (long)n;            // (hslots >= 64 n_rooms covers the scalar blocks too)
-    const int gi = (int)((init_n + PREP_THREADS - 1) / PREP_THREADS), gh = (int)((L.hslots + PREP_THREADS - 1) / PREP_THREADS);
-    const int gm = (n + PREP_THREADS - 1) / PREP_THREADS, ge = (n + 1 + PREP_THREADS - 1) / PREP_THREADS;      // (n + 1 > n_rooms)
-    hipLaunchKernelGGL(pb_init_kernel, dim3(gi), dim3(PREP_THREADS), 0, st, a);
-    hipLaunchKernelGGL(pb_insert_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
-    hipLaunchKernelGGL(prep_flag_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a.slot, a.first, n, a.flag);
-    LRG_LAUNCH_CHECK();
-    // file-wide rank of every first point (scanned into `list`, which is filled only afterwards)
-    if ((rc = prep_exscan(a.flag, n, a.bsum, a.list, st))) return rc;
-    const long per_block = PREP_THREADS * PREP_SCAN_ITEMS;
-    const int nb_m = (int)((n + per_block - 1) / per_block);
-    hipLaunchKernelGGL(pb_equalize_kernel, dim3(ge), dim3(PREP_THREADS), 0, st, a, a.list, a.bsum + nb_m);
-    LRG_LAUNCH_CHECK();
-    if ((rc = prep_exscan(a.count, L.hslots, a.bsum, a.off, st))) return rc;
-    hipLaunchKernelGGL(pb_fill_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
-    hipLaunchKernelGGL(prep_sort_lists_kernel, dim3(gh), dim3(PREP_THREADS), 0, st, a.off, a.count, (int)L.hslots, a.list);
-    hipLaunchKernelGGL(pb_cov_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
-    if (eig_mode >= 1) hipLaunchKernelGGL(pb_features_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
-    LRG_LAUNCH_CHECK();
-    return 0;
+    return pb_run(L, a, 0, st);
 }
 
 /* error flags of the last lrg_preprocess_batch on this workspace, one per room: 1 = a point of the room fell outside the voxel window */

@@ -1,4 +1,4 @@
-"""Room preprocessing P0 on the GPU (C-ABI ``lrg_preprocess``; the reference block is test_region_grow.py:119-173).
+"""Room preprocessing P0 on the GPU (C-ABI ``lrg_preprocess_batch``; the reference block is test_region_grow.py:119-173).
 
 ``preprocess_room`` has the signature and return dict of ``preprocess.preprocess_room`` (the host NumPy version).
 
@@ -16,10 +16,10 @@ eig='exact'   the Jacobi solve on the GPU, VERIFIED: both solvers are backward s
               everything the region-grow loop reads -- equal the host version bit for bit; ``curvatures`` (float64, not read by the
               loop) are LAPACK's where redone and within 1e-13 elsewhere.  The all-GPU rate instead of a host decomposition per point.
 
-``preprocess_rooms`` does the same for a list of rooms through ``lrg_preprocess_batch``: the rooms of a chunk (``plan_chunks``) go to the
+There is one pipeline: ``preprocess_rooms`` takes a list of rooms, and ``preprocess_room`` is a chunk of one room.  The rooms of a chunk (``plan_chunks``) go to the
 device as one array and through one fixed set of launches, and come back with one copy per output array; the host finishes of 'exact'
 and 'lapack' call ``numpy.linalg.svd`` once per pass on the stacked covariances of all rooms.  Every room's dict equals what
-``preprocess_room`` returns for that room alone, bit for bit.
+the room gives alone, bit for bit.
 """
 import ctypes
 import time
@@ -43,129 +43,6 @@ def _lapack(cov_h):
     return np.fabs(V[:, 2, :]), np.fabs(S[:, 2] / (S[:, 0] + S[:, 1] + S[:, 2]))
 
 
-def _exact_finish(lib, dev, ws, M, N, pts, obj_o, cls_o, curv, cov, F, st):
-    """eig='exact': Jacobi results from the GPU, the points whose float32 features or seed-order position could differ under LAPACK redone
-    with LAPACK.  Returns points / obj_id / cls_id / curvatures / order."""
-    nflag = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
-    _lib.check(lib.lrg_preprocess_unsafe_normals(_ptr(ws), M, N, _ptr(nflag), st), 'lrg_preprocess_unsafe_normals')
-    c = curv[:N].cpu().numpy().copy()                    # un-normalised S[2] / sum(S) by Jacobi
-    feats = pts[:N].cpu().numpy()
-    unsafe_n = nflag[:N].cpu().numpy().astype(bool)
-    stats = dict(points=N)
-    if not np.isfinite(c).all():                         # degenerate room (a NaN curvature poisons the maximum, :163): every point through LAPACK
-        redo = np.ones(N, dtype=bool)
-    else:
-        redo = unsafe_n | (c >= c.max() - 2.0 * EXACT_SLACK)        # ... and whoever could be the maximum
-    exact = np.zeros(N, dtype=bool)
-    normals = None
-
-    def redo_points(mask):
-        nonlocal normals
-        idx = np.nonzero(mask & ~exact)[0]
-        if len(idx) == 0:
-            return
-        cov_h = cov[torch.from_numpy(idx).to(dev)].cpu().numpy().reshape(-1, 3, 3)
-        nrm, cc = _lapack(cov_h)
-        c[idx] = cc
-        if F >= 12:
-            feats[idx, 9:12] = nrm.astype(np.float32)
-        exact[idx] = True
-    redo_points(redo)
-    stats['first_pass'] = int(exact.sum())
-    cmax = c[exact].max() if exact.any() else c.max()                  # LAPACK's maximum: the true one is among the candidates
-    cn = c / cmax                                                       # (:163; the reference's own operation for the exact ones)
-    dn = np.where(exact, 0.0, EXACT_SLACK / cmax * (1.0 + 1e-9))
-    amb = (cn - dn).astype(np.float32) != (cn + dn).astype(np.float32)
-    s = np.argsort(cn)
-    # neighbours in the seed order closer than TWICE the sum of their slacks: after the redo a point has moved by at most its slack, and
-    # the true value of an untouched neighbour lies within its own -- what is left of the gap keeps every pair's order
-    close = np.diff(cn[s]) <= 2.0 * (dn[s][1:] + dn[s][:-1])
-    near = np.zeros(N, dtype=bool)
-    near[s[1:][close]] = True
-    near[s[:-1][close]] = True
-    again = (amb | near) & ~exact
-    if again.any():
-        redo_points(again)
-        cn = c / cmax
-    stats['lapack_points'] = int(exact.sum())
-    if F >= 13:
-        feats[:, 12] = cn.astype(np.float32)
-    return dict(points=feats, obj_id=obj_o[:N].cpu().numpy(), cls_id=cls_o[:N].cpu().numpy(), curvatures=cn, order=np.argsort(cn), exact_stats=stats)
-
-
-def preprocess_room(unequalized_points, obj_id, cls_id, resolution=0.1, feature_size=13, eig='jacobi', device='cuda:0',
-                    return_device=False):
-    lib = _lib.load()
-    if not torch.cuda.is_available():
-        raise _lib.LrgHipError('preprocess_gpu needs a GPU (use learn_region_grow_amd.preprocess on the host)')
-    if eig not in ('jacobi', 'lapack', 'exact'):
-        raise ValueError(eig)
-    dev = torch.device(device)
-    raw_np = np.ascontiguousarray(np.asarray(unequalized_points)[:, :6], dtype=np.float32)
-    M = len(raw_np)
-    if M == 0:
-        raise ValueError('empty room')
-    with torch.cuda.device(dev):
-        raw = torch.from_numpy(raw_np).to(dev)
-        obj = torch.from_numpy(np.ascontiguousarray(obj_id, dtype=np.int32)).to(dev)
-        cls = torch.from_numpy(np.ascontiguousarray(cls_id, dtype=np.int32)).to(dev)
-        ws = torch.empty(lib.lrg_preprocess_workspace_bytes(M), dtype=torch.uint8, device=dev)
-        eq = torch.empty(M, dtype=torch.int32, device=dev)
-        uneq = torch.empty(M, dtype=torch.int32, device=dev)
-        n_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        mode = {'jacobi': 1, 'lapack': 0, 'exact': 2}[eig]
-        pts = torch.empty((M, feature_size), dtype=torch.float32, device=dev) if mode else None
-        obj_o = torch.empty(M, dtype=torch.int32, device=dev) if mode else None
-        cls_o = torch.empty(M, dtype=torch.int32, device=dev) if mode else None
-        curv = torch.empty(M, dtype=torch.float64, device=dev) if mode else None
-        cov = torch.empty((M, 9), dtype=torch.float64, device=dev) if mode != 1 else None
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        rc = lib.lrg_preprocess(_ptr(raw), 6, _ptr(obj), _ptr(cls), M, ctypes.c_float(resolution), feature_size, mode, _ptr(ws),
-                                ws.numel(), _ptr(pts), _ptr(obj_o), _ptr(cls_o), _ptr(curv), _ptr(eq), _ptr(uneq), _ptr(cov),
-                                _ptr(n_dev), st)
-        _lib.check(rc, 'lrg_preprocess')
-        status = ctypes.c_int32(0)
-        _lib.check(lib.lrg_preprocess_status(_ptr(ws), M, ctypes.byref(status), st), 'lrg_preprocess_status')
-        if status.value:
-            raise _lib.LrgHipError('a point lies outside the +-2^20 voxel window at resolution %g' % resolution)
-        N = int(n_dev.item())
-        equalized_idx = eq[:N].cpu().numpy().astype(np.int64)
-        unequalized_idx = uneq.cpu().numpy().astype(np.int64)
-        if mode == 2:
-            out = _exact_finish(lib, dev, ws, M, N, pts, obj_o, cls_o, curv, cov, feature_size, st)
-            out.update(equalized_idx=equalized_idx, unequalized_idx=unequalized_idx)
-            if return_device:
-                out['points_device'] = torch.from_numpy(out['points']).to(dev)
-            return out
-        if mode:
-            c = curv[:N].cpu().numpy()
-            out = dict(points=pts[:N].cpu().numpy(), obj_id=obj_o[:N].cpu().numpy(), cls_id=cls_o[:N].cpu().numpy(), curvatures=c,
-                       order=np.argsort(c), equalized_idx=equalized_idx, unequalized_idx=unequalized_idx)
-            if return_device:
-                out['points_device'] = pts[:N]
-            return out
-        cov_h = cov[:N].cpu().numpy().reshape(N, 3, 3)
-    # ---- host finish, the reference's own calls (:158-172) ----
-    points = raw_np[equalized_idx]
-    xyz, rgb = points[:, :3], points[:, 3:6]
-    room_coordinates = (xyz - xyz.min(axis=0)) / (xyz.max(axis=0) - xyz.min(axis=0))
-    _, S, V = np.linalg.svd(cov_h)
-    normals = np.fabs(V[:, 2, :])
-    c = np.fabs(S[:, 2] / (S[:, 0] + S[:, 1] + S[:, 2]))
-    c = c / c.max()
-    if feature_size == 6:
-        feats = np.hstack((xyz, room_coordinates)).astype(np.float32)
-    elif feature_size == 9:
-        feats = np.hstack((xyz, room_coordinates, rgb)).astype(np.float32)
-    elif feature_size == 12:
-        feats = np.hstack((xyz, room_coordinates, rgb, normals)).astype(np.float32)
-    else:
-        feats = np.hstack((xyz, room_coordinates, rgb, normals, c.reshape(-1, 1))).astype(np.float32)
-    return dict(points=feats, obj_id=np.asarray(obj_id)[equalized_idx].astype(np.int32),
-                cls_id=np.asarray(cls_id)[equalized_idx].astype(np.int32), curvatures=c, order=np.argsort(c),
-                equalized_idx=equalized_idx, unequalized_idx=unequalized_idx)
-
-
 # ---- all rooms of a file in one device pass ----
 DEFAULT_MAX_RAW_POINTS = 1 << 22       # raw points per lrg_preprocess_batch call: ~300 bytes of workspace and outputs per raw point on the device
 
@@ -187,8 +64,9 @@ def plan_chunks(sizes, max_raw_points):
 
 
 def exact_finish_batch(eq_start, curv, feats, unsafe, fetch_cov, feature_size, timing=None):
-    """The host finish of eig='exact' for the rooms of one batch: `_exact_finish`'s decisions room by room, its LAPACK calls once per pass
-    on the covariances of all rooms.  NumPy in, NumPy out -- no GPU needed:
+    """The host finish of eig='exact' for the rooms of one batch: Jacobi results from the GPU, the points whose float32 features or seed-order
+    position could differ under LAPACK redone with LAPACK -- the decisions room by room, the LAPACK calls once per pass on the covariances
+    of all rooms.  NumPy in, NumPy out -- no GPU needed:
 
     eq_start [R + 1]        equalised rows of room r are eq_start[r] .. eq_start[r + 1] of everything below
     curv [N] float64        un-normalised S[2] / sum(S) of the device solve (not modified)
@@ -226,10 +104,10 @@ def exact_finish_batch(eq_start, curv, feats, unsafe, fetch_cov, feature_size, t
     redo = np.zeros(N, dtype=bool)
     for a, b in bounds:
         cr = c[a:b]
-        if not np.isfinite(cr).all():                        # degenerate room: every point through LAPACK
+        if not np.isfinite(cr).all():                        # degenerate room (a NaN curvature poisons the maximum, :163): every point through LAPACK
             redo[a:b] = True
         else:
-            redo[a:b] = unsafe[a:b] | (cr >= cr.max() - 2.0 * EXACT_SLACK)
+            redo[a:b] = unsafe[a:b] | (cr >= cr.max() - 2.0 * EXACT_SLACK)        # ... and whoever could be the maximum
     redo_points(redo)
     stats = [dict(points=b - a, first_pass=int(exact[a:b].sum())) for a, b in bounds]
     again = np.zeros(N, dtype=bool)
@@ -244,7 +122,9 @@ def exact_finish_batch(eq_start, curv, feats, unsafe, fetch_cov, feature_size, t
         t0 = clock()
         s = np.argsort(cn)
         spend('argsort', t0)
-        close = np.diff(cn[s]) <= 2.0 * (dn[s][1:] + dn[s][:-1])      # (see _exact_finish)
+        # neighbours in the seed order closer than TWICE the sum of their slacks: after the redo a point has moved by at most its slack, and
+        # the true value of an untouched neighbour lies within its own -- what is left of the gap keeps every pair's order
+        close = np.diff(cn[s]) <= 2.0 * (dn[s][1:] + dn[s][:-1])
         near = np.zeros(b - a, dtype=bool)
         near[s[1:][close]] = True
         near[s[:-1][close]] = True
@@ -263,7 +143,8 @@ def exact_finish_batch(eq_start, curv, feats, unsafe, fetch_cov, feature_size, t
     return out
 
 
-def _preprocess_chunk(lib, dev, rooms, first_room, resolution, F, mode, timing):
+def _preprocess_chunk(lib, dev, rooms, first_room, resolution, F, mode, timing, single=False):
+    """The rooms of one lrg_preprocess_batch call, start to finish.  single: the call is preprocess_room's (errors name no room)."""
     clock = time.perf_counter
     t_begin = clock()
     sizes = [len(p) for p, _, _ in rooms]
@@ -282,13 +163,12 @@ def _preprocess_chunk(lib, dev, rooms, first_room, resolution, F, mode, timing):
     rs_p = raw_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
     nbytes = lib.lrg_preprocess_batch_workspace_bytes(rs_p, R)
     if nbytes == 0:
-        raise _lib.LrgHipError('lrg_preprocess_batch: %d rooms with %d raw points do not fit one call (lower max_raw_points)' % (R, int(sum(sizes))))
+        raise _lib.LrgHipError('a room of %d raw points is too large for the hash tables' % M if single else
+                               'lrg_preprocess_batch: %d rooms with %d raw points do not fit one call (lower max_raw_points)' % (R, M))
     spent = {}
     with torch.cuda.device(dev):
         t0 = clock()
-        raw = torch.from_numpy(raw_np).to(dev)
-        obj = torch.from_numpy(obj_np).to(dev)
-        cls = torch.from_numpy(cls_np).to(dev)
+        raw = torch.from_numpy(raw_np).to(dev)        # (the ids stay on the host: every mode gathers them there with equalized_idx)
         spent['copies'] = clock() - t0
         t0 = clock()
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -296,23 +176,20 @@ def _preprocess_chunk(lib, dev, rooms, first_room, resolution, F, mode, timing):
         uneq = torch.empty(M, dtype=torch.int32, device=dev)
         eqs_dev = torch.empty(R + 1, dtype=torch.int32, device=dev)
         pts = torch.empty((M, F), dtype=torch.float32, device=dev) if mode else None
-        obj_o = torch.empty(M, dtype=torch.int32, device=dev) if mode else None
-        cls_o = torch.empty(M, dtype=torch.int32, device=dev) if mode else None
         curv = torch.empty(M, dtype=torch.float64, device=dev) if mode else None
         cov = torch.empty((M, 9), dtype=torch.float64, device=dev) if mode != 1 else None
         nflag = torch.empty(M, dtype=torch.int32, device=dev) if mode == 2 else None
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        rc = lib.lrg_preprocess_batch(_ptr(raw), 6, _ptr(obj), _ptr(cls), rs_p, R, ctypes.c_float(resolution), F, mode, _ptr(ws), ws.numel(),
-                                      _ptr(pts), _ptr(obj_o), _ptr(cls_o), _ptr(curv), _ptr(eq), _ptr(uneq), _ptr(cov), _ptr(eqs_dev),
-                                      _ptr(nflag), st)
-        _lib.check(rc, 'lrg_preprocess_batch')
+        rc = lib.lrg_preprocess_batch(_ptr(raw), 6, None, None, rs_p, R, ctypes.c_float(resolution), F, mode, _ptr(ws), ws.numel(),
+                                      _ptr(pts), None, None, _ptr(curv), _ptr(eq), _ptr(uneq), _ptr(cov), _ptr(eqs_dev), _ptr(nflag), st)
+        _lib.check(rc, 'lrg_preprocess_batch (one room)' if single else 'lrg_preprocess_batch')
         status = (ctypes.c_int32 * R)()
         _lib.check(lib.lrg_preprocess_batch_status(_ptr(ws), rs_p, R, status, st), 'lrg_preprocess_batch_status')
         spent['device'] = clock() - t0
         bad = [first_room + k for k in range(R) if status[k]]
         if bad:
-            raise _lib.LrgHipError('room %s: a point lies outside the +-2^20 voxel window at resolution %g'
-                                   % (', '.join(str(b) for b in bad), resolution))
+            raise _lib.LrgHipError('%sa point lies outside the +-2^20 voxel window at resolution %g'
+                                   % ('' if single else 'room %s: ' % ', '.join(str(b) for b in bad), resolution))
         t0 = clock()
         eq_start = eqs_dev.cpu().numpy().astype(np.int64)
         N = int(eq_start[-1])
@@ -320,7 +197,6 @@ def _preprocess_chunk(lib, dev, rooms, first_room, resolution, F, mode, timing):
         uneq_h = uneq.cpu().numpy().astype(np.int64)
         if mode:
             feats = pts[:N].cpu().numpy()
-            obj_h, cls_h = obj_o[:N].cpu().numpy(), cls_o[:N].cpu().numpy()
             c_h = curv[:N].cpu().numpy()
         if mode == 2:
             unsafe_h = nflag[:N].cpu().numpy()
@@ -347,13 +223,12 @@ def _preprocess_chunk(lib, dev, rooms, first_room, resolution, F, mode, timing):
         equalized_idx, unequalized_idx = eq_h[a:b], uneq_h[s0:s1]
         if mode == 2:
             d = fin[k]
-            d.update(obj_id=obj_h[a:b], cls_id=cls_h[a:b])
         elif mode == 1:
             c = c_h[a:b]
             t0 = clock()
             order = np.argsort(c)
             spent['argsort'] = spent.get('argsort', 0.0) + clock() - t0
-            d = dict(points=feats[a:b], obj_id=obj_h[a:b], cls_id=cls_h[a:b], curvatures=c, order=order)
+            d = dict(points=feats[a:b], curvatures=c, order=order)
         else:
             points = raw_np[s0:s1][equalized_idx]
             xyz, rgb = points[:, :3], points[:, 3:6]
@@ -366,9 +241,8 @@ def _preprocess_chunk(lib, dev, rooms, first_room, resolution, F, mode, timing):
             t0 = clock()
             order = np.argsort(c)
             spent['argsort'] = spent.get('argsort', 0.0) + clock() - t0
-            d = dict(points=np.hstack(cols).astype(np.float32), obj_id=np.asarray(rooms[k][1])[equalized_idx].astype(np.int32),
-                     cls_id=np.asarray(rooms[k][2])[equalized_idx].astype(np.int32), curvatures=c, order=order)
-        d.update(equalized_idx=equalized_idx, unequalized_idx=unequalized_idx)
+            d = dict(points=np.hstack(cols).astype(np.float32), curvatures=c, order=order)
+        d.update(obj_id=obj_np[s0:s1][equalized_idx], cls_id=cls_np[s0:s1][equalized_idx], equalized_idx=equalized_idx, unequalized_idx=unequalized_idx)
         out.append(d)
     if timing is not None:
         spent['total'] = clock() - t_begin
@@ -398,3 +272,16 @@ def preprocess_rooms(rooms, resolution=0.1, feature_size=13, eig='jacobi', devic
     for first, last in plan_chunks(sizes, max_raw_points):
         out.extend(_preprocess_chunk(lib, dev, rooms[first:last], first, resolution, feature_size, mode, timing))
     return out
+
+
+def preprocess_room(unequalized_points, obj_id, cls_id, resolution=0.1, feature_size=13, eig='jacobi', device='cuda:0'):
+    """One room: a chunk of one."""
+    lib = _lib.load()
+    if not torch.cuda.is_available():
+        raise _lib.LrgHipError('preprocess_gpu needs a GPU (use learn_region_grow_amd.preprocess on the host)')
+    if eig not in ('jacobi', 'lapack', 'exact'):
+        raise ValueError(eig)
+    if len(unequalized_points) == 0:
+        raise ValueError('empty room')
+    mode = {'jacobi': 1, 'lapack': 0, 'exact': 2}[eig]
+    return _preprocess_chunk(lib, torch.device(device), [(unequalized_points, obj_id, cls_id)], 0, resolution, feature_size, mode, None, single=True)[0]

@@ -1,6 +1,9 @@
-"""GPU: all rooms of a file in one device pass (lrg_preprocess_batch, preprocess_gpu.preprocess_rooms) against the single-room entry
-(lrg_preprocess, preprocess_gpu.preprocess_room: this file's yardstick, bit for bit) and against the oracle loop."""
+"""GPU: all rooms of a file in one device pass (lrg_preprocess_batch, preprocess_gpu.preprocess_rooms).  The single-room entries
+(lrg_preprocess, preprocess_gpu.preprocess_room) are the same pipeline with one room, so "the batch equals every room alone, bit for
+bit" is the room-isolation test, not an independent yardstick.  The independent ones: the digests of everything lrg_preprocess wrote
+when it still had launches of its own (tests/golden/preprocess_single_room.json, tools/prep_golden_digests.py), and the oracle loop."""
 import ctypes
+import json
 import os
 import subprocess
 import sys
@@ -11,6 +14,9 @@ import pytest
 from learn_region_grow_amd import checkpoint, synthetic
 from learn_region_grow_amd import io as lio
 from oracle import preprocess_ref
+import prep_fixtures as P
+from prep_fixtures import _ptr, raw_room, six_rooms
+from prep_fixtures import capi_single as _capi_single
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,63 +24,10 @@ KEYS = ('points', 'obj_id', 'cls_id', 'curvatures', 'order', 'equalized_idx', 'u
 MODES = {'lapack': 0, 'jacobi': 1, 'exact': 2}
 
 
-def raw_room(seed, n=2500, wlh=(1.6, 1.3, 1.0)):
-    r = synthetic.generate_room_points(n, seed, wlh=wlh).astype(np.float32)
-    return r[:, :6], r[:, 6].astype(int), r[:, 7].astype(int)
-
-
-def degenerate_room():
-    """tests/test_gpu_preprocess.py::test_degenerate_inputs: one crowded voxel and isolated points (NaN curvature)."""
-    rs = np.random.RandomState(0)
-    raw = np.zeros((400, 6), np.float32)
-    raw[:300, :3] = 0.5 + rs.rand(300, 3) * 0.04
-    raw[300:, :3] = rs.rand(100, 3) * 3
-    raw[:, 3:6] = rs.rand(400, 3)
-    obj = np.arange(400) % 7
-    return raw, obj, obj
-
-
-def six_rooms():
-    """Twice the same room (same voxels: the two must not see each other), two more, a single point, the degenerate room."""
-    one = raw_room(1)
-    return [one, (one[0].copy(), one[1].copy(), one[2].copy()), raw_room(2), raw_room(3), (one[0][:1], one[1][:1], one[2][:1]), degenerate_room()]
-
-
 def _same(got, want, keys=KEYS, what=''):
     for k in keys:
         assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, (what, k, got[k].dtype, want[k].dtype, got[k].shape, want[k].shape)
         np.testing.assert_array_equal(got[k], want[k], err_msg='%s %s' % (what, k))           # (NaN == NaN)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _capi_single(lib, dev, room, F, mode):
-    """lrg_preprocess on one room: everything it writes, as it writes it."""
-    import torch
-    raw_np = np.ascontiguousarray(room[0][:, :6], np.float32)
-    M = len(raw_np)
-    raw = torch.from_numpy(raw_np).to(dev)
-    obj = torch.from_numpy(np.ascontiguousarray(room[1], np.int32)).to(dev)
-    cls = torch.from_numpy(np.ascontiguousarray(room[2], np.int32)).to(dev)
-    ws = torch.empty(lib.lrg_preprocess_workspace_bytes(M), dtype=torch.uint8, device=dev)
-    eq, uneq, n_dev = (torch.empty(M, dtype=torch.int32, device=dev) for _ in range(3))
-    pts = torch.empty((M, F), dtype=torch.float32, device=dev)
-    obj_o, cls_o, nflag = (torch.empty(M, dtype=torch.int32, device=dev) for _ in range(3))
-    curv = torch.empty(M, dtype=torch.float64, device=dev)
-    cov = torch.empty((M, 9), dtype=torch.float64, device=dev)
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    assert lib.lrg_preprocess(_ptr(raw), 6, _ptr(obj), _ptr(cls), M, ctypes.c_float(0.1), F, mode, _ptr(ws), ws.numel(), _ptr(pts), _ptr(obj_o),
-                              _ptr(cls_o), _ptr(curv), _ptr(eq), _ptr(uneq), _ptr(cov), _ptr(n_dev), st) == 0
-    N = int(n_dev[0].item())
-    out = dict(eq=eq[:N], uneq=uneq, cov=cov[:N])
-    if mode:
-        out.update(points=pts[:N], obj=obj_o[:N], cls=cls_o[:N], curv=curv[:N])
-    if mode == 2:
-        assert lib.lrg_preprocess_unsafe_normals(_ptr(ws), M, N, _ptr(nflag), st) == 0
-        out['unsafe'] = nflag[:N]
-    return {k: v.cpu().numpy() for k, v in out.items()}
 
 
 class Batch:
@@ -157,6 +110,30 @@ def test_batch_equals_the_single_room_entry(cuda_device, hip_lib, rooms6, eig, F
         _same(g, w, keys=sorted(w), what='C-ABI room %d' % k)
 
 
+def test_digests_of_the_single_room_pipeline(cuda_device, hip_lib, rooms6):
+    """Everything lrg_preprocess writes for each of the six rooms (2 500, 2 500, 2 500, 2 500, 1 and 400 raw points), every feature size
+    and eig_mode, and the same from room slices of ONE lrg_preprocess_batch call: the sha256 digests recorded from the single-room
+    launches before the two pipelines became one.  Bit-exact by construction (nothing written out depends on atomic order); the bits do
+    depend on the compiler that builds the library, so the file names it."""
+    with open(os.path.join(ROOT, 'tests', 'golden', 'preprocess_single_room.json')) as f:
+        gold = json.load(f)
+    assert gold['raw_points'] == [len(r[0]) for r in rooms6]
+    built = P.hipcc_version()
+    note = 'same compiler as recorded' if built == gold['hipcc_version'] else \
+        'the library was built by another compiler than the file records (record again with tools/prep_golden_digests.py): %r, recorded %r' % (built, gold['hipcc_version'])
+    assert len(gold['digests']) == len(P.DIGEST_F) * len(P.DIGEST_MODES) * 6
+    for F in P.DIGEST_F:
+        b = Batch(hip_lib, cuda_device, rooms6, F)
+        for mode in P.DIGEST_MODES:
+            assert b.call(mode) == 0
+            for k, (g, room) in enumerate(zip(b.rooms(mode), rooms6)):
+                want = gold['digests'][P.digest_key(F, mode, k)]
+                w = _capi_single(hip_lib, cuda_device, room, F, mode)
+                assert len(w['eq']) == len(g['eq']) == gold['n_equalized'][k]
+                assert P.digests(w, mode) == want, ('lrg_preprocess', F, mode, k, note)
+                assert P.digests(g, mode) == want, ('lrg_preprocess_batch', F, mode, k, note)
+
+
 @pytest.fixture(scope='module')
 def oracle_rooms():
     rooms = [raw_room(seed) for seed in (1, 2, 5, 7)]
@@ -236,6 +213,45 @@ def test_errors(cuda_device, hip_lib):
     assert wb(b.rs([0, rs[2], rs[1], rs[3], rs[4]]), 4) == 0 and wb(b.rs([0, rs[1], rs[1], rs[3], rs[4]]), 4) == 0
     assert wb(b.rs([1, rs[1], rs[2], rs[3], rs[4]]), 4) == 0
     assert wb(b.rs([0, 1 << 30]), 1) == 0 and wb(b.rs([0, 1 << 29]), 1) == 0          # sum M, and the hash segments, past int32
+
+
+def test_single_room_entry_codes_and_status(cuda_device, hip_lib):
+    """lrg_preprocess is the batch with one room and keeps its own codes, in its own precedence; its status is the room's word."""
+    import torch
+    from learn_region_grow_amd import _lib
+    E = _lib.LRG_EINVAL
+    raw_np, _, _ = raw_room(1, n=600)
+    far_np = raw_np.copy()
+    far_np[5, 0] = 3e5
+    M, dev = len(raw_np), cuda_device
+    nbytes = hip_lib.lrg_preprocess_workspace_bytes(M)
+    assert nbytes > 0 and hip_lib.lrg_preprocess_workspace_bytes(0) == 0 and hip_lib.lrg_preprocess_workspace_bytes(1 << 29) == 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    eq, uneq, n_dev, obj_o, cls_o = (torch.empty(M, dtype=torch.int32, device=dev) for _ in range(5))
+    pts = torch.empty((M, 13), dtype=torch.float32, device=dev)
+    curv = torch.empty(M, dtype=torch.float64, device=dev)
+    cov = torch.empty((M, 9), dtype=torch.float64, device=dev)
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def call(raw, n_raw=M, eq=eq, ws_bytes=nbytes, mode=1):
+        return hip_lib.lrg_preprocess(_ptr(raw), 6, None, None, n_raw, ctypes.c_float(0.1), 13, mode, _ptr(ws), ws_bytes, _ptr(pts), _ptr(obj_o),
+                                      _ptr(cls_o), _ptr(curv), _ptr(eq), _ptr(uneq), _ptr(cov), _ptr(n_dev), st)
+
+    def status():
+        got = ctypes.c_int32(-1)
+        assert hip_lib.lrg_preprocess_status(_ptr(ws), M, ctypes.byref(got), st) == 0
+        return got.value
+    raw, far = torch.from_numpy(raw_np).to(dev), torch.from_numpy(far_np).to(dev)
+    # refused before anything is launched
+    assert call(raw, n_raw=0) == E - 50
+    assert call(raw, n_raw=1 << 29) == E - 51
+    assert call(raw, eq=None) == E - 52
+    assert call(raw, ws_bytes=nbytes - 1) == E - 53
+    assert call(raw, mode=3) == E - 56
+    assert call(raw, n_raw=0, eq=None, mode=3) == E - 50 and call(raw, eq=None, ws_bytes=nbytes - 1, mode=3) == E - 52       # precedence
+    # the room with the far point, then a clean room on the same workspace
+    assert call(far) == 0 and status() == 1
+    assert call(raw) == 0 and status() == 0
 
 
 def test_same_batch_twice_same_bits(cuda_device, hip_lib, rooms6):
