@@ -42,6 +42,9 @@ def parse(argv=None):
     ap.add_argument('--features', default='lapack', choices=('lapack', 'verified'),
                     help="3x3 decompositions: 'lapack' = numpy.linalg.svd for every point on the host; 'verified' = on the GPU, LAPACK only "
                          'for the points the certificate names (same labels)')
+    ap.add_argument('--metrics', default='host', choices=('host', 'device'),
+                    help="the per-room evaluation: 'host' = metrics.room_metrics room by room; 'device' = all rooms of a segmentation call in one "
+                         'pass on the GPU (metrics_gpu.room_metrics_batch)')
     return ap.parse_args(argv)
 
 
@@ -84,11 +87,16 @@ def main(argv=None):
             labels = baselines.segment(feats, args.mode, resolution=args.resolution, device=args.device, thresholds=t)
             seg = time.time() - t0
             total = max(1, sum(len(f['points']) for f in feats))
+            room_ms = None
+            if args.metrics == 'device':
+                from learn_region_grow_amd import metrics_gpu
+                room_ms = metrics_gpu.room_metrics_batch([obj_ids[r][feats[j]['equalized_idx']] for j, r in enumerate(batch)],
+                                                         [lab.astype(np.int64) for lab in labels], device=args.device)
             for j, r in enumerate(batch):
                 f, lab = feats[j], labels[j].astype(np.int64)
                 print('%s %d points: %.2fs' % (names[r] if names is not None and r < len(names) else '', len(rooms[r]),
                                                ftime[j] + seg * len(f['points']) / total))
-                m = metrics.room_metrics(obj_ids[r][f['equalized_idx']], lab)
+                m = room_ms[j] if room_ms is not None else metrics.room_metrics(obj_ids[r][f['equalized_idx']], lab)
                 ms.append(m)
                 print(metrics.room_line(area, r, m))
                 if args.save is not None:

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 12
+#define LRG_ABI_VERSION 13
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -850,6 +850,50 @@ int lrg_preprocess_batch(const float *raw, int raw_stride, const int32_t *obj_id
 /* test_region_grow.py:119-173, the batch's lrg_preprocess_status: host_status_per_room [n_rooms] (host), 1 = a point of that room lies
  * outside the voxel window (it was left out; the room's outputs are not valid).  Synchronises the stream. */
 int lrg_preprocess_batch_status(const void *workspace, const int32_t *raw_start, int n_rooms, int32_t *host_status_per_room, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 13.  The evaluation block that follows a labelled room (test_region_grow.py:319-355, test_mcpnet.py:146-170: greedy IoU > 0.5
+ * matching, PRC / RCL / mean best IoU, the relabelled clusters, and what sklearn's NMI / AMI / ARS are made of) for all rooms of a call in
+ * one pass: a fixed number of launches whatever n_rooms is, everything on the stream, nothing allocated.
+ *
+ * Device inputs, the rooms one after the other: labels [sum N] = each room's cluster_label (0 = none, 1 .. C_r); gt_row [sum N] = the row of
+ * each point's ground-truth instance (the return_inverse of numpy.unique(obj_id)); order [sum G] = per room the order in which the GT rows
+ * are visited (numpy.argsort(count)[::-1] at test_region_grow.py:327, set(obj_id) order at test_mcpnet.py:152 -- the host's, because both are
+ * NumPy / Python behaviour); relabel [sum G] = the value a cluster matched at visit k receives (k + 1, or the instance's id);
+ * unmatched_base [n_rooms] = obj_id.max() (:339-341).  HOST arrays, copied on the stream: room_start [n_rooms + 1] and gt_start [n_rooms + 1]
+ * (both begin at 0 and increase strictly: room r has N_r = room_start[r + 1] - room_start[r] points and G_r GT rows), n_cluster [n_rooms] = C_r.
+ * flags bit 0: leave out the scores' float sums (the analogue of with_sklearn=False).
+ *
+ * Outputs (device): cluster_label2 [sum N] (matched cluster -> relabel[k], unmatched cluster j -> j + unmatched_base, 0 -> 0); best_iou
+ * [sum G] float64 in visit order, with the host's bits (IEEE division of exact integers); dt_match [sum C] uint8; gt_match [n_rooms];
+ * int_sums [n_rooms, 8] int64 = sum nij^2, sum a^2, sum b^2 (the adjusted Rand score's, finished in wide integers by the host), the points
+ * counted, the non-empty rows, the non-empty columns (label 0 included when it occurs -- what numpy.unique keeps), the EMI's terms and its
+ * chunks; float_sums [n_rooms, 4] float64 = H(true), H(pred), the mutual information before sklearn's clip at 0, and the expected mutual
+ * information (sklearn's entropy, mutual_info_score and _expected_mutual_info_fast.pyx term by term over one lgamma table 0 .. max N), zero
+ * with flags bit 0.  No floating-point atomics: every float64 sum is made of partials whose bounds depend on the room alone, added in a
+ * fixed order, so a room's outputs are the same bits in any batch and from run to run.
+ *
+ * A label outside [0, C_r] or a gt_row outside [0, G_r) is skipped and raises bit 0 of the room's status word (bit 1: an `order` entry
+ * outside [0, G_r)); nothing is written out of bounds, the other rooms are not affected.  lrg_metrics_batch_status copies the words to
+ * host_status_per_room [n_rooms] (host) and synchronises the stream.
+ *
+ * Limits: at most 65536 rooms; sum N, sum G, sum (C_r + 1) and the table cells sum G_r (C_r + 1) each below 2^30; at most 2^24 table cells
+ * per room; the EMI's chunk numbering, sum over the rooms of G_r (C_r + 1) + min(G_r, C_r + 1) N_r / 32 + 1, below 2^31 - 256.  Tables of up
+ * to 8192 cells are counted in LDS, larger ones with global integer atomics (the same bits).
+ * Refused with a code of their own, nothing launched: n_rooms out of range, a NULL host array or a start that does not begin at 0
+ * (LRG_EINVAL - 90), a decreasing start (- 91), an empty room or a room without a GT row (- 92), a negative n_cluster (- 93), a sum past
+ * the limits above (- 94), a NULL among the device pointers / workspace / outputs (- 95), a short or not 256-byte aligned workspace (- 96).
+ * lrg_metrics_batch_workspace_bytes is host-only arithmetic and returns 0 for arguments the call would refuse. */
+size_t lrg_metrics_batch_workspace_bytes(const int32_t *room_start, const int32_t *gt_start, const int32_t *n_cluster,
+                                         int n_rooms);     /* test_region_grow.py:319-355, test_mcpnet.py:146-170 */
+/* test_region_grow.py:319-355, test_mcpnet.py:146-170 */
+int lrg_metrics_batch(const int32_t *labels, const int32_t *gt_row, const int32_t *order, const int32_t *relabel, const int32_t *unmatched_base,
+                      const int32_t *room_start, const int32_t *gt_start, const int32_t *n_cluster, int n_rooms, unsigned flags,
+                      void *workspace, size_t workspace_bytes, int32_t *cluster_label2, double *best_iou, uint8_t *dt_match,
+                      int32_t *gt_match, int64_t *int_sums, double *float_sums, void *stream);
+/* test_region_grow.py:319-355, test_mcpnet.py:146-170: the per-room status words of the last lrg_metrics_batch on this workspace. */
+int lrg_metrics_batch_status(const void *workspace, const int32_t *room_start, const int32_t *gt_start, const int32_t *n_cluster, int n_rooms,
+                             int32_t *host_status_per_room, void *stream);
 
 #ifdef __cplusplus
 }

@@ -11,9 +11,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
-           'lrg_baselines.hip', 'lrg_mcpnet.hip']
+           'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip']
 
-LRG_ABI_VERSION = 12      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 13      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -295,6 +295,9 @@ _SIGS = {
     'lrg_preprocess_batch': (ctypes.c_int, [_fp, ctypes.c_int, _fp, _fp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                             ctypes.c_int, _fp, ctypes.c_size_t, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     'lrg_preprocess_batch_status': (ctypes.c_int, [_fp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp]),
+    'lrg_metrics_batch_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.c_int]),
+    'lrg_metrics_batch': (ctypes.c_int, [_fp] * 5 + [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.c_int, ctypes.c_uint, _fp, ctypes.c_size_t] + [_fp] * 7),
+    'lrg_metrics_batch_status': (ctypes.c_int, [_fp] + [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp]),
 }
 
 EXPORTS = sorted(_SIGS)

@@ -33,6 +33,9 @@ def parse(argv=None):
     ap.add_argument('--seed', type=int, default=0, help='seed of the neighbour draws (legacy: numpy.random.seed, :15)')
     ap.add_argument('--batch-rooms', type=int, default=68, help='rooms per GPU call')
     ap.add_argument('--device', default=None, help='default: cuda:0')
+    ap.add_argument('--metrics', default='host', choices=('host', 'device'),
+                    help="the per-room evaluation (:146-170): 'host' = metrics.room_metrics_set_order room by room; 'device' = all rooms of a "
+                         "batch in one pass on the GPU (metrics_gpu.room_metrics_batch, order='set')")
     return ap.parse_args(argv)
 
 
@@ -66,9 +69,14 @@ def main(argv=None):
             nbrs = mcpnet.neighbors(rooms, rng=args.rng, seed=args.seed, state=state, device=args.device)
             embs = net.embed([r['points'] for r in rooms], nbrs)
             labels = mcpnet.segment(rooms, embs, device=args.device)
+            room_ms = None
+            if args.metrics == 'device':
+                from learn_region_grow_amd import metrics_gpu
+                room_ms = metrics_gpu.room_metrics_batch([obj_ids[r][rooms[j]['equalized_idx']] for j, r in enumerate(batch)],
+                                                         [lab.astype(np.int64) for lab in labels], order='set', device=args.device)
             for j, r in enumerate(batch):
                 lab = labels[j].astype(np.int64)
-                m = metrics.room_metrics_set_order(obj_ids[r][rooms[j]['equalized_idx']], lab)
+                m = room_ms[j] if room_ms is not None else metrics.room_metrics_set_order(obj_ids[r][rooms[j]['equalized_idx']], lab)
                 ms.append(m)
                 print(metrics.room_line(area, r, m))
                 if args.save is not None:

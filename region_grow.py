@@ -89,6 +89,10 @@ def parse(argv=None):
                          "numpy.linalg.svd on the host (features and seed order bit-identical, 4.5 x the rate of 'gpu-lapack'); 'gpu-lapack' = GPU "
                          "gathering and covariances + numpy.linalg.svd for every point (every output bit-identical); 'gpu' = all on the GPU "
                          "(features equal to float32 rounding, seed order up to near-ties); 'host' = vectorised NumPy")
+    ap.add_argument('--metrics', default='host', choices=['host', 'device'],
+                    help="the per-room evaluation (test_region_grow.py:319-355): 'host' = metrics.room_metrics, NumPy and sklearn room by room; "
+                         "'device' = all rooms of the rank in one pass on the GPU (metrics_gpu.room_metrics_batch: same matching outputs bit "
+                         "for bit, ARS equal, NMI / AMI to ~1e-10)")
     args = ap.parse_args(argv)
     if args.beam > 0:
         bad = [o for o, on in (('--rng legacy', args.rng != 'counter'), ('--restarts', args.restarts > 1), ('--lanes', args.lanes > 1),
@@ -284,8 +288,13 @@ def main(argv=None):
         t_grow = time.time() - t0
         # ---- per-room evaluation where the room was grown; lines, metrics and labels to rank 0 ----
         local_out = []
+        if args.metrics == 'device' and my_rooms:
+            from learn_region_grow_amd import metrics_gpu
+            room_ms = metrics_gpu.room_metrics_batch([p['obj_id'] for p in pre], [res.filled_label for res in results], device=device)
+        else:
+            room_ms = [metrics.room_metrics(pre[k]['obj_id'], res.filled_label) for k, res in enumerate(results)]
         for k, (r, res) in enumerate(zip(my_rooms, results)):
-            m = metrics.room_metrics(pre[k]['obj_id'], res.filled_label)
+            m = room_ms[k]
             lines = [] if (args.quiet_regions or args.beam > 0) else region_lines(r, res, pre[k]['obj_id'], pre[k]['cls_id'], classes)
             local_out.append(dict(room=r, lines=lines, metrics={q: m[q] for q in ('nmi', 'ami', 'ars', 'prc', 'rcl', 'iou')},
                                   regions=len(res.regions), steps=res.total_steps, feature_s=t_feat[k],
