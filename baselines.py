@@ -10,8 +10,8 @@ The rooms of a file go to the GPU in batches (--batch-rooms per lrg_baseline_seg
 (device equalisation and covariances, host numpy.linalg.svd: learn_region_grow_amd.baselines.room_features).  The timing line
 of a room is its feature time plus its share, by equalised points, of its batch's segmentation time.  --features verified solves
 the 3x3 decompositions on the GPU too and sends only the points whose labels or rank could depend on the solver through LAPACK: the
-same lines, several times faster in the modes that read normals.  The other modes of
-benchmarks.py (edge, fpfh, pointnet, pointnet2) are not ported.
+same lines, several times faster in the modes that read normals.  Mode pointnet2 of
+benchmarks.py is pointnet2.py; edge, fpfh and pointnet are not ported.
 """
 import argparse
 import os
@@ -56,6 +56,31 @@ def area_file(args, area):
     return os.path.join(args.data_dir, 's3dis_area%s.h5' % area)
 
 
+def room_names(args, area):
+    """The room names of an area (benchmarks.py:186-190), or None."""
+    name_file = args.room_names or os.path.join(args.data_dir, '%s_room_name.txt' % area)
+    if os.path.exists(name_file):
+        return open(name_file).read().split('\n')
+    return None
+
+
+def report_room(args, mode, area, r, names, raw_points, seconds, m, unequalized_idx, save_id):
+    """The lines benchmarks.py prints for a room of any mode (its timing line, then the metric line) and, with --save, the room's
+    PLY coloured by cluster (default dir: data/results/<mode>).  Returns the next save id.  Shared with pointnet2.py."""
+    from learn_region_grow_amd import io, metrics
+    print('%s %d points: %.2fs' % (names[r] if names is not None and r < len(names) else '', len(raw_points), seconds))
+    print(metrics.room_line(area, r, m))
+    if args.save is None:
+        return save_id
+    out_dir = args.save or os.path.join(args.data_dir, 'results', mode)
+    os.makedirs(out_dir, exist_ok=True)
+    pts = np.array(raw_points[:, :6], dtype=np.float64)
+    colors = io.label_colors(int(m['cluster_label2'].max()) + 1)
+    pts[:, 3:6] = colors[m['cluster_label2'], :][unequalized_idx]
+    io.savePLY(os.path.join(out_dir, ('scannet%d.ply' if area == 'scannet' else '%d.ply') % save_id), pts)
+    return save_id + 1
+
+
 def main(argv=None):
     args = parse(argv)
     from learn_region_grow_amd import baselines, io, metrics
@@ -71,10 +96,7 @@ def main(argv=None):
         rooms, obj_ids, _ = io.loadFromH5(area_file(args, area))
         if args.max_rooms:
             rooms = rooms[:args.max_rooms]
-        names = None
-        name_file = args.room_names or os.path.join(args.data_dir, '%s_room_name.txt' % area)
-        if os.path.exists(name_file):
-            names = open(name_file).read().split('\n')
+        names = room_names(args, area)
         for b0 in range(0, len(rooms), max(1, args.batch_rooms)):
             batch = range(b0, min(len(rooms), b0 + max(1, args.batch_rooms)))
             feats, ftime = [], []
@@ -94,19 +116,10 @@ def main(argv=None):
                                                          [lab.astype(np.int64) for lab in labels], device=args.device)
             for j, r in enumerate(batch):
                 f, lab = feats[j], labels[j].astype(np.int64)
-                print('%s %d points: %.2fs' % (names[r] if names is not None and r < len(names) else '', len(rooms[r]),
-                                               ftime[j] + seg * len(f['points']) / total))
                 m = room_ms[j] if room_ms is not None else metrics.room_metrics(obj_ids[r][f['equalized_idx']], lab)
                 ms.append(m)
-                print(metrics.room_line(area, r, m))
-                if args.save is not None:
-                    out_dir = args.save or os.path.join(args.data_dir, 'results', args.mode)
-                    os.makedirs(out_dir, exist_ok=True)
-                    pts = np.array(rooms[r][:, :6], dtype=np.float64)
-                    colors = io.label_colors(int(m['cluster_label2'].max()) + 1)
-                    pts[:, 3:6] = colors[m['cluster_label2'], :][f['unequalized_idx']]
-                    io.savePLY(os.path.join(out_dir, ('scannet%d.ply' if area == 'scannet' else '%d.ply') % save_id), pts)
-                    save_id += 1
+                save_id = report_room(args, args.mode, area, r, names, rooms[r], ftime[j] + seg * len(f['points']) / total, m,
+                                      f['unequalized_idx'], save_id)
     if ms:
         print(metrics.aggregate_line(ms))
     return 0

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 13
+#define LRG_ABI_VERSION 14
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -729,6 +729,37 @@ int lrg_baseline_certify(const float *pts, int ld, const int32_t *room_start, in
 int lrg_baseline_segment_embedding(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const float *emb,
                                    int dim, double t, int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels,
                                    int32_t *n_clusters, void *stream);
+/* The edges of benchmarks.py:300-306 (modes pointnet / pointnet2): cls[k] == cls[i] on the 26-neighbour voxel graph, cls [n] int32 on
+ * the device (any values: a class count is not needed).  Components of more than min_cluster_size points are numbered in networkx's
+ * order (:405-416), as lrg_baseline_segment_embedding does; same workspace (lrg_baseline_workspace_bytes), same lrg_baseline_status. */
+int lrg_baseline_segment_labels(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const int32_t *cls,
+                                int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * PointNet2's shared MLPs (train_pointnet.py:126-167, :193-202; the caller is benchmarks.py:281-298).  fp32 on
+ * v_mfma_f32_32x32x2_f32; a tile of 32 rows stays on its CU from the first layer to the last (csrc/lrg_pointnet2.hip).  An output
+ * value depends on its own row or group only: not on the launch's size nor on what else is in it.
+ * ---------------------------------------------------------------------------------------------- */
+/* Floats of one packed layer of k inputs and n outputs (1 <= k <= 1024, 1 <= n <= 512; 0 otherwise): both rounded up to a multiple of 32,
+ * then the bias.  A multiple of 32 floats, so the layers of one MLP follow each other in one 16-byte aligned buffer. */
+size_t lrg_pointnet2_packed_floats(int k, int n);
+/* One 1x1 convolution (:133-136, :161-164, :194-202): w [k, n] row-major (the TF kernel [1,1,k,n] or [1,k,n]) and bias [n] on the device
+ * -> packed [lrg_pointnet2_packed_floats(k, n)] in the MFMA operand order, zero where padded.  The packed image of an MLP is its layers'
+ * images one after the other. */
+int lrg_pointnet2_pack_layer(int k, int n, const float *w, const float *bias, float *packed, void *stream);
+/* A set-abstraction level after its ball query (pointnet_sa_module, :126-140, with the grouping of sample_and_group :116-122): for every
+ * group g of batch element bi, the 32 rows concat(xyz[bi][idx[g][s]] - new_xyz[g], points[bi][idx[g][s]]) (float32 subtraction; never
+ * written to memory), three layers relu(x W + bias) of widths[0..2] (HOST memory; each a multiple of 32, at most 512), then the
+ * maximum over the 32 rows: out [b, m, widths[2]].  xyz [b,n,3], new_xyz [b,m,3], points [b,n,c] (NULL with c == 0; 3 + c <= 1024),
+ * idx [b,m,32] int32 (an index outside [0, n) reads row 0).  nsample must be 32: one MFMA row tile is one group. */
+int lrg_pointnet2_group_mlp(int b, int n, int m, int nsample, int c, const float *xyz, const float *new_xyz, const float *points,
+                            const int32_t *idx, const int32_t *widths, const float *packed, float *out, void *stream);
+/* The layers of pointnet_fp_module after its interpolation (:152-166) and the head (:193-202): rows concat(a[i], b[i]) (a [r, ca],
+ * b [r, cb], NULL with cb == 0; ca + cb <= 1024; the concat of :153 is never written), n_layers (1 .. 3) layers x W + bias of
+ * widths[0 .. n_layers-1] (HOST memory; at most 512; all but the last a multiple of 32, the last any value from 1), ReLU after each
+ * layer except that relu_last == 0 leaves it off the last: out [r, widths[n_layers-1]].  r >= 0. */
+int lrg_pointnet2_row_mlp(long r, int ca, int cb, const float *a, const float *b, int n_layers, const int32_t *widths, int relu_last,
+                          const float *packed, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * MCPNet (test_mcpnet.py:71-120, learn_region_grow_util.py:191-225): candidate lists on 0.3 m cells, 50 neighbour rows per point,

@@ -442,3 +442,72 @@ def load_mcpnet_weights(prefix, verify=True):
         if entries[name].dtype != 1:
             raise BundleError('%s: not float32' % name)
     return load_bundle(prefix, names=list(MCPNET_SHAPES), verify=verify)
+
+
+POINTNET2_SA_MLPS = ((32, 32, 64), (64, 64, 128), (128, 128, 256), (256, 256, 512))     # train_pointnet.py:181-184
+POINTNET2_FP_MLPS = ((256, 256), (256, 256), (256, 128), (128, 128, 128))               # :187-190
+
+
+def pointnet2_variable_shapes(num_class=13, rgb_features=False):
+    """name -> TF shape of PointNet2's 46 trainables (train_pointnet.py:133-134, :161-162, :194-200).  rgb_features: l0_points is
+    the colour (:178; 6 and 131 input channels at layer1 and fa_layer4) instead of None (:177, the shipped models: 3 and 128)."""
+    c0 = 3 if rgb_features else 0
+    shapes = {}
+    feat = [c0] + [m[-1] for m in POINTNET2_SA_MLPS]                  # l0 .. l4 feature widths
+    for lv, mlp in enumerate(POINTNET2_SA_MLPS):
+        cin = 3 + feat[lv]
+        for i, c in enumerate(mlp):
+            shapes['layer%d/kernel%d' % (lv + 1, i)] = (1, 1, cin, c)
+            shapes['layer%d/bias%d' % (lv + 1, i)] = (c,)
+            cin = c
+    up = feat[4]                                                      # the interpolated width, then the skip's
+    for lv, mlp in enumerate(POINTNET2_FP_MLPS):
+        cin = up + feat[3 - lv]
+        for i, c in enumerate(mlp):
+            shapes['fa_layer%d/kernel%d' % (lv + 1, i)] = (1, 1, cin, c)
+            shapes['fa_layer%d/bias%d' % (lv + 1, i)] = (c,)
+            cin = c
+        up = mlp[-1]
+    shapes['kernel1'] = (1, 128, 128)
+    shapes['bias1'] = (128,)
+    shapes['kernel2'] = (1, 128, int(num_class))
+    shapes['bias2'] = (int(num_class),)
+    return shapes
+
+
+def pointnet2_variant(shape_of):
+    """(num_class, rgb_features) from a name -> shape mapping: the variant is read from the input channels of layer1/kernel0 (3 or
+    6) and fa_layer4/kernel0 (128 or 131), which must agree; the class count is the last dimension of kernel2."""
+    for name in ('layer1/kernel0', 'fa_layer4/kernel0', 'kernel2'):
+        if name not in shape_of:
+            raise BundleError('variable %s missing (not a PointNet2 checkpoint?)' % name)
+    k0, k4, k2 = (tuple(shape_of[n]) for n in ('layer1/kernel0', 'fa_layer4/kernel0', 'kernel2'))
+    if len(k0) != 4 or k0[2] not in (3, 6):
+        raise BundleError('layer1/kernel0: shape %s has neither 3 (xyz) nor 6 (xyz and colour) input channels' % (k0,))
+    if len(k4) != 4 or k4[2] not in (128, 131):
+        raise BundleError('fa_layer4/kernel0: shape %s has neither 128 nor 131 input channels' % (k4,))
+    if (k0[2] == 6) != (k4[2] == 131):
+        raise BundleError('layer1/kernel0 %s and fa_layer4/kernel0 %s disagree about the colour features' % (k0, k4))
+    if len(k2) != 3 or k2[2] < 1:
+        raise BundleError('kernel2: shape %s is not (1, 128, num_class)' % (k2,))
+    return int(k2[2]), k0[2] == 6
+
+
+def load_pointnet2_weights(prefix, verify=True):
+    """The 46 trainables of a PointNet2 checkpoint (``Variable`` and the Adam slots ignored) -- what ``saver.restore`` assigns at
+    benchmarks.py:172.  The variant and the class count come from the checkpoint itself (pointnet2_variant); every shape and dtype
+    is checked, every tensor's bytes against its CRC-32C.  A missing or mis-shaped variable raises BundleError naming it."""
+    _, entries = read_bundle_index(prefix, verify=verify)
+    try:
+        num_class, rgb = pointnet2_variant({n: e.shape for n, e in entries.items()})
+    except BundleError as e:
+        raise BundleError('%s: %s' % (prefix, e))
+    shapes = pointnet2_variable_shapes(num_class, rgb)
+    for name, shp in shapes.items():
+        if name not in entries:
+            raise BundleError('%s: variable %s missing (not a PointNet2 checkpoint?)' % (prefix, name))
+        if tuple(entries[name].shape) != tuple(shp):
+            raise BundleError('%s: checkpoint has shape %s, PointNet2 needs %s' % (name, tuple(entries[name].shape), shp))
+        if entries[name].dtype != 1:
+            raise BundleError('%s: not float32' % name)
+    return load_bundle(prefix, names=list(shapes), verify=verify)

@@ -31,7 +31,7 @@
 #define BL_THREADS 256
 #define BL_SCAN_ITEMS 8                       // per thread: 2048 elements per block
 
-enum { BL_NORMAL = 0, BL_CURVATURE = 1, BL_COLOR = 2, BL_FEATURE = 3, BL_SMOOTHNESS = 4, BL_EMBEDDING = 5 };   // 5: lrg_baseline_segment_embedding only
+enum { BL_NORMAL = 0, BL_CURVATURE = 1, BL_COLOR = 2, BL_FEATURE = 3, BL_SMOOTHNESS = 4, BL_EMBEDDING = 5, BL_LABELS = 6 };   // 5: lrg_baseline_segment_embedding only, 6: lrg_baseline_segment_labels only
 // status bits (lrg_baseline_status)
 enum { BL_ST_WINDOW = 1, BL_ST_DUPLICATE = 2, BL_ST_RANK = 4, BL_ST_STACK = 8 };
 
@@ -78,6 +78,7 @@ struct BlArgs {
     float res; int mode;
     const double *normals, *curv; const int32_t *rank;
     const float *emb; int dim;
+    const int32_t *cls;
     double t1, t2, t3; int mcs;
     uint64_t *keys; int32_t *vals, *room_of, *parent, *size; unsigned long long *minkey;
     int32_t *ckey, *visited, *flag, *scan, *bsum, *stack, *scal;
@@ -137,6 +138,7 @@ __device__ __forceinline__ bool bl_edge(const BlArgs &a, int i, int k) {
     case BL_CURVATURE: return bl_curv_edge(a.curv, i, k, a.t1);
     case BL_COLOR: return bl_color_edge(a.pts, a.ld, i, k, (float)a.t1);
     case BL_EMBEDDING: return bl_embedding_edge(a.emb, a.dim, i, k, a.t1);
+    case BL_LABELS: return a.cls[k] == a.cls[i];             // class_labels[voxel_map[kk]] == class_labels[i] (benchmarks.py:305)
     default:
         return bl_normal_edge(a.normals, i, k, a.t1) && bl_curv_edge(a.curv, i, k, a.t2) &&
                bl_color_edge(a.pts, a.ld, i, k, (float)a.t3);
@@ -477,7 +479,7 @@ size_t lrg_baseline_workspace_bytes(int n_points, int n_rooms, int min_cluster_s
 // The checks and the argument block that lrg_baseline_segment, lrg_baseline_segment_embedding and lrg_baseline_certify share
 // (room_start is copied to the workspace on the stream)
 static int bl_setup(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode, const double *normals,
-                    const double *curvatures, const int32_t *rank, const float *emb, int dim, double t1, double t2, double t3,
+                    const double *curvatures, const int32_t *rank, const float *emb, int dim, const int32_t *cls, double t1, double t2, double t3,
                     int min_cluster_size, void *ws, size_t ws_bytes, bool need_rank, bool have_outputs, hipStream_t st, LrgBaselineLayout *Lout, BlArgs *out) {
     LrgBaselineLayout &L = *Lout;
     if (n_rooms < 1 || n_rooms > (1 << 20) || !room_start || room_start[0] != 0) return LRG_EINVAL - 73;
@@ -486,8 +488,9 @@ static int bl_setup(const float *pts, int ld, const int32_t *room_start, int n_r
     const int n_points = room_start[n_rooms];
     int rc = bl_layout(n_points, n_rooms, min_cluster_size, &L);
     if (rc) return rc;
-    if (mode < BL_NORMAL || mode > BL_EMBEDDING) return LRG_EINVAL - 72;
+    if (mode < BL_NORMAL || mode > BL_LABELS) return LRG_EINVAL - 72;
     if (mode == BL_EMBEDDING && (!emb || dim < 1 || dim > 64)) return LRG_EINVAL - 74;
+    if (mode == BL_LABELS && !cls && n_points > 0) return LRG_EINVAL - 74;
     if (!ws || !have_outputs) return LRG_EINVAL - 73;
     if (n_points > 0 && (!pts || ld < 6)) return LRG_EINVAL - 73;
     const bool need_n = mode == BL_NORMAL || mode == BL_FEATURE || mode == BL_SMOOTHNESS;
@@ -500,7 +503,7 @@ static int bl_setup(const float *pts, int ld, const int32_t *room_start, int n_r
     int32_t *rooms = reinterpret_cast<int32_t *>(w + L.rooms);     // a device copy of room_start (the caller's is host memory)
     LRG_HIP_CHECK(hipMemcpyAsync(rooms, room_start, (size_t)(n_rooms + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
     a.pts = pts; a.ld = ld; a.room_start = rooms; a.n_rooms = n_rooms; a.n = n_points; a.res = resolution; a.mode = mode;
-    a.normals = normals; a.curv = curvatures; a.rank = rank; a.emb = emb; a.dim = dim; a.t1 = t1; a.t2 = t2; a.t3 = t3; a.mcs = min_cluster_size;
+    a.normals = normals; a.curv = curvatures; a.rank = rank; a.emb = emb; a.dim = dim; a.cls = cls; a.t1 = t1; a.t2 = t2; a.t3 = t3; a.mcs = min_cluster_size;
     a.keys = reinterpret_cast<uint64_t *>(w + L.keys); a.vals = reinterpret_cast<int32_t *>(w + L.vals);
     a.room_of = reinterpret_cast<int32_t *>(w + L.room_of); a.parent = reinterpret_cast<int32_t *>(w + L.parent);
     a.size = reinterpret_cast<int32_t *>(w + L.size); a.minkey = reinterpret_cast<unsigned long long *>(w + L.minkey);
@@ -521,13 +524,13 @@ static inline int bl_init_grid(const LrgBaselineLayout &L, int n_points) {
 
 // lrg_baseline_segment and lrg_baseline_segment_embedding: the same checks and the same nine launches
 static int bl_segment_impl(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode,
-                           const double *normals, const double *curvatures, const int32_t *rank, const float *emb, int dim, double t1,
+                           const double *normals, const double *curvatures, const int32_t *rank, const float *emb, int dim, const int32_t *cls, double t1,
                            double t2, double t3, int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters,
                            void *stream) {
     LrgBaselineLayout L;
     BlArgs a;
     hipStream_t st = (hipStream_t)stream;
-    int rc = bl_setup(pts, ld, room_start, n_rooms, resolution, mode, normals, curvatures, rank, emb, dim, t1, t2, t3, min_cluster_size, ws,
+    int rc = bl_setup(pts, ld, room_start, n_rooms, resolution, mode, normals, curvatures, rank, emb, dim, cls, t1, t2, t3, min_cluster_size, ws,
                       ws_bytes, true, labels && n_clusters, st, &L, &a);
     if (rc) return rc;
     const int n_points = a.n;
@@ -555,14 +558,20 @@ extern "C" {
 int lrg_baseline_segment(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode,
                          const double *normals, const double *curvatures, const int32_t *rank, double t1, double t2, double t3,
                          int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream) {
-    return bl_segment_impl(pts, ld, room_start, n_rooms, resolution, mode == BL_EMBEDDING ? -1 : mode, normals, curvatures, rank, nullptr, 0, t1, t2, t3,
+    return bl_segment_impl(pts, ld, room_start, n_rooms, resolution, mode >= BL_EMBEDDING ? -1 : mode, normals, curvatures, rank, nullptr, 0, nullptr, t1, t2, t3,
                            min_cluster_size, ws, ws_bytes, labels, n_clusters, stream);
 }
 
 int lrg_baseline_segment_embedding(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const float *emb,
                                    int dim, double t, int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels,
                                    int32_t *n_clusters, void *stream) {
-    return bl_segment_impl(pts, ld, room_start, n_rooms, resolution, BL_EMBEDDING, nullptr, nullptr, nullptr, emb, dim, t, 0.0, 0.0,
+    return bl_segment_impl(pts, ld, room_start, n_rooms, resolution, BL_EMBEDDING, nullptr, nullptr, nullptr, emb, dim, nullptr, t, 0.0, 0.0,
+                           min_cluster_size, ws, ws_bytes, labels, n_clusters, stream);
+}
+
+int lrg_baseline_segment_labels(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const int32_t *cls,
+                                int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream) {
+    return bl_segment_impl(pts, ld, room_start, n_rooms, resolution, BL_LABELS, nullptr, nullptr, nullptr, nullptr, 0, cls, 0.0, 0.0, 0.0,
                            min_cluster_size, ws, ws_bytes, labels, n_clusters, stream);
 }
 
@@ -582,8 +591,8 @@ int lrg_baseline_certify(const float *pts, int ld, const int32_t *room_start, in
     LrgBaselineLayout L;
     BlArgs a;
     hipStream_t st = (hipStream_t)stream;
-    if (mode == BL_EMBEDDING) return LRG_EINVAL - 72;
-    int rc = bl_setup(pts, ld, room_start, n_rooms, resolution, mode, normals, curvatures, nullptr, nullptr, 0, t1, t2, t3, min_cluster_size,
+    if (mode >= BL_EMBEDDING) return LRG_EINVAL - 72;
+    int rc = bl_setup(pts, ld, room_start, n_rooms, resolution, mode, normals, curvatures, nullptr, nullptr, 0, nullptr, t1, t2, t3, min_cluster_size,
                       ws, ws_bytes, false, flags && n_flagged, st, &L, &a);
     if (rc) return rc;
     const int n_points = a.n;
