@@ -9,6 +9,7 @@ import pytest
 from conftest import seed_without_near_tie
 from learn_region_grow_amd import synthetic
 from oracle import grow_ref, rng_ref
+import placement_rooms
 from test_gpu_grow import WEIGHT_KW, SAME_LOGITS_MARGIN, gpu_net_fn, small_room, same_regions
 
 pytestmark = pytest.mark.gpu
@@ -379,6 +380,7 @@ def test_free_run_preview_agrees_with_load_rooms(net, cuda_device):
     small = _rooms()[:3]
     cases = [(net, small, {}, True), (net, small, dict(restarts=4), False), (net, small, dict(free_run=False), False),
              (net, [_line_room(2047, 1)], {}, True), (net, [_line_room(2048, 1)], {}, False),      # packed voxel words: 2047 voxels across at most
+             (net, [placement_rooms.placed('fits_x')], {}, True), (net, [placement_rooms.placed('wide_x')], {}, False),      # ... of rooms away from the origin
              (lite1, small, {}, False)]
     for nt, rooms, kw, want in cases:
         assert RegionGrower.free_run_applies(nt, rooms, 68, **kw) == want, kw

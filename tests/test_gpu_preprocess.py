@@ -20,10 +20,17 @@ def raw_room(seed, n=2500, wlh=(1.6, 1.3, 1.0)):
     return r[:, :6], r[:, 6].astype(int), r[:, 7].astype(int)
 
 
-@pytest.mark.parametrize('seed,F', [(1, 13), (2, 12), (3, 9), (4, 6)])
-def test_lapack_mode_is_bit_exact(cuda_device, seed, F):
+@pytest.mark.parametrize('seed,F,offset', [pytest.param(1, 13, None, id='1-13'), pytest.param(2, 12, None, id='2-12'), pytest.param(3, 9, None, id='3-9'),
+                                           pytest.param(4, 6, None, id='4-6'), pytest.param(1, 13, (-37.3, -12.9, -3.1), id='1-13-negative'),
+                                           pytest.param(2, 12, (163.7, -204.1, 2.0), id='2-12-far')])
+def test_lapack_mode_is_bit_exact(cuda_device, seed, F, offset):
+    """offset: the raw room moved into building coordinates (a float32 offset added to xyz in float32, before either side sees it)."""
     from learn_region_grow_amd import preprocess_gpu
     raw, obj, cls = raw_room(seed)
+    if offset is not None:
+        raw = raw.copy()
+        raw[:, :3] = (raw[:, :3] + np.asarray(offset, dtype=np.float32)).astype(np.float32)
+        assert raw.dtype == np.float32
     want = preprocess_ref.preprocess_room(raw, obj, cls, feature_size=F)
     got = preprocess_gpu.preprocess_room(raw, obj, cls, feature_size=F, eig='lapack', device=cuda_device)
     np.testing.assert_array_equal(got['equalized_idx'], want['equalized_idx'])
