@@ -396,8 +396,8 @@ int lrg_forward_packed(const LrgWeights *w, const float *x_in, const float *x_nb
 /* Device buffers of one packed iteration over n_slots slots (all caller-owned; counters zero before the first call). */
 typedef struct LrgPackedBuffers {
     float *center;          /* [n_slots,16]                                                                  */
-    int32_t *sample_in;     /* [n_slots,n_inlier]   sample positions (:237-240)                              */
-    int32_t *sample_nb;     /* [n_slots,n_neighbor] (:249-252)                                               */
+    int32_t *sample_in;     /* [n_slots,n_inlier]   sample positions (:237-240); written by lrg_front_kernel only: the greedy */
+    int32_t *sample_nb;     /* [n_slots,n_neighbor] (:249-252)   front kernels draw them again in their mask update          */
     float *x_in;            /* [row_cap,F] packed distinct inlier rows of all slots (:245-247)               */
     float *x_nb;            /* [row_cap,F] packed distinct neighbour rows (:243-244,:253)                    */
     int32_t *row_slot_in;   /* [row_cap] slot of each packed row                                             */
