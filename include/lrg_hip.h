@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 14
+#define LRG_ABI_VERSION 15
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -760,6 +760,30 @@ int lrg_pointnet2_group_mlp(int b, int n, int m, int nsample, int c, const float
  * layer except that relu_last == 0 leaves it off the last: out [r, widths[n_layers-1]].  r >= 0. */
 int lrg_pointnet2_row_mlp(long r, int ca, int cb, const float *a, const float *b, int n_layers, const int32_t *widths, int relu_last,
                           const float *packed, float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The plain PointNet of benchmarks.py --mode pointnet (train_pointnet.py:31-99) at inference (ABI 15; csrc/lrg_pointnet.hip).  A cell
+ * is 1024 rows.  fp32 on v_mfma_f32_32x32x2_f32; a tile of 32 rows stays on its CU through the conv stack, and again through the fc
+ * stack.  A cell's values depend on that cell only: not on the launch's size nor on what else is in it.  No entry point allocates.
+ * ---------------------------------------------------------------------------------------------- */
+/* lrg_pointnet2_packed_floats / lrg_pointnet2_pack_layer with the caps 1 <= k <= 2048, 1 <= n <= 1024 (the same image). */
+size_t lrg_pointnet_packed_floats(int k, int n);
+int lrg_pointnet_pack_layer(int k, int n, const float *w, const float *bias, float *packed, void *stream);
+/* :49-56.  x [cells,1024,6] through n_conv (2 .. 5) layers relu(x W + bias) of widths[0 .. n_conv-1] (HOST memory; each a multiple of
+ * 32, at most 1024); packed: the layers' images one after the other, the first with k = 6.  skip [cells,1024,widths[1]] receives
+ * conv[1], last [cells,1024,widths[n_conv-1]] the last layer's rows (NULL: not written), pooled [cells,widths[n_conv-1]] the column
+ * maximum over ALL 1024 rows of the cell (an integer maximum on the bits of the non-negative values: the same bits in any order; the
+ * entry point zeroes pooled on the stream first).  cells >= 0. */
+int lrg_pointnet_features(int cells, int n_conv, const int32_t *widths, const float *x, const float *packed, float *skip, float *last,
+                          float *pooled, void *stream);
+/* :57-99.  Rows concat(last[p] - pooled[cell] (float32), skip[p]) (never written; c_last, c_skip multiples of 32 up to 1024, their
+ * sum at most 1248), n_fc (2 .. 3) layers of widths[0 .. n_fc-1] (HOST memory): the hidden ones (multiples of 32 up to 512) are
+ * relu((x W + bias) * scale[p][c] + shift[p][c]) with p = 0 .. 1023 the row's position in its cell, the last (1 .. 1024 classes) is
+ * x W + bias: out [cells,1024,widths[n_fc-1]].  bn: for every hidden layer j in turn scale [1024, widths[j]] then shift
+ * [1024, widths[j]], the batch norm of :63-84 folded as tf.nn.batch_normalization does (scale = rsqrt(var + 1e-3) * gamma,
+ * shift = beta - mean * scale). */
+int lrg_pointnet_head(int cells, int c_last, int c_skip, const float *last, const float *skip, const float *pooled, int n_fc,
+                      const int32_t *widths, const float *packed, const float *bn, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * MCPNet (test_mcpnet.py:71-120, learn_region_grow_util.py:191-225): candidate lists on 0.3 m cells, 50 neighbour rows per point,

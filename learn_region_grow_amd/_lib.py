@@ -11,9 +11,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
-           'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip']
+           'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip']
 
-LRG_ABI_VERSION = 14      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 15      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -279,6 +279,10 @@ _SIGS = {
     'lrg_pointnet2_group_mlp': (ctypes.c_int, [ctypes.c_int] * 5 + [_fp, _fp, _fp, _fp, ctypes.POINTER(ctypes.c_int32), _fp, _fp, _fp]),
     'lrg_pointnet2_row_mlp': (ctypes.c_int, [ctypes.c_long, ctypes.c_int, ctypes.c_int, _fp, _fp, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                              ctypes.c_int, _fp, _fp, _fp]),
+    'lrg_pointnet_packed_floats': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    'lrg_pointnet_pack_layer': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp]),
+    'lrg_pointnet_features': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp, _fp, _fp, _fp, _fp, _fp]),
+    'lrg_pointnet_head': (ctypes.c_int, [ctypes.c_int] * 3 + [_fp, _fp, _fp, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp, _fp, _fp, _fp]),
     'lrg_mcp_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     'lrg_mcp_candidates': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, _fp, ctypes.c_size_t, _fp, _fp]),
     'lrg_mcp_neighbors': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, _fp, ctypes.c_size_t, _fp, ctypes.c_uint32, _fp, _fp, _fp]),

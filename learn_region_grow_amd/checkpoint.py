@@ -511,3 +511,129 @@ def load_pointnet2_weights(prefix, verify=True):
         if entries[name].dtype != 1:
             raise BundleError('%s: not float32' % name)
     return load_bundle(prefix, names=list(shapes), verify=verify)
+
+
+POINTNET_NUM_POINT = 1024                                            # the row positions of a cell: the batch-norm tables' first axis
+_POINTNET_MEAN = 'moments/Squeeze/ExponentialMovingAverage'
+_POINTNET_VARIANCE = 'moments/Squeeze_1/ExponentialMovingAverage'
+
+
+def pointnet_bn_names(j):
+    """(beta, gamma, moving mean, moving variance) of the batch norm after hidden fc layer j (train_pointnet.py:63-84, :92).
+
+    Block 0's names are those of the shipped models/pointnet_model5.ckpt.index.  A second block exists only in the network that
+    train_pointnet.py builds today (NUM_FC_CHANNELS = [512, 256]), of which no checkpoint ships, so its names are INFERRED from
+    TF 1's scoping rules and not pinned by a reference-made file: the re-entered ``variable_scope('bn')`` keeps the variable scope
+    'bn' but opens the name scope 'bn_1', which names the ``tf.Variable``s ('bn_1/beta', 'bn_1/gamma') and the moments ops
+    ('bn_1/moments/Squeeze'), and the moving averages take the variable scope in front of the op's name.  The loader therefore
+    accepts for j >= 1 ANY entry that ends in the moments suffix and contains 'bn_<j>/' (load_pointnet_weights)."""
+    scope = 'bn' if j == 0 else 'bn_%d' % j
+    return ('%s/beta' % scope, '%s/gamma' % scope, 'bn/%s/%s' % (scope, _POINTNET_MEAN), 'bn/%s/%s' % (scope, _POINTNET_VARIANCE))
+
+
+def pointnet_variable_shapes(conv_widths=(64, 64, 128, 512), fc_widths=(512,), num_class=13):
+    """name -> TF shape of PointNet's trainables and batch-norm moving averages (train_pointnet.py:50-51, :66-71, :88-89, :96-97):
+    conv_widths the 1x1 convolutions (the first reads the six input channels as a [1, 6] window), fc_widths the HIDDEN fc layers,
+    each followed by a batch norm over the batch axis whose moving averages are [1024, c] tables, then fc_weights<len(fc_widths)>
+    onto num_class.  The defaults are the shipped checkpoint; today's source builds ((64, 64, 64, 128, 1024), (512, 256)).  The
+    names of the second batch-norm block are inferred, not pinned by a reference-made file: pointnet_bn_names."""
+    conv, fc = tuple(int(c) for c in conv_widths), tuple(int(c) for c in fc_widths)
+    shapes = {}
+    for i, c in enumerate(conv):
+        shapes['kernel%d' % i] = (1, 6, 1, c) if i == 0 else (1, 1, conv[i - 1], c)
+        shapes['bias%d' % i] = (c,)
+    k = conv[-1] + conv[1]                                            # the pooled-row difference joined with conv[1] (:59-61)
+    for j, c in enumerate(fc + (int(num_class),)):
+        shapes['fc_weights%d' % j] = (1, k, c)
+        shapes['fc_bias%d' % j] = (c,)
+        if j < len(fc):
+            beta, gamma, mean, variance = pointnet_bn_names(j)
+            shapes[beta] = shapes[gamma] = (c,)
+            shapes[mean] = shapes[variance] = (POINTNET_NUM_POINT, c)
+        k = c
+    return shapes
+
+
+def pointnet_variant(shape_of):
+    """(conv_widths, fc_widths, num_class) from a name -> shape mapping.  The shipped checkpoint is not the network that
+    train_pointnet.py builds today, so the architecture is read from the shapes: kernel0 (1, 6, 1, c0), then kernel<i>
+    (1, 1, c_{i-1}, c_i) for as long as they exist (2 .. 5 layers), fc_weights<j> (1, k, n) for as long as they exist (2 .. 3; the
+    last one's n is the class count, the others are fc_widths).  fc_weights0's k must be conv[-1] + conv[1] (the skip is conv[1],
+    :60).  Every conv and hidden fc width is a multiple of 32; conv widths are at most 1024, hidden fc widths at most 512 (the
+    kernels' limits).  BundleError names the offending variable."""
+    def count(fmt):
+        n = 0
+        while fmt % n in shape_of:
+            n += 1
+        return n
+    nk, nf = count('kernel%d'), count('fc_weights%d')
+    if nk < 2:
+        raise BundleError('variable kernel%d missing (not a PointNet checkpoint?)' % nk)
+    if nk > 5:
+        raise BundleError('kernel5: more than 5 convolutions')
+    if nf < 2:
+        raise BundleError('variable fc_weights%d missing (not a PointNet checkpoint?)' % nf)
+    if nf > 3:
+        raise BundleError('fc_weights3: more than 3 fc layers')
+    conv = []
+    for i in range(nk):
+        s = tuple(shape_of['kernel%d' % i])
+        want = (1, 6, 1) if i == 0 else (1, 1, conv[-1])
+        if len(s) != 4 or s[:3] != want:
+            raise BundleError('kernel%d: shape %s is not %s' % (i, s, want + ('c',)))
+        if s[3] < 32 or s[3] % 32 or s[3] > 1024:
+            raise BundleError('kernel%d: width %d is not a multiple of 32 in [32, 1024]' % (i, s[3]))
+        conv.append(int(s[3]))
+    widths = []
+    k = conv[-1] + conv[1]
+    for j in range(nf):
+        s = tuple(shape_of['fc_weights%d' % j])
+        if len(s) != 3 or s[:2] != (1, k):
+            raise BundleError('fc_weights%d: shape %s is not (1, %d, n)%s' % (j, s, k, ' with %d = conv[-1] + conv[1]' % k if j == 0 else ''))
+        if j < nf - 1 and (s[2] < 32 or s[2] % 32 or s[2] > 512):
+            raise BundleError('fc_weights%d: width %d is not a multiple of 32 in [32, 512]' % (j, s[2]))
+        if j == nf - 1 and not 1 <= s[2] <= 1024:
+            raise BundleError('fc_weights%d: %d classes (1 .. 1024)' % (j, s[2]))
+        widths.append(int(s[2]))
+        k = s[2]
+    return tuple(conv), tuple(widths[:-1]), widths[-1]
+
+
+def _pointnet_entry_name(name, shp, shape_of):
+    """The checkpoint's name for this repository's `name`: itself, or for a moving average of batch-norm block j >= 1 the unique
+    entry of its shape that ends in the moments suffix and contains 'bn_<j>/'."""
+    if name in shape_of:
+        return name
+    for suffix in (_POINTNET_MEAN, _POINTNET_VARIANCE):
+        if name.endswith('/' + suffix) and not name.startswith('bn/bn/'):
+            scope = name[len('bn/'):-len(suffix)]                     # 'bn_<j>/'
+            named = [n for n in shape_of if n.endswith('/' + suffix) and scope in n]
+            hits = [n for n in named if tuple(shape_of[n]) == tuple(shp)]
+            if len(hits) == 1:
+                return hits[0]
+            if named and not hits:
+                raise BundleError('%s: checkpoint has shape %s, PointNet needs %s' % (named[0], tuple(shape_of[named[0]]), tuple(shp)))
+            if hits:
+                raise BundleError('%s: %d entries match (%s)' % (name, len(hits), ', '.join(sorted(hits))))
+    raise BundleError('variable %s missing (not a PointNet checkpoint?)' % name)
+
+
+def load_pointnet_weights(prefix, verify=True):
+    """PointNet's trainables and batch-norm moving averages (``Variable``, ``beta*_power`` and the Adam slots ignored) under this
+    repository's names (pointnet_variable_shapes) -- what ``saver.restore`` assigns at benchmarks.py:172.  The architecture comes
+    from the checkpoint itself (pointnet_variant); every shape and dtype is checked, every tensor's bytes against its CRC-32C.  A
+    missing or mis-shaped variable raises BundleError naming it."""
+    _, entries = read_bundle_index(prefix, verify=verify)
+    shape_of = {n: tuple(e.shape) for n, e in entries.items()}
+    try:
+        shapes = pointnet_variable_shapes(*pointnet_variant(shape_of))
+        found = {name: _pointnet_entry_name(name, shp, shape_of) for name, shp in shapes.items()}
+    except BundleError as e:
+        raise BundleError('%s: %s' % (prefix, e))
+    for name, shp in shapes.items():
+        if shape_of[found[name]] != tuple(shp):
+            raise BundleError('%s: %s: checkpoint has shape %s, PointNet needs %s' % (prefix, found[name], shape_of[found[name]], shp))
+        if entries[found[name]].dtype != 1:
+            raise BundleError('%s: %s: not float32' % (prefix, found[name]))
+    loaded = load_bundle(prefix, names=sorted(set(found.values())), verify=verify)
+    return {name: loaded[found[name]] for name in shapes}

@@ -19,6 +19,7 @@
 // LDS: 32 * (max width + 4) * 4 bytes, dynamic: 131.6 KB for the widest legal input (1024), 16.9 KB for a 128-wide level, so the
 // narrow levels keep several workgroups on a CU.
 #include "lrg_common.h"
+#include "lrg_mlp_pack.h"
 
 #define PN2_THREADS 256
 #define PN2_ROWS 32
@@ -42,7 +43,7 @@ struct Pn2Args {
     const float *packed; float *out;
 };
 
-static inline int pn2_up32(int v) { return (v + 31) & ~31; }
+static inline int pn2_up32(int v) { return lrg_mlp_up32(v); }
 
 template <bool GROUPED>
 __global__ __launch_bounds__(PN2_THREADS) void pn2_mlp_kernel(Pn2Args a) {
@@ -166,26 +167,7 @@ __global__ __launch_bounds__(PN2_THREADS) void pn2_mlp_kernel(Pn2Args a) {
     }
 }
 
-// packed layer: [npad / 32 tiles][kpad / 8 groups][64 lanes] float4, then bias [npad].  Component q of lane l of group g of tile t is
-// W[8 g + 4 (l >> 5) + q][32 t + (l & 31)] (zero outside [k, n)): the k-step the lane's half feeds to the q-th MFMA of the group.
-__global__ __launch_bounds__(PN2_THREADS) void pn2_pack_kernel(const float *w, const float *bias, int k, int n, int kpad, int npad, float *out) {
-    const long x = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long nw = (long)kpad * npad;
-    if (x >= nw + npad) return;
-    float v = 0.f;
-    if (x < nw) {
-        const int q = (int)(x & 3), l = (int)((x >> 2) & 63);
-        const long gt = x >> 8;
-        const int G = kpad >> 3, g = (int)(gt % G), t = (int)(gt / G);
-        const int kk = 8 * g + 4 * (l >> 5) + q, col = 32 * t + (l & 31);
-        if (kk < k && col < n) v = w[(long)kk * n + col];
-    } else {
-        const int col = (int)(x - nw);
-        if (col < n) v = bias[col];
-    }
-    out[x] = v;
-}
-
+// The packed layer image and its kernel: lrg_mlp_pack.h (shared with lrg_pointnet.hip).
 static bool pn2_layer_ok(int k, int n) { return k >= 1 && k <= PN2_MAX_IN && n >= 1 && n <= PN2_MAX_WIDTH; }
 
 // widths[0] the input width, widths[1 ..] the layers' outputs.  Fills the layer table of `a`; every hidden width a multiple of 32.
@@ -233,11 +215,7 @@ size_t lrg_pointnet2_packed_floats(int k, int n) {
 int lrg_pointnet2_pack_layer(int k, int n, const float *w, const float *bias, float *packed, void *stream) {
     if (!pn2_layer_ok(k, n)) return LRG_EINVAL - 90;
     if (!w || !bias || !packed || ((uintptr_t)packed & 15)) return LRG_EINVAL - 90;
-    const long total = (long)lrg_pointnet2_packed_floats(k, n);
-    hipLaunchKernelGGL(pn2_pack_kernel, dim3((unsigned)((total + PN2_THREADS - 1) / PN2_THREADS)), dim3(PN2_THREADS), 0, (hipStream_t)stream,
-                       w, bias, k, n, pn2_up32(k), pn2_up32(n), packed);
-    LRG_LAUNCH_CHECK();
-    return 0;
+    return lrg_mlp_pack_launch(k, n, w, bias, packed, (hipStream_t)stream);
 }
 
 int lrg_pointnet2_group_mlp(int b, int n, int m, int nsample, int c, const float *xyz, const float *new_xyz, const float *points,

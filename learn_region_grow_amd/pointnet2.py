@@ -227,39 +227,50 @@ class PointNet2HIP:
     def classify_cells(self, batch):
         """batch [B, 1024, 6] -> int32 [B, 1024]: the argmax of every row's logits on the device, a tie to the lowest class as
         numpy.argmax (benchmarks.py:297)."""
-        batch = np.ascontiguousarray(batch, dtype=np.float32)
-        out = np.empty((len(batch), NUM_POINT), dtype=np.int32)
-        with torch.cuda.device(self.device):
-            classes = torch.arange(self.num_class, dtype=torch.int32, device=self.device)
-            for c0 in range(0, len(batch), CHUNK_CELLS):
-                lg = self._forward(torch.from_numpy(batch[c0:c0 + CHUNK_CELLS]).to(self.device))
-                best = lg.amax(dim=2, keepdim=True)
-                first = torch.where(lg == best, classes, self.num_class).amin(dim=2)         # the lowest index among equal maxima
-                out[c0:c0 + CHUNK_CELLS] = first.to(torch.int32).cpu().numpy()
-        return out
+        return classify_cells(self, batch, CHUNK_CELLS)
 
     def classify(self, rooms, area=None, grid_resolution_m=None):
         """class_labels of every room (benchmarks.py:282-298): rooms are dicts with 'points' (equalised: prepare_room) or [N, >= 6]
         arrays.  The cells of ALL rooms go through the network together.  area picks the cell size as :283 does (or give
         grid_resolution_m).  Returns one int32 array per room."""
-        res = float(grid_resolution_m) if grid_resolution_m is not None else grid_resolution(area)
-        pts = [np.asarray(r['points'] if isinstance(r, dict) else r, dtype=np.float32) for r in rooms]
-        batches, maps = [], []
-        for k, p in enumerate(pts):
-            name = rooms[k].get('room_id', k) if isinstance(rooms[k], dict) else k
-            batch, members, _ = cell_inputs(p, res, room=name)
-            batches.append(batch)
-            maps.append(members)
-        out = [np.zeros(len(p), dtype=np.int32) for p in pts]
-        if not batches or sum(len(b) for b in batches) == 0:
-            return out
-        cls = self.classify_cells(np.concatenate(batches))
-        c = 0
-        for k, members in enumerate(maps):
-            for idx in members:
-                out[k][idx] = cls[c, :len(idx)]
-                c += 1
+        return classify_rooms(self, rooms, area, grid_resolution_m)
+
+
+def classify_cells(net, batch, chunk_cells):
+    """PointNet2HIP.classify_cells and PointNetHIP.classify_cells: net._forward(x) -> logits [b, 1024, net.num_class] on
+    net.device, chunk_cells cells at a time."""
+    batch = np.ascontiguousarray(batch, dtype=np.float32)
+    out = np.empty((len(batch), NUM_POINT), dtype=np.int32)
+    with torch.cuda.device(net.device):
+        classes = torch.arange(net.num_class, dtype=torch.int32, device=net.device)
+        for c0 in range(0, len(batch), chunk_cells):
+            lg = net._forward(torch.from_numpy(batch[c0:c0 + chunk_cells]).to(net.device))
+            best = lg.amax(dim=2, keepdim=True)
+            first = torch.where(lg == best, classes, net.num_class).amin(dim=2)         # the lowest index among equal maxima
+            out[c0:c0 + chunk_cells] = first.to(torch.int32).cpu().numpy()
+    return out
+
+
+def classify_rooms(net, rooms, area=None, grid_resolution_m=None):
+    """PointNet2HIP.classify and PointNetHIP.classify: the cells of all rooms through net.classify_cells together."""
+    res = float(grid_resolution_m) if grid_resolution_m is not None else grid_resolution(area)
+    pts = [np.asarray(r['points'] if isinstance(r, dict) else r, dtype=np.float32) for r in rooms]
+    batches, maps = [], []
+    for k, p in enumerate(pts):
+        name = rooms[k].get('room_id', k) if isinstance(rooms[k], dict) else k
+        batch, members, _ = cell_inputs(p, res, room=name)
+        batches.append(batch)
+        maps.append(members)
+    out = [np.zeros(len(p), dtype=np.int32) for p in pts]
+    if not batches or sum(len(b) for b in batches) == 0:
         return out
+    cls = net.classify_cells(np.concatenate(batches))
+    c = 0
+    for k, members in enumerate(maps):
+        for idx in members:
+            out[k][idx] = cls[c, :len(idx)]
+            c += 1
+    return out
 
 
 def segment(rooms, classes, min_cluster_size=10, device=None, return_counts=False):
