@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 15
+#define LRG_ABI_VERSION 16
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -837,6 +837,13 @@ int lrg_mcp_embed(const float *pts, int ld, int n_points, const int32_t *nbr, co
  * epilogue is allowed.  dX = dZ W^T is (transB = 1); dW = X^T dZ over all rows is (transA = 1, split_k ~ rows / 1024). */
 int lrg_gemm_f32(int M, int N, int K, const float *A, int lda, int transA, const float *B, int ldb, int transB, float *C, int ldc,
                  const float *addend, const float *mask, int split_k, void *stream);
+/* The same product with the reduction split WITHOUT atomics (ABI 16): slice z of K stores its partial product in
+ * planes[z] ([M,N], row stride N; every element of every plane is written), z < lrg_gemm_f32_planes_count(K, split_k) <= split_k.
+ * The caller adds the planes in a fixed order (lrg_segment_colsum(planes, 1, count, M * N, out)), so that the same inputs give the
+ * same bits.  LRG_EINVAL - 2: more than 65535 planes. */
+int lrg_gemm_f32_planes_count(int K, int split_k);
+int lrg_gemm_f32_planes(int M, int N, int K, const float *A, int lda, int transA, const float *B, int ldb, int transB, float *planes,
+                        int split_k, void *stream);
 /* d(loss)/d(logits) of a sparse softmax cross entropy over `rows` two-class slots with per-class weights
  * (add head :174: w_pos = w_neg = 1 / rows; remove head :166-172: 1 / #positive and 1 / #negative slots of the batch).
  * stats (device double[8], ACCUMULATED): 0 weighted loss, 1 slots with argmax == label, 2 true positives, 3 predicted
@@ -855,6 +862,47 @@ int lrg_segment_colsum(const float *x, long n_seg, int seg_rows, int N, float *o
  * p -= lr_t m / (sqrt(v) + epsilon), with lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t) computed by the caller. */
 int lrg_adam_step(float *params, const float *grads, float *m, float *v, long n, float lr_t, float beta1, float beta2, float epsilon,
                   void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training side of the plain PointNet (train_pointnet.py:31-111; ABI 16; csrc/lrg_pointnet_train.hip): what its step needs beyond
+ * lrg_gemm_f32, lrg_pointwise_layer, lrg_segmax, lrg_segment_colsum and lrg_adam_step.  The step is sequenced by
+ * learn_region_grow_amd/pointnet_train.py (PointNetTrainer.train_step = sess.run([class_acc, class_loss, train_op]) at :408).
+ * A cell is 1024 rows.  No entry point allocates; none uses an atomic: every sum runs in one fixed order (the batch axis in ascending
+ * cell order), so the same inputs give the same bits.  Errors: LRG_EINVAL - 1 a NULL pointer, - 2 a size out of range, - 3 as noted.
+ * ---------------------------------------------------------------------------------------------- */
+/* :63-93 with is_training True.  z [cells,1024,c], gamma [c], beta [c]; c a multiple of 32 up to 512, cells >= 1.
+ * mean [1024,c] = the mean of z over the cells; var [1024,c] = the mean over the cells of (z - mean)^2 (tf.nn.moments :70: biased,
+ * two passes; exactly 0 for cells == 1); inv = rsqrt(var + 1e-3) * gamma; y = relu(z * inv + (beta - mean * inv))
+ * (tf.nn.batch_normalization :83 and the ReLU of :93). */
+int lrg_pointnet_bn_forward(const float *z, const float *gamma, const float *beta, int cells, int c, float *y, float *mean, float *var,
+                            void *stream);
+/* Bytes of lrg_pointnet_bn_backward's workspace (2 * 1024 * c floats); 0 when c is out of range. */
+size_t lrg_pointnet_bn_backward_workspace_bytes(int c);
+/* The gradient of :83-93 (batch norm in training mode, then ReLU).  z, y, dy [cells,1024,c]; mean, var [1024,c] as
+ * lrg_pointnet_bn_forward left them.  With g = dy where y > 0 else 0, rstd = rsqrt(var + 1e-3), xhat = (z - mean) * rstd:
+ * dz = gamma * rstd * (g - mean_cells(g) - xhat * mean_cells(g * xhat)) per (row position, channel); dbeta [c] and dgamma [c] are the
+ * sums of g and of g * xhat over cells and rows: over the cells first (workspace), then over the 1024 row positions in a second,
+ * fixed-order stage.  dz may be dy.  cells == 1 gives dz == +0 everywhere.  LRG_EINVAL - 3: the workspace is too small. */
+int lrg_pointnet_bn_backward(const float *z, const float *y, const float *dy, const float *mean, const float *var, const float *gamma, int cells,
+                             int c, float *dz, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream);
+/* :102-105.  logits [rows,classes], labels [rows] int32; 1 <= classes <= 1024 (LRG_EINVAL - 3 otherwise).
+ * dlogits [rows,classes] = (softmax - onehot) / rows (tf.reduce_mean of the rows' losses); NULL: not computed (evaluation).
+ * stats (device double[3], ACCUMULATED): 0 the sum of the rows' losses (one fixed order), 1 the rows whose argmax is the label (a tie
+ * to the lowest class, tf.argmax :104), 2 the rows whose label is outside [0, classes): such a row adds no loss, gets a zero gradient
+ * row and is never used as an index. */
+int lrg_pointnet_softmax_ce_grad(const float *logits, const int32_t *labels, long rows, int classes, float *dlogits, double *stats, void *stream);
+/* :56-59.  t [cells,1024,c_last] = last - pooled[cell] (float32), the first block of the head's input; the second is conv[1] (:60).
+ * c_last a multiple of 32 up to 1024. */
+int lrg_pointnet_head_input(const float *last, const float *pooled, int cells, int c_last, float *t, void *stream);
+/* The gradient of :56-59 with respect to conv_last, given dt [cells,1024,c_last]: dlast = dt, and -S[cell,c], S = the sum of dt over
+ * the cell's rows, is added on the FIRST row (lowest index) of the cell whose value equals pooled[cell,c] -- the single winner of
+ * tf.nn.max_pool2d's gradient (lrg_pool_backward shares among ties, tf.reduce_max's rule).  addend (nullable, the same shape) is
+ * added: a second gradient of the same tensor.  relu != 0 then zeroes the result where last <= 0 (the last convolution's own ReLU).
+ * dlast may be dt.  cells <= 65535. */
+int lrg_pointnet_head_input_backward(const float *last, const float *pooled, const float *dt, const float *addend, int cells, int c_last,
+                                     int relu, float *dlast, void *stream);
+/* ExponentialMovingAverage.apply (:71-78) on n floats: shadow -= (shadow - value) * one_minus_decay. */
+int lrg_pointnet_ema_update(float *shadow, const float *value, long n, float one_minus_decay, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Room preprocessing P0 (replaces the per-room block test_region_grow.py:119-173: equalisation, per-point PCA normals and

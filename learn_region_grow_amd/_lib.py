@@ -11,9 +11,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
-           'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip']
+           'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip', 'lrg_pointnet_train.hip']
 
-LRG_ABI_VERSION = 15      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 16      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -283,6 +283,13 @@ _SIGS = {
     'lrg_pointnet_pack_layer': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp]),
     'lrg_pointnet_features': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp, _fp, _fp, _fp, _fp, _fp]),
     'lrg_pointnet_head': (ctypes.c_int, [ctypes.c_int] * 3 + [_fp, _fp, _fp, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp, _fp, _fp, _fp]),
+    'lrg_pointnet_bn_forward': (ctypes.c_int, [_fp, _fp, _fp, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp]),
+    'lrg_pointnet_bn_backward_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int]),
+    'lrg_pointnet_bn_backward': (ctypes.c_int, [_fp] * 6 + [ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, ctypes.c_size_t, _fp]),
+    'lrg_pointnet_softmax_ce_grad': (ctypes.c_int, [_fp, _fp, ctypes.c_long, ctypes.c_int, _fp, _fp, _fp]),
+    'lrg_pointnet_head_input': (ctypes.c_int, [_fp, _fp, ctypes.c_int, ctypes.c_int, _fp, _fp]),
+    'lrg_pointnet_head_input_backward': (ctypes.c_int, [_fp, _fp, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp]),
+    'lrg_pointnet_ema_update': (ctypes.c_int, [_fp, _fp, ctypes.c_long, ctypes.c_float, _fp]),
     'lrg_mcp_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     'lrg_mcp_candidates': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, _fp, ctypes.c_size_t, _fp, _fp]),
     'lrg_mcp_neighbors': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, _fp, ctypes.c_size_t, _fp, ctypes.c_uint32, _fp, _fp, _fp]),
@@ -292,6 +299,9 @@ _SIGS = {
     'lrg_mcp_embed': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _fp]),
     'lrg_gemm_f32': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int,
                                     _fp, ctypes.c_int, _fp, _fp, ctypes.c_int, _fp]),
+    'lrg_gemm_f32_planes_count': (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    'lrg_gemm_f32_planes': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int,
+                                           _fp, ctypes.c_int, _fp]),
     'lrg_ce_grad': (ctypes.c_int, [_fp, _fp, ctypes.c_long, ctypes.c_float, ctypes.c_float, _fp, _fp, _fp]),
     'lrg_pool_backward': (ctypes.c_int, [_fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp]),
     'lrg_segment_colsum': (ctypes.c_int, [_fp, ctypes.c_long, ctypes.c_int, ctypes.c_int, _fp, _fp]),

@@ -637,3 +637,35 @@ def load_pointnet_weights(prefix, verify=True):
             raise BundleError('%s: %s: not float32' % (prefix, found[name]))
     loaded = load_bundle(prefix, names=sorted(set(found.values())), verify=verify)
     return {name: loaded[found[name]] for name in shapes}
+
+
+def pointnet_checkpoint_tensors(weights, adam_m=None, adam_v=None, step=0, beta1=0.9, beta2=0.999):
+    """Everything ``tf.compat.v1.train.Saver().save`` (train_pointnet.py:367, :438) writes for the PointNet graph: the trainables
+    (kernel*, bias*, fc_weights*, fc_bias*, every block's beta and gamma) with their Adam slots ``<name>/Adam`` and
+    ``<name>/Adam_1``, the batch norms' moving averages (pointnet_bn_names; shadows of tensors, not trainable, so without slots),
+    ``beta1_power`` / ``beta2_power`` and ``Variable`` (the global step ``batch``, :108) -- the key set of the shipped
+    models/pointnet_model5.ckpt.index for that architecture.  weights: name -> array in the TF shapes under the names of
+    pointnet_variable_shapes; adam_m / adam_v: the trainables' slots (missing: zeros, a freshly built optimizer).  The beta powers
+    follow lrgnet_checkpoint_tensors: beta ** (step + 1)."""
+    shapes = pointnet_variable_shapes(*pointnet_variant({k: np.shape(v) for k, v in weights.items()}))
+    averages = set()
+    j = 0
+    while pointnet_bn_names(j)[2] in shapes:
+        averages.update(pointnet_bn_names(j)[2:])
+        j += 1
+    out = {}
+    for k, shp in shapes.items():
+        if k not in weights:
+            raise KeyError('PointNet weight %s missing' % k)
+        w = np.asarray(weights[k], dtype=np.float32)
+        if w.shape != tuple(shp):
+            raise BundleError('%s has shape %s, PointNet needs %s' % (k, w.shape, shp))
+        out[k] = w
+        if k in averages:
+            continue
+        out[k + '/Adam'] = np.asarray(adam_m[k], dtype=np.float32).reshape(w.shape) if adam_m is not None else np.zeros_like(w)
+        out[k + '/Adam_1'] = np.asarray(adam_v[k], dtype=np.float32).reshape(w.shape) if adam_v is not None else np.zeros_like(w)
+    out['beta1_power'] = np.float32(float(beta1) ** (int(step) + 1))
+    out['beta2_power'] = np.float32(float(beta2) ** (int(step) + 1))
+    out['Variable'] = np.int32(step)
+    return out

@@ -20,10 +20,12 @@ struct LrgGemmArgs {
     const float *addend;     // nullable [M,N] (ldc): C = acc + addend
     const float *mask;       // nullable [M,N] (ldc): C = mask > 0 ? C : 0   (the ReLU gradient of the layer that PRODUCED the operand)
     int M, N, K, lda, ldb, ldc, transA, transB, kchunk, atomic;
+    long zstride;            // floats between the planes of C that the slices of K write (0: all slices share C and add atomically)
 };
 
 // C[M,N] = op(A)[M,K] op(B)[K,N]: one 64x64 tile per 256-thread workgroup (2x2 wavefronts of 32x32, v_mfma_f32_32x32x2_f32),
-// K through LDS in chunks of 32; blockIdx.z takes a slice of K and adds its partial tile atomically when the reduction is split.
+// K through LDS in chunks of 32; blockIdx.z takes a slice of K and, when the reduction is split, adds its partial tile atomically
+// (lrg_gemm_f32) or stores it in a plane of its own (lrg_gemm_f32_planes: the caller adds the planes in a fixed order).
 __global__ __launch_bounds__(256) void lrg_gemm_f32_kernel(LrgGemmArgs a) {
     __shared__ __attribute__((aligned(16))) float As[TG_BM * TG_LDA];
     __shared__ __attribute__((aligned(16))) float Bs[TG_BK * TG_LDB];
@@ -87,7 +89,8 @@ __global__ __launch_bounds__(256) void lrg_gemm_f32_kernel(LrgGemmArgs a) {
         const int row = m0 + wm * 32 + 4 * lh + (r & 3) + 8 * (r >> 2);
         if (row < a.M) {
             const long o = (long)row * a.ldc + col;
-            if (a.atomic) atomicAdd(&a.C[o], acc[r]);
+            if (a.zstride) a.C[blockIdx.z * a.zstride + o] = acc[r];
+            else if (a.atomic) atomicAdd(&a.C[o], acc[r]);
             else {
                 float v = acc[r];
                 if (a.addend) v += a.addend[o];
@@ -206,6 +209,32 @@ int lrg_gemm_f32(int M, int N, int K, const float *A, int lda, int transA, const
     a.kchunk = per * TG_BK;
     const int nz = (chunks + per - 1) / per;
     a.atomic = split_k > 1;
+    a.zstride = 0;
+    hipLaunchKernelGGL(lrg_gemm_f32_kernel, dim3((N + TG_BN - 1) / TG_BN, (M + TG_BM - 1) / TG_BM, nz), dim3(256), 0, (hipStream_t)stream, a);
+    LRG_LAUNCH_CHECK();
+    return 0;
+}
+
+int lrg_gemm_f32_planes_count(int K, int split_k) {
+    if (K <= 0 || split_k < 1) return 0;
+    const int chunks = (K + TG_BK - 1) / TG_BK;
+    const int per = (chunks + split_k - 1) / split_k;
+    return (chunks + per - 1) / per;
+}
+
+int lrg_gemm_f32_planes(int M, int N, int K, const float *A, int lda, int transA, const float *B, int ldb, int transB, float *planes,
+                        int split_k, void *stream) {
+    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !planes || lda <= 0 || ldb <= 0 || split_k < 1) return LRG_EINVAL - 1;
+    LrgGemmArgs a;
+    a.A = A; a.B = B; a.C = planes; a.addend = nullptr; a.mask = nullptr;
+    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = N; a.transA = transA; a.transB = transB;
+    const int chunks = (K + TG_BK - 1) / TG_BK;
+    const int per = (chunks + split_k - 1) / split_k;
+    a.kchunk = per * TG_BK;
+    const int nz = (chunks + per - 1) / per;
+    if (nz > 65535) return LRG_EINVAL - 2;
+    a.atomic = 0;
+    a.zstride = (long)M * N;
     hipLaunchKernelGGL(lrg_gemm_f32_kernel, dim3((N + TG_BN - 1) / TG_BN, (M + TG_BM - 1) / TG_BM, nz), dim3(256), 0, (hipStream_t)stream, a);
     LRG_LAUNCH_CHECK();
     return 0;
