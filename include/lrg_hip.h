@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 16
+#define LRG_ABI_VERSION 17
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -760,6 +760,18 @@ int lrg_pointnet2_group_mlp(int b, int n, int m, int nsample, int c, const float
  * layer except that relu_last == 0 leaves it off the last: out [r, widths[n_layers-1]].  r >= 0. */
 int lrg_pointnet2_row_mlp(long r, int ca, int cb, const float *a, const float *b, int n_layers, const int32_t *widths, int relu_last,
                           const float *packed, float *out, void *stream);
+/* The two entry points above in the training forward (ABI 17): the same arguments, the same checks and error codes, bit for bit the
+ * same `out`, and besides it what the backward pass reads, each pointer nullable (NULL: not written):
+ *   rows  [b*m*32, 3 + c]      the grouped rows concat(xyz[idx] - new_xyz, points[idx]) that group_point and the concat of
+ *                              sample_and_group (:116-120) would have written;
+ *   keepL [rows, widths[L]]    layer L's output after its ReLU (:137, :165), unpadded; for the grouped form keep2 is the last layer
+ *                              BEFORE the maximum over the 32 rows ([b*m*32, widths[2]]); for the row form keepL with L == n_layers-1
+ *                              repeats `out` and keepL with L >= n_layers is ignored. */
+int lrg_pointnet2_group_mlp_train(int b, int n, int m, int nsample, int c, const float *xyz, const float *new_xyz, const float *points,
+                                  const int32_t *idx, const int32_t *widths, const float *packed, float *out, float *rows, float *keep0,
+                                  float *keep1, float *keep2, void *stream);
+int lrg_pointnet2_row_mlp_train(long r, int ca, int cb, const float *a, const float *b, int n_layers, const int32_t *widths, int relu_last,
+                                const float *packed, float *out, float *keep0, float *keep1, float *keep2, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The plain PointNet of benchmarks.py --mode pointnet (train_pointnet.py:31-99) at inference (ABI 15; csrc/lrg_pointnet.hip).  A cell
@@ -903,6 +915,30 @@ int lrg_pointnet_head_input_backward(const float *last, const float *pooled, con
                                      int relu, float *dlast, void *stream);
 /* ExponentialMovingAverage.apply (:71-78) on n floats: shadow -= (shadow - value) * one_minus_decay. */
 int lrg_pointnet_ema_update(float *shadow, const float *value, long n, float one_minus_decay, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training side of PointNet2 (train_pointnet.py:113-211; ABI 17; csrc/lrg_pointnet2_train.hip): what its step needs beyond
+ * lrg_pointnet2_*_mlp_train, lrg_three_nn_interpolate, lrg_pool_backward, lrg_gemm_f32, lrg_gemm_f32_planes, lrg_segment_colsum,
+ * lrg_pointnet_softmax_ce_grad and lrg_adam_step.  The step is sequenced by learn_region_grow_amd/pointnet2_train.py
+ * (PointNet2Trainer.train_step = sess.run([class_acc, class_loss, train_op])).  DESIGN.md §3.14.
+ * ---------------------------------------------------------------------------------------------- */
+/* The gradients of group_point (groupPointGradLauncher, tf_grouping_g.cu:61-78, :137) and of three_interpolate
+ * (threeinterpolate_grad_cpu, tf_interpolate.cpp:131-155) WITHOUT atomic additions, in place of lrg_group_point_grad and
+ * lrg_three_interpolate_grad inside a training step:
+ *   out[bi, idx[bi, e], k] = addend[bi, idx[bi, e], k] + sum over e of weight[bi, e] * grad[bi, e / per, col0 + k],   k < c,
+ * the sum over the entries e (0 <= e < q * per) that name the same source row taken in ASCENDING e from 0 (float32 multiplication, then
+ * float32 addition), whatever the launch holds besides: the same inputs give the same bits.  grad [b, q, ldg] (col0 + c <= ldg: a column
+ * block of a wider tensor is read in place), idx [b, q * per] int32, weight [b, q * per] (NULL: 1, no multiplication), out [b, n, c];
+ * addend and mask [b, n, c], both nullable; addend may be out.  Every row of out is written: a row nobody names gets 0, or the addend
+ * alone.  With mask, out = 0 where mask <= 0 (the ReLU of the layer whose output `out` is the gradient of), as lrg_gemm_f32's epilogue.
+ * An index outside [0, n) follows the forward op: drop_out_of_range == 0 sends it to row 0 (lrg_pointnet2_group_mlp reads row 0),
+ * 1 drops it (lrg_three_interpolate adds 0).
+ *   group_point's gradient     q = m * 32, per = 1, weight NULL, col0 = 3 on the first layer's dX [b, m * 32, 3 + c], drop 0
+ *   three_interpolate's        q = the queries, per = 3, weight the interpolation weights, col0 = 0, drop 1
+ * q * per <= 16384 (the element's inverse lists are built in LDS); b <= 65535.  Errors: LRG_EINVAL - 1 a NULL pointer, - 2 a size out of
+ * range (nothing is launched).  b == 0 returns 0. */
+int lrg_pointnet2_scatter_grad(int b, int n, int q, int per, int c, const float *grad, int ldg, int col0, const int32_t *idx,
+                               const float *weight, int drop_out_of_range, const float *addend, const float *mask, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Room preprocessing P0 (replaces the per-room block test_region_grow.py:119-173: equalisation, per-point PCA normals and

@@ -11,9 +11,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
-           'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip', 'lrg_pointnet_train.hip']
+           'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip', 'lrg_pointnet_train.hip',
+           'lrg_pointnet2_train.hip']
 
-LRG_ABI_VERSION = 16      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 17      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -279,6 +280,11 @@ _SIGS = {
     'lrg_pointnet2_group_mlp': (ctypes.c_int, [ctypes.c_int] * 5 + [_fp, _fp, _fp, _fp, ctypes.POINTER(ctypes.c_int32), _fp, _fp, _fp]),
     'lrg_pointnet2_row_mlp': (ctypes.c_int, [ctypes.c_long, ctypes.c_int, ctypes.c_int, _fp, _fp, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                              ctypes.c_int, _fp, _fp, _fp]),
+    'lrg_pointnet2_group_mlp_train': (ctypes.c_int, [ctypes.c_int] * 5 + [_fp, _fp, _fp, _fp, ctypes.POINTER(ctypes.c_int32), _fp, _fp, _fp, _fp, _fp, _fp,
+                                                     _fp]),
+    'lrg_pointnet2_row_mlp_train': (ctypes.c_int, [ctypes.c_long, ctypes.c_int, ctypes.c_int, _fp, _fp, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
+                                                   ctypes.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),
+    'lrg_pointnet2_scatter_grad': (ctypes.c_int, [ctypes.c_int] * 5 + [_fp, ctypes.c_int, ctypes.c_int, _fp, _fp, ctypes.c_int, _fp, _fp, _fp, _fp]),
     'lrg_pointnet_packed_floats': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     'lrg_pointnet_pack_layer': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp]),
     'lrg_pointnet_features': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp, _fp, _fp, _fp, _fp, _fp]),

@@ -513,7 +513,30 @@ def load_pointnet2_weights(prefix, verify=True):
     return load_bundle(prefix, names=list(shapes), verify=verify)
 
 
-POINTNET_NUM_POINT = 1024                                            # the row positions of a cell: the batch-norm tables' first axis
+def pointnet2_checkpoint_tensors(weights, adam_m=None, adam_v=None, step=0, beta1=0.9, beta2=0.999):
+    """Everything ``tf.compat.v1.train.Saver().save`` (train_pointnet.py:367, :438) writes for the PointNet2 graph: the 46 trainables
+    with their Adam slots ``<name>/Adam`` and ``<name>/Adam_1``, ``beta1_power`` / ``beta2_power`` and ``Variable`` (the global step
+    ``batch``, :209) -- 141 entries, the key set of the shipped models/pointnet2_model5.ckpt.index for the xyz-only variant.  weights:
+    name -> array in the TF shapes of pointnet2_variable_shapes (the variant and the class count are read from them); adam_m / adam_v:
+    the slots (missing: zeros, a freshly built optimizer).  The beta powers follow pointnet_checkpoint_tensors: beta ** (step + 1)."""
+    shapes = pointnet2_variable_shapes(*pointnet2_variant({k: np.shape(v) for k, v in weights.items()}))
+    out = {}
+    for k, shp in shapes.items():
+        if k not in weights:
+            raise KeyError('PointNet2 weight %s missing' % k)
+        w = np.asarray(weights[k], dtype=np.float32)
+        if w.shape != tuple(shp):
+            raise BundleError('%s has shape %s, PointNet2 needs %s' % (k, w.shape, shp))
+        out[k] = w
+        out[k + '/Adam'] = np.asarray(adam_m[k], dtype=np.float32).reshape(w.shape) if adam_m is not None else np.zeros_like(w)
+        out[k + '/Adam_1'] = np.asarray(adam_v[k], dtype=np.float32).reshape(w.shape) if adam_v is not None else np.zeros_like(w)
+    out['beta1_power'] = np.float32(float(beta1) ** (int(step) + 1))
+    out['beta2_power'] = np.float32(float(beta2) ** (int(step) + 1))
+    out['Variable'] = np.int32(step)
+    return out
+
+
+POINTNET_NUM_POINT = 1024                                           # the row positions of a cell: the batch-norm tables' first axis
 _POINTNET_MEAN = 'moments/Squeeze/ExponentialMovingAverage'
 _POINTNET_VARIANCE = 'moments/Squeeze_1/ExponentialMovingAverage'
 

@@ -16,6 +16,9 @@
 //            buffer serves input and output) and they meet again.
 //   last     grouped: bias, ReLU, the maximum over the lane's 16 rows, then over the two lane halves (no atomics); row form:
 //            bias (ReLU unless relu_last == 0) straight to out.
+//   keep     the training forms (KEEP; lrg_pointnet2_*_mlp_train) also store what the backward pass reads: the rows as filled
+//            (grouped form) and every layer's post-ReLU output, [rows, width] unpadded.  The stores sit beside the arithmetic,
+//            never in it: the last output carries the same bits with and without them.
 // LDS: 32 * (max width + 4) * 4 bytes, dynamic: 131.6 KB for the widest legal input (1024), 16.9 KB for a 128-wide level, so the
 // narrow levels keep several workgroups on a CU.
 #include "lrg_common.h"
@@ -41,11 +44,13 @@ struct Pn2Args {
     int kpad[PN2_MAX_LAYERS], nout[PN2_MAX_LAYERS], npad[PN2_MAX_LAYERS];
     long woff[PN2_MAX_LAYERS];
     const float *packed; float *out;
+    // training forms only (each nullable): the filled rows [tiles * 32, k0] and the layers' post-ReLU outputs [rows, nout[L]]
+    float *rows_out; float *keep[PN2_MAX_LAYERS];
 };
 
 static inline int pn2_up32(int v) { return lrg_mlp_up32(v); }
 
-template <bool GROUPED>
+template <bool GROUPED, bool KEEP>
 __global__ __launch_bounds__(PN2_THREADS) void pn2_mlp_kernel(Pn2Args a) {
     extern __shared__ __attribute__((aligned(16))) float pn2_act[];      // [32][ldw]
     __shared__ int s_j[PN2_ROWS];
@@ -71,6 +76,7 @@ __global__ __launch_bounds__(PN2_THREADS) void pn2_mlp_kernel(Pn2Args a) {
             if (col < 3) v = __fsub_rn(xb[(long)j * 3 + col], ctr[col]);
             else if (col < k0) v = pb[(long)j * a.c + (col - 3)];
             act[row * ldw + col] = v;
+            if (KEEP && a.rows_out && col < k0) a.rows_out[(row0 + row) * k0 + col] = v;
         }
     } else {
         for (int e = tid; e < PN2_ROWS * k0p; e += PN2_THREADS) {
@@ -129,11 +135,14 @@ __global__ __launch_bounds__(PN2_THREADS) void pn2_mlp_kernel(Pn2Args a) {
                 if (t < nt) {
                     const int col = 32 * t + rl;
                     const float bv = bias[col];
+                    float *kp = KEEP ? a.keep[L] : nullptr;              // hidden widths are multiples of 32: col < nout[L]
 #pragma unroll
                     for (int q = 0; q < 16; ++q) {
                         const int rr = (q & 3) + 8 * (q >> 2) + 4 * h;
                         const float v = __fadd_rn(acc[u][q], bv);
-                        act[rr * ldw + col] = v > 0.f ? v : 0.f;
+                        const float y = v > 0.f ? v : 0.f;
+                        act[rr * ldw + col] = y;
+                        if (KEEP && kp && (GROUPED || row0 + rr < a.r)) kp[(row0 + rr) * a.nout[L] + col] = y;
                     }
                 }
             }
@@ -150,6 +159,13 @@ __global__ __launch_bounds__(PN2_THREADS) void pn2_mlp_kernel(Pn2Args a) {
                         float mx = 0.f;                                  // ReLU output: the maximum is >= 0
 #pragma unroll
                         for (int q = 0; q < 16; ++q) mx = fmaxf(mx, __fadd_rn(acc[u][q], bv));
+                        if (KEEP && a.keep[L] && col < n_out) {
+#pragma unroll
+                            for (int q = 0; q < 16; ++q) {
+                                const float v = __fadd_rn(acc[u][q], bv);
+                                a.keep[L][(row0 + (q & 3) + 8 * (q >> 2) + 4 * h) * n_out + col] = v > 0.f ? v : 0.f;
+                            }
+                        }
                         mx = fmaxf(mx, __shfl_xor(mx, 32));
                         if (h == 0 && col < n_out) a.out[tile * n_out + col] = mx;
                     } else {
@@ -159,6 +175,7 @@ __global__ __launch_bounds__(PN2_THREADS) void pn2_mlp_kernel(Pn2Args a) {
                             float v = __fadd_rn(acc[u][q], bv);
                             if (a.relu_last) v = v > 0.f ? v : 0.f;
                             if (i < a.r && col < n_out) a.out[i * n_out + col] = v;
+                            if (KEEP && a.keep[L] && i < a.r && col < n_out) a.keep[L][i * n_out + col] = v;
                         }
                     }
                 }
@@ -190,9 +207,9 @@ static int pn2_layers(int n_layers, const int32_t *widths, bool last_any, Pn2Arg
     return 0;
 }
 
-template <bool GROUPED>
+template <bool GROUPED, bool KEEP>
 static int pn2_launch(const Pn2Args &a, hipStream_t st) {
-    auto kern = pn2_mlp_kernel<GROUPED>;
+    auto kern = pn2_mlp_kernel<GROUPED, KEEP>;
     static bool attr_done[LRG_MAX_DEVICES] = {};
     const int dev = lrg_current_device();
     if (!attr_done[dev]) {
@@ -203,6 +220,46 @@ static int pn2_launch(const Pn2Args &a, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3((unsigned)a.tiles), dim3(PN2_THREADS), lds, st, a);
     LRG_LAUNCH_CHECK();
     return 0;
+}
+
+// The argument checks and the launch of both grouped forms (KEEP = false: the inference form, rows and keep unused), then of both row forms.
+template <bool KEEP>
+static int pn2_group_mlp(int b, int n, int m, int nsample, int c, const float *xyz, const float *new_xyz, const float *points,
+                         const int32_t *idx, const int32_t *widths, const float *packed, float *out, float *rows, float *const *keep,
+                         void *stream) {
+    if (nsample != PN2_ROWS) return LRG_EINVAL - 95;
+    if (b < 0 || n < 1 || m < 0 || c < 0 || c > PN2_MAX_IN - 3) return LRG_EINVAL - 96;
+    if (!widths) return LRG_EINVAL - 91;
+    Pn2Args a = {};
+    const int32_t w4[4] = {3 + c, widths[0], widths[1], widths[2]};
+    int rc = pn2_layers(3, w4, false, &a);
+    if (rc) return rc;
+    const long groups = (long)b * m;
+    if (groups == 0) return 0;
+    if (groups > (1L << 30)) return LRG_EINVAL - 96;
+    if (!xyz || !new_xyz || !idx || !packed || !out || (c > 0 && !points) || ((uintptr_t)packed & 15)) return LRG_EINVAL - 97;
+    a.xyz = xyz; a.new_xyz = new_xyz; a.points = c > 0 ? points : nullptr; a.idx = idx; a.n = n; a.m = m; a.c = c;
+    a.tiles = groups; a.relu_last = 1; a.packed = packed; a.out = out;
+    if (KEEP) { a.rows_out = rows; for (int L = 0; L < 3; ++L) a.keep[L] = keep[L]; }
+    return pn2_launch<true, KEEP>(a, (hipStream_t)stream);
+}
+
+template <bool KEEP>
+static int pn2_row_mlp(long r, int ca, int cb, const float *rows_a, const float *rows_b, int n_layers, const int32_t *widths,
+                       int relu_last, const float *packed, float *out, float *const *keep, void *stream) {
+    if (r < 0 || r > (1L << 35) || ca < 1 || cb < 0 || ca > PN2_MAX_IN || cb > PN2_MAX_IN || ca + cb > PN2_MAX_IN) return LRG_EINVAL - 98;
+    if (n_layers < 1 || n_layers > PN2_MAX_LAYERS || !widths || (relu_last != 0 && relu_last != 1)) return LRG_EINVAL - 91;
+    Pn2Args a = {};
+    int32_t w4[4] = {ca + cb, 0, 0, 0};
+    for (int L = 0; L < n_layers; ++L) w4[L + 1] = widths[L];
+    int rc = pn2_layers(n_layers, w4, true, &a);
+    if (rc) return rc;
+    if (r == 0) return 0;
+    if (!rows_a || (cb > 0 && !rows_b) || !packed || !out || ((uintptr_t)packed & 15)) return LRG_EINVAL - 97;
+    a.a = rows_a; a.b = cb > 0 ? rows_b : nullptr; a.ca = ca; a.cb = cb; a.r = r;
+    a.tiles = (r + PN2_ROWS - 1) / PN2_ROWS; a.relu_last = relu_last; a.packed = packed; a.out = out;
+    if (KEEP) for (int L = 0; L < n_layers; ++L) a.keep[L] = keep[L];
+    return pn2_launch<false, KEEP>(a, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -220,36 +277,25 @@ int lrg_pointnet2_pack_layer(int k, int n, const float *w, const float *bias, fl
 
 int lrg_pointnet2_group_mlp(int b, int n, int m, int nsample, int c, const float *xyz, const float *new_xyz, const float *points,
                             const int32_t *idx, const int32_t *widths, const float *packed, float *out, void *stream) {
-    if (nsample != PN2_ROWS) return LRG_EINVAL - 95;
-    if (b < 0 || n < 1 || m < 0 || c < 0 || c > PN2_MAX_IN - 3) return LRG_EINVAL - 96;
-    if (!widths) return LRG_EINVAL - 91;
-    Pn2Args a = {};
-    const int32_t w4[4] = {3 + c, widths[0], widths[1], widths[2]};
-    int rc = pn2_layers(3, w4, false, &a);
-    if (rc) return rc;
-    const long groups = (long)b * m;
-    if (groups == 0) return 0;
-    if (groups > (1L << 30)) return LRG_EINVAL - 96;
-    if (!xyz || !new_xyz || !idx || !packed || !out || (c > 0 && !points) || ((uintptr_t)packed & 15)) return LRG_EINVAL - 97;
-    a.xyz = xyz; a.new_xyz = new_xyz; a.points = c > 0 ? points : nullptr; a.idx = idx; a.n = n; a.m = m; a.c = c;
-    a.tiles = groups; a.relu_last = 1; a.packed = packed; a.out = out;
-    return pn2_launch<true>(a, (hipStream_t)stream);
+    return pn2_group_mlp<false>(b, n, m, nsample, c, xyz, new_xyz, points, idx, widths, packed, out, nullptr, nullptr, stream);
 }
 
 int lrg_pointnet2_row_mlp(long r, int ca, int cb, const float *rows_a, const float *rows_b, int n_layers, const int32_t *widths,
                           int relu_last, const float *packed, float *out, void *stream) {
-    if (r < 0 || r > (1L << 35) || ca < 1 || cb < 0 || ca > PN2_MAX_IN || cb > PN2_MAX_IN || ca + cb > PN2_MAX_IN) return LRG_EINVAL - 98;
-    if (n_layers < 1 || n_layers > PN2_MAX_LAYERS || !widths || (relu_last != 0 && relu_last != 1)) return LRG_EINVAL - 91;
-    Pn2Args a = {};
-    int32_t w4[4] = {ca + cb, 0, 0, 0};
-    for (int L = 0; L < n_layers; ++L) w4[L + 1] = widths[L];
-    int rc = pn2_layers(n_layers, w4, true, &a);
-    if (rc) return rc;
-    if (r == 0) return 0;
-    if (!rows_a || (cb > 0 && !rows_b) || !packed || !out || ((uintptr_t)packed & 15)) return LRG_EINVAL - 97;
-    a.a = rows_a; a.b = cb > 0 ? rows_b : nullptr; a.ca = ca; a.cb = cb; a.r = r;
-    a.tiles = (r + PN2_ROWS - 1) / PN2_ROWS; a.relu_last = relu_last; a.packed = packed; a.out = out;
-    return pn2_launch<false>(a, (hipStream_t)stream);
+    return pn2_row_mlp<false>(r, ca, cb, rows_a, rows_b, n_layers, widths, relu_last, packed, out, nullptr, stream);
+}
+
+int lrg_pointnet2_group_mlp_train(int b, int n, int m, int nsample, int c, const float *xyz, const float *new_xyz, const float *points,
+                                  const int32_t *idx, const int32_t *widths, const float *packed, float *out, float *rows, float *keep0,
+                                  float *keep1, float *keep2, void *stream) {
+    float *const keep[3] = {keep0, keep1, keep2};
+    return pn2_group_mlp<true>(b, n, m, nsample, c, xyz, new_xyz, points, idx, widths, packed, out, rows, keep, stream);
+}
+
+int lrg_pointnet2_row_mlp_train(long r, int ca, int cb, const float *rows_a, const float *rows_b, int n_layers, const int32_t *widths,
+                                int relu_last, const float *packed, float *out, float *keep0, float *keep1, float *keep2, void *stream) {
+    float *const keep[3] = {keep0, keep1, keep2};
+    return pn2_row_mlp<true>(r, ca, cb, rows_a, rows_b, n_layers, widths, relu_last, packed, out, keep, stream);
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@ reads.
     python train_pointnet.py --arch shipped --epochs 20 --ckpt out/pointnet.ckpt
 
 Options of the reference that are kept: --mode, --train-area, --val-area, --cross-domain.  ``--mode pointnet2`` is refused: training
-PointNet++ needs the gradients of the whole sampling and interpolation stack and is out of scope.  ``--arch`` picks
+PointNet++ needs the gradients of the whole sampling and interpolation stack and has a driver of its own, ``train_pointnet2.py``.  ``--arch`` picks
 the network: 'today' is what the script builds now ((64,64,64,128,1024) / (512,256)), 'shipped' the one of the shipped
 pointnet_model5 ((64,64,128,512) / (512,)).  Staging, the per-batch choice of 1024 of a cell's 2048 rows (:399-402) and jitter_data
 (:235-246) make the legacy NumPy generator's draws in the script's order, seeded by --seed.  The last partial batch is dropped (:388).
@@ -117,8 +117,8 @@ def run_epoch(trainer, points, labels, rs, batch_size, train):
 def main(argv=None):
     args = parse(argv)
     if args.mode == 'pointnet2':
-        raise SystemExit('train_pointnet.py: --mode pointnet2 is not supported: training PointNet++ needs the gradients of the whole sampling '
-                         'and interpolation stack and is out of scope (DESIGN.md §7); use --mode pointnet')
+        raise SystemExit('train_pointnet.py: --mode pointnet2 is not supported here: training PointNet++ needs the gradients of the whole '
+                         'sampling and interpolation stack and has a driver of its own, train_pointnet2.py (DESIGN.md §7); use --mode pointnet')
     if args.mode != 'pointnet':
         raise SystemExit("train_pointnet.py: unknown --mode %r (only 'pointnet')" % args.mode)
     import torch
