@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Command-line driver with the job of the reference's ``benchmarks.py`` for its classical region-growing baselines:
-modes ``normal``, ``curvature``, ``color``, ``feature`` and ``smoothness`` on the GPU, the reference's per-room timing and
+modes ``normal``, ``curvature``, ``color``, ``feature``, ``smoothness`` and ``fpfh`` on the GPU, the reference's per-room timing and
 metric lines and its aggregate line, optional PLY export.
 
     python baselines.py --area 5 --mode smoothness          # data/s3dis_area5.h5 (benchmarks.py:187-190)
@@ -11,7 +11,9 @@ The rooms of a file go to the GPU in batches (--batch-rooms per lrg_baseline_seg
 of a room is its feature time plus its share, by equalised points, of its batch's segmentation time.  --features verified solves
 the 3x3 decompositions on the GPU too and sends only the points whose labels or rank could depend on the solver through LAPACK: the
 same lines, several times faster in the modes that read normals.  Mode pointnet2 of
-benchmarks.py is pointnet2.py; edge, fpfh and pointnet are not ported.
+benchmarks.py is pointnet2.py and mode pointnet is pointnet.py (§3.12).  Mode fpfh computes its descriptor on the GPU
+with the arithmetic of PCL's FPFHEstimation, not with PCL's command-line tools (§3.15); its time goes into the batch's segmentation
+time.  Mode edge is not ported.
 """
 import argparse
 import os
@@ -26,9 +28,9 @@ if REPO not in sys.path:
 
 
 def parse(argv=None):
-    from learn_region_grow_amd.baselines import MODES
+    from learn_region_grow_amd.baselines import ALL_MODES
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('--mode', default='normal', choices=MODES)
+    ap.add_argument('--mode', default='normal', choices=ALL_MODES)
     ap.add_argument('--area', default='1,2,3,4,5,6,scannet', help="comma list of areas: 'scannet', 's3dis', 'kitti_train', ... or an S3DIS area number")
     ap.add_argument('--h5', default=None, help='room file (overrides --area for the data; the area still names the lines)')
     ap.add_argument('--data-dir', default='data')
@@ -84,6 +86,8 @@ def report_room(args, mode, area, r, names, raw_points, seconds, m, unequalized_
 def main(argv=None):
     args = parse(argv)
     from learn_region_grow_amd import baselines, io, metrics
+    if args.mode == 'fpfh' and args.features == 'verified':
+        sys.exit("--mode fpfh needs --features lapack: no certificate covers the descriptor (DESIGN.md §3.15)")
     areas = args.area.split(',')
     t = list(baselines.default_thresholds(args.mode, areas[0]))
     if args.threshold is not None:

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 17
+#define LRG_ABI_VERSION 18
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -734,6 +734,37 @@ int lrg_baseline_segment_embedding(const float *pts, int ld, const int32_t *room
  * order (:405-416), as lrg_baseline_segment_embedding does; same workspace (lrg_baseline_workspace_bytes), same lrg_baseline_status. */
 int lrg_baseline_segment_labels(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const int32_t *cls,
                                 int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream);
+/* ABI 18.  The edges of benchmarks.py:359-367 (mode fpfh) on the 26-neighbour voxel graph: hist [n, 33] float32 on the device; in float64
+ * without contraction s = the sum over d = 0 .. 32, in that order, of double(hist[d])^2, u[d] = double(hist[d]) / sqrt(s), and an edge iff
+ * ((u_i[0] u_k[0] + u_i[1] u_k[1]) + ...) > t, every product and every sum rounded (a zero histogram gives NaN: no edge).  u [n, 33]
+ * float64 is made once per call in the workspace, which is therefore larger than its siblings': lrg_baseline_fpfh_workspace_bytes
+ * (0 when an argument is out of range).  Components and numbering as lrg_baseline_segment_embedding; the same lrg_baseline_status
+ * reads this workspace too.  DESIGN.md §3.15. */
+size_t lrg_baseline_fpfh_workspace_bytes(int n_points, int n_rooms, int min_cluster_size);
+int lrg_baseline_segment_fpfh(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const float *hist, double t,
+                              int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 18.  Fast Point Feature Histograms for benchmarks.py --mode fpfh (:354-358) without PCL: the arithmetic of PCL's
+ * FPFHEstimation in float32 on the +-2 voxel window of an equalised room (csrc/lrg_fpfh.hip).
+ * ---------------------------------------------------------------------------------------------- */
+#define LRG_FPFH_LISTS 1               /* flags: the pair pass stores each point's neighbour list for the gather pass (192 B a point) */
+/* Workspace of lrg_fpfh: 0 when an argument is out of range. */
+size_t lrg_fpfh_workspace_bytes(int n_points, int n_rooms, int flags);
+/* A batch of equalised rooms in one fixed sequence of launches (init, insert, pairs, gather).  room_start [n_rooms + 1] is HOST memory,
+ * as for lrg_baseline_segment.  Device pointers: pts [n, ld] float32, ld >= 3: columns 0-2 give the voxels (rint(x / resolution));
+ * xyz [n, 3] and normals [n, 3] float32: the values every distance and pair feature is computed from (the caller's PCD round trip of
+ * pts and of the normals).  A neighbour of i is every j of i's room, i included, whose voxel lies within +-2 of i's on every axis and
+ * whose d2 = (dx dx + dy dy) + dz dz <= radius * radius in float32; neighbours never cross a room boundary.  radius > 2 * resolution
+ * is refused with LRG_EINVAL: the window could not hold the ball.
+ * Outputs (device): counts [n, 33] int32, the three 11-bin pair-feature histograms of the point; k [n] int32, its neighbour count
+ * (itself included); fpfh [n, 33] float32, the distance-weighted sum of the neighbours' histograms, each block of 11 scaled to
+ * sum 100.  The output does not depend on flags, on the batch or on the run.  Errors found on the device go to lrg_fpfh_status. */
+int lrg_fpfh(const float *pts, int ld, const float *xyz, const float *normals, const int32_t *room_start, int n_rooms, float resolution,
+             float radius, int flags, void *ws, size_t ws_bytes, int32_t *counts, int32_t *k, float *fpfh, void *stream);
+/* Error bits of the last lrg_fpfh on this workspace (synchronises the stream), with the meanings of lrg_baseline_status: 1 a voxel
+ * outside the 21-bit window, 2 two points of one room in one voxel.  The outputs are not valid when it is non-zero. */
+int lrg_fpfh_status(const void *ws, int n_points, int n_rooms, int flags, int32_t *host_status, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * PointNet2's shared MLPs (train_pointnet.py:126-167, :193-202; the caller is benchmarks.py:281-298).  fp32 on

@@ -12,9 +12,9 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
            'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip', 'lrg_pointnet_train.hip',
-           'lrg_pointnet2_train.hip']
+           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip']
 
-LRG_ABI_VERSION = 17      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 18      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -127,6 +127,7 @@ LRG_VGRID_MAX_CELLS = 1 << 26          # dense voxel grid of a room (LrgRoom.vgr
 LRG_VGRID_TOTAL_CELLS = 1 << 31        # ... and 8 GB for the rooms of one grower
 LRG_DONE_RING = 1020
 LRG_STATS_WORDS = 4 + LRG_DONE_RING
+LRG_FPFH_LISTS = 1                     # lrg_fpfh flags: the pair pass stores the neighbour lists for the gather pass
 
 
 class LrgHipError(RuntimeError):
@@ -275,6 +276,13 @@ _SIGS = {
                                                       ctypes.c_int, _fp, ctypes.c_size_t, _fp, _fp, _fp]),
     'lrg_baseline_segment_labels': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_float, _fp, ctypes.c_int, _fp, ctypes.c_size_t,
                                                    _fp, _fp, _fp]),
+    'lrg_baseline_fpfh_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3),
+    'lrg_baseline_segment_fpfh': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_float, _fp, ctypes.c_double, ctypes.c_int, _fp,
+                                                 ctypes.c_size_t, _fp, _fp, _fp]),
+    'lrg_fpfh_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3),
+    'lrg_fpfh': (ctypes.c_int, [_fp, ctypes.c_int, _fp, _fp, _fp, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int, _fp, ctypes.c_size_t,
+                                _fp, _fp, _fp, _fp]),
+    'lrg_fpfh_status': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp]),
     'lrg_pointnet2_packed_floats': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     'lrg_pointnet2_pack_layer': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp]),
     'lrg_pointnet2_group_mlp': (ctypes.c_int, [ctypes.c_int] * 5 + [_fp, _fp, _fp, _fp, ctypes.POINTER(ctypes.c_int32), _fp, _fp, _fp]),

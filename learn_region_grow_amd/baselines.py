@@ -2,7 +2,9 @@
 
 Modes ``normal``, ``curvature``, ``color``, ``feature`` and ``smoothness`` (benchmarks.py:127-142, 251-416): edges on the
 26-neighbour voxel graph of an equalised room by a per-mode predicate, connected components, and the components of more than
-``min_cluster_size`` points numbered as the reference numbers them.
+``min_cluster_size`` points numbered as the reference numbers them.  Mode ``fpfh`` (:354-367, ``ALL_MODES``) does
+the same with Fast Point Feature Histograms, computed here (``fpfh``, C-ABI ``lrg_fpfh``) instead of by PCL's command-line tools
+(DESIGN.md §3.15).
 
 ``room_features``  equalisation and float64 covariances on the GPU (``lrg_preprocess`` eig_mode 0), then the reference's own
                    ``numpy.linalg.svd`` on the host (benchmarks.py:199-249): normals and UNnormalised curvatures bit for bit.
@@ -23,6 +25,7 @@ import torch
 from . import _lib
 
 MODES = ('normal', 'curvature', 'color', 'feature', 'smoothness')
+ALL_MODES = MODES + ('fpfh',)                           # fpfh: its own entry points (lrg_fpfh, lrg_baseline_segment_fpfh), no LRG_BASELINE_* id
 _MODE_ID = {m: i for i, m in enumerate(MODES)}          # include/lrg_hip.h: LRG_BASELINE_*
 MAX_MIN_CLUSTER_SIZE = 64                               # LRG_BASELINE_MAX_MIN_CLUSTER
 _NEEDS_NORMALS = ('normal', 'curvature', 'feature', 'smoothness')
@@ -46,7 +49,9 @@ def default_thresholds(mode, area=None):
         return (0.985 if str(area) == 'scannet' else 0.98, 0.0, 0.0)
     if mode == 'feature':
         return (0.98, 0.1, 0.1)
-    raise ValueError('unknown baseline mode %r (one of %s)' % (mode, ', '.join(MODES)))
+    if mode == 'fpfh':
+        return (0.985, 0.0, 0.0)
+    raise ValueError('unknown baseline mode %r (one of %s)' % (mode, ', '.join(ALL_MODES)))
 
 
 def _device(device):
@@ -152,6 +157,71 @@ def room_features(unequalized_points, resolution=0.1, need_normals=True, device=
     return out
 
 
+def pcd_roundtrip(a):
+    """What a float32 value is after the reference's PCD round trip (benchmarks.py:355: savePCD prints '%f', PCL parses float32):
+    float32(float('%f' % v)) for every element.  '%f' rounds the value's exact decimal expansion to six places, half to even;
+    double(v) * 1e6 is exact (24 bits times the 14 of 15625, times 2^6), so rint of it is that integer, and dividing it by 1e6 is
+    correctly rounded, i.e. the double that float() parses from the string."""
+    v = np.asarray(a, dtype=np.float32).astype(np.float64)
+    with np.errstate(invalid='ignore'):
+        return (np.rint(v * 1e6) / 1e6).astype(np.float32)
+
+
+def _check_radius(resolution, radius):
+    radius = 2 * resolution if radius is None else radius
+    if not np.float32(radius) > 0 or np.float32(radius) > np.float32(2) * np.float32(resolution):
+        raise ValueError('fpfh: radius %g must lie in (0, 2 * resolution = %g]: neighbours are looked for in the +-2 voxel window' %
+                         (radius, 2 * resolution))
+    return radius
+
+
+def fpfh(rooms, resolution=0.1, radius=None, device=None, return_counts=False, lists=True):
+    """Fast Point Feature Histograms of every room in ONE lrg_fpfh call (benchmarks.py:355-358 without PCL).
+
+    rooms: dicts as ``room_features(..., need_normals=True)`` returns them.  Points and float32(normals) go through
+    ``pcd_roundtrip``; the voxels come from the points as they are.  radius defaults to 2 * resolution (:356) and may not exceed it.
+    Returns a list of [N, 33] float32 arrays; with return_counts=True also a list of (counts [N, 33] int32, k [N] int32) per room: the
+    pair-feature histograms and the neighbour counts (the point itself included) the descriptor is made of.  lists=True (the
+    default: the faster form, DESIGN.md §3.15) makes the gather pass read neighbour lists the pair pass stored, 192 bytes a point;
+    lists=False makes it probe the window again: same output."""
+    radius = _check_radius(resolution, radius)
+    if any(r.get('normals') is None for r in rooms):
+        raise ValueError("fpfh needs 'normals' for every room (room_features(..., need_normals=True))")
+    if len(rooms) == 0:
+        return ([], []) if return_counts else []
+    lib = _lib.load()
+    dev = _device(device)
+    room_start = np.zeros(len(rooms) + 1, dtype=np.int32)
+    room_start[1:] = np.cumsum([len(r['points']) for r in rooms])
+    n = int(room_start[-1])
+    flags = _lib.LRG_FPFH_LISTS if lists else 0
+
+    def up(parts, width, dtype=np.float32):
+        a = np.concatenate([np.asarray(p, dtype=dtype).reshape(-1, width) for p in parts]) if n else np.zeros((1, width), dtype)
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    with torch.cuda.device(dev):
+        pts = up([np.asarray(r['points'], np.float32)[:, :3] for r in rooms], 3)
+        xyz = up([pcd_roundtrip(np.asarray(r['points'])[:, :3]) for r in rooms], 3)
+        nrm = up([pcd_roundtrip(np.asarray(r['normals'], dtype=np.float64).astype(np.float32)) for r in rooms], 3)
+        ws = torch.empty(max(1, lib.lrg_fpfh_workspace_bytes(n, len(rooms), flags)), dtype=torch.uint8, device=dev)
+        counts = torch.zeros((max(n, 1), 33), dtype=torch.int32, device=dev)
+        k = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        out = torch.zeros((max(n, 1), 33), dtype=torch.float32, device=dev)
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(lib.lrg_fpfh(_ptr(pts), 3, _ptr(xyz), _ptr(nrm), room_start.ctypes.data_as(ctypes.c_void_p), len(rooms),
+                                ctypes.c_float(resolution), ctypes.c_float(radius), flags, _ptr(ws), ws.numel(), _ptr(counts), _ptr(k), _ptr(out),
+                                st), 'lrg_fpfh')
+        status = ctypes.c_int32(0)
+        _lib.check(lib.lrg_fpfh_status(_ptr(ws), n, len(rooms), flags, ctypes.byref(status), st), 'lrg_fpfh_status')
+        if status.value:
+            raise _lib.LrgHipError('lrg_fpfh: ' + '; '.join(v for b, v in _STATUS.items() if status.value & b))
+        out, counts, k = out[:n].cpu().numpy(), counts[:n].cpu().numpy(), k[:n].cpu().numpy()
+    cut = lambda a: [a[room_start[r]:room_start[r + 1]] for r in range(len(rooms))]
+    if return_counts:
+        return cut(out), list(zip(cut(counts), cut(k)))
+    return cut(out)
+
+
 def _certify(lib, dev, rooms, room_start, n, mode, t, resolution, min_cluster_size, pts, normals, curv, ws, st, cat):
     """lrg_baseline_certify with THIS call's mode and thresholds, then LAPACK's normals and curvatures (from room['cov']) for the
     flagged points, written into the rooms' arrays with slack 0.  Returns the device normals / curvatures to segment with, the flags
@@ -187,6 +257,8 @@ def segment(rooms, mode, threshold=None, resolution=0.1, min_cluster_size=10, de
     """Labels of every room in ONE lrg_baseline_segment call.
 
     rooms: list of dicts as ``room_features`` returns them (points; normals / curvatures / rank where the mode reads them).
+    mode: one of ALL_MODES.  'fpfh' (lrg_baseline_segment_fpfh) reads room['fpfh'] ([N, 33] float32) when EVERY room carries it and
+    otherwise computes it with ``fpfh`` at this resolution; rooms from eig='verified' are refused for it (ValueError).
     threshold overrides the mode's first threshold as --threshold does (:119); thresholds=(t1, t2, t3) sets all three.
     Returns a list of int32 label arrays (0 = no cluster), and the per-room cluster counts with return_counts=True.
 
@@ -195,8 +267,8 @@ def segment(rooms, mode, threshold=None, resolution=0.1, min_cluster_size=10, de
     room['curvatures'], slacks set to 0; 'rank' is left alone: no certified pair changes order), so the labels are those of the
     'lapack' route.  return_stats=True appends dict(flagged=[per-room count], flags=[per-room bool array]) to the result, or None
     for rooms without the key, which take the path they always took."""
-    if mode not in _MODE_ID:
-        raise ValueError('unknown baseline mode %r (one of %s)' % (mode, ', '.join(MODES)))
+    if mode not in ALL_MODES:
+        raise ValueError('unknown baseline mode %r (one of %s)' % (mode, ', '.join(ALL_MODES)))
     lib = _lib.load()
     dev = _device(device)
     t = list(thresholds if thresholds is not None else default_thresholds(mode))
@@ -205,6 +277,10 @@ def segment(rooms, mode, threshold=None, resolution=0.1, min_cluster_size=10, de
     if not 1 <= min_cluster_size <= MAX_MIN_CLUSTER_SIZE:
         raise ValueError('min_cluster_size must be in [1, %d]' % MAX_MIN_CLUSTER_SIZE)
     verified = len(rooms) > 0 and all(r.get('normal_slack') is not None for r in rooms)
+    if mode == 'fpfh' and any(r.get('normal_slack') is not None for r in rooms):
+        raise ValueError("mode 'fpfh' does not take rooms from room_features(..., eig='verified'): the certificate bounds how far an edge of "
+                         "the normal and curvature predicates can move under LAPACK's features, and none covers the descriptor, whose bins "
+                         "depend on the normals discontinuously; use eig='lapack'")
     stats = None
     if len(rooms) == 0:
         res = ([], np.zeros(0, np.int32)) if return_counts else ([],)
@@ -223,6 +299,22 @@ def segment(rooms, mode, threshold=None, resolution=0.1, min_cluster_size=10, de
         return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     with torch.cuda.device(dev):
         pts = cat('points', np.float32, 6)
+        if mode == 'fpfh':
+            if any(r.get('fpfh') is None for r in rooms):                    # computed here unless every room brings its own
+                hist = fpfh(rooms, resolution=resolution, device=dev)
+            else:
+                hist = [r['fpfh'] for r in rooms]
+            h = np.concatenate([np.asarray(x, dtype=np.float32).reshape(-1, 33) for x in hist]) if n else np.zeros((1, 33), np.float32)
+            h = torch.from_numpy(np.ascontiguousarray(h)).to(dev)
+            ws = torch.empty(max(1, lib.lrg_baseline_fpfh_workspace_bytes(n, len(rooms), min_cluster_size)), dtype=torch.uint8, device=dev)
+            labels = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+            counts = torch.empty(len(rooms), dtype=torch.int32, device=dev)
+            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(lib.lrg_baseline_segment_fpfh(_ptr(pts), 6, room_start.ctypes.data_as(ctypes.c_void_p), len(rooms), ctypes.c_float(resolution),
+                                                     _ptr(h), t[0], min_cluster_size, _ptr(ws), ws.numel(), _ptr(labels), _ptr(counts), st),
+                       'lrg_baseline_segment_fpfh')
+            return _finish(lib, ws, st, n, rooms, room_start, min_cluster_size, labels, counts, return_counts, return_stats, None,
+                           'lrg_baseline_segment_fpfh')
         normals = cat('normals', np.float64, 3) if need_n else None
         curv = cat('curvatures', np.float64, 1) if need_c else None
         rank = cat('rank', np.int32, 1) if mode == 'smoothness' else None
@@ -241,12 +333,18 @@ def segment(rooms, mode, threshold=None, resolution=0.1, min_cluster_size=10, de
         _lib.check(lib.lrg_baseline_segment(_ptr(pts), 6, room_start.ctypes.data_as(ctypes.c_void_p), len(rooms), ctypes.c_float(resolution),
                                             _MODE_ID[mode], _ptr(normals), _ptr(curv), _ptr(rank), t[0], t[1], t[2], min_cluster_size,
                                             _ptr(ws), ws.numel(), _ptr(labels), _ptr(counts), st), 'lrg_baseline_segment')
-        status = ctypes.c_int32(0)
-        _lib.check(lib.lrg_baseline_status(_ptr(ws), n, len(rooms), min_cluster_size, ctypes.byref(status), st), 'lrg_baseline_status')
-        if status.value:
-            raise _lib.LrgHipError('lrg_baseline_segment: ' + '; '.join(v for b, v in _STATUS.items() if status.value & b))
-        lab = labels[:n].cpu().numpy()
-        cnt = counts.cpu().numpy()
+        return _finish(lib, ws, st, n, rooms, room_start, min_cluster_size, labels, counts, return_counts, return_stats, stats,
+                       'lrg_baseline_segment')
+
+
+def _finish(lib, ws, st, n, rooms, room_start, min_cluster_size, labels, counts, return_counts, return_stats, stats, what):
+    """The status word, then the labels cut into rooms, in the shape ``segment`` returns."""
+    status = ctypes.c_int32(0)
+    _lib.check(lib.lrg_baseline_status(_ptr(ws), n, len(rooms), min_cluster_size, ctypes.byref(status), st), 'lrg_baseline_status')
+    if status.value:
+        raise _lib.LrgHipError(what + ': ' + '; '.join(v for b, v in _STATUS.items() if status.value & b))
+    lab = labels[:n].cpu().numpy()
+    cnt = counts.cpu().numpy()
     out = [lab[room_start[r]:room_start[r + 1]] for r in range(len(rooms))]
     res = (out, cnt) if return_counts else (out,)
     if return_stats:

@@ -15,6 +15,9 @@
 //   scan     exclusive scan of the flags (three launches); per-room ids are differences of the global scan
 //   label    label[i] = scan[key of i's component] - scan[room start] + 1 if kept, else 0; n_clusters per room
 //
+// lrg_baseline_segment_fpfh (benchmarks.py --mode fpfh) puts one launch in front of these: the normalised histograms
+// u [n, 33] in float64, which its edge predicate reads; the descriptor itself is lrg_fpfh.hip's.
+//
 // Features solved on the device (DESIGN §3.8 "verified"): lrg_baseline_eig is prep_jacobi3 on every covariance with a bound on each
 // value's distance from LAPACK's, and lrg_baseline_certify (init, insert, certify, tally) flags both ends of every edge whose
 // predicate could come out differently within those bounds, so that only they go through LAPACK on the host.
@@ -31,7 +34,7 @@
 #define BL_THREADS 256
 #define BL_SCAN_ITEMS 8                       // per thread: 2048 elements per block
 
-enum { BL_NORMAL = 0, BL_CURVATURE = 1, BL_COLOR = 2, BL_FEATURE = 3, BL_SMOOTHNESS = 4, BL_EMBEDDING = 5, BL_LABELS = 6 };   // 5: lrg_baseline_segment_embedding only, 6: lrg_baseline_segment_labels only
+enum { BL_NORMAL = 0, BL_CURVATURE = 1, BL_COLOR = 2, BL_FEATURE = 3, BL_SMOOTHNESS = 4, BL_EMBEDDING = 5, BL_LABELS = 6, BL_FPFH = 7 };   // 5: lrg_baseline_segment_embedding only, 6: lrg_baseline_segment_labels only, 7: lrg_baseline_segment_fpfh only
 // status bits (lrg_baseline_status)
 enum { BL_ST_WINDOW = 1, BL_ST_DUPLICATE = 2, BL_ST_RANK = 4, BL_ST_STACK = 8 };
 
@@ -79,6 +82,7 @@ struct BlArgs {
     const double *normals, *curv; const int32_t *rank;
     const float *emb; int dim;
     const int32_t *cls;
+    double *unit;                                                      // lrg_baseline_segment_fpfh only: [n, 33] normalised histograms
     double t1, t2, t3; int mcs;
     uint64_t *keys; int32_t *vals, *room_of, *parent, *size; unsigned long long *minkey;
     int32_t *ckey, *visited, *flag, *scan, *bsum, *stack, *scal;
@@ -132,6 +136,27 @@ __device__ __forceinline__ bool bl_embedding_edge(const float *emb, int dim, int
     return d > t;
 }
 
+// u[k].dot(u[i]) > t on the normalised histograms (benchmarks.py:359-366), summed in order, every product and sum rounded; a NaN
+// (zero histogram) is no edge.  Symmetric in i and k.
+#define BL_FPFH_DIM 33
+__device__ __forceinline__ bool bl_fpfh_edge(const double *u, int i, int k, double t) {
+    const double *a = u + (long)k * BL_FPFH_DIM, *b = u + (long)i * BL_FPFH_DIM;
+    double d = __dmul_rn(a[0], b[0]);
+    for (int c = 1; c < BL_FPFH_DIM; ++c) d = __dadd_rn(d, __dmul_rn(a[c], b[c]));
+    return d > t;
+}
+
+// unit[i] = double(hist[i]) / sqrt(sum of its squares taken in order); 0 / 0 = NaN for a zero histogram
+__global__ __launch_bounds__(BL_THREADS) void bl_fpfh_unit_kernel(const float *hist, int n, double *unit) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *h = hist + (long)i * BL_FPFH_DIM;
+    double s = 0.0;
+    for (int c = 0; c < BL_FPFH_DIM; ++c) s = __dadd_rn(s, __dmul_rn((double)h[c], (double)h[c]));
+    const double nrm = __dsqrt_rn(s);
+    for (int c = 0; c < BL_FPFH_DIM; ++c) unit[(long)i * BL_FPFH_DIM + c] = __ddiv_rn((double)h[c], nrm);
+}
+
 __device__ __forceinline__ bool bl_edge(const BlArgs &a, int i, int k) {
     switch (a.mode) {
     case BL_NORMAL: case BL_SMOOTHNESS: return bl_normal_edge(a.normals, i, k, a.t1);
@@ -139,6 +164,7 @@ __device__ __forceinline__ bool bl_edge(const BlArgs &a, int i, int k) {
     case BL_COLOR: return bl_color_edge(a.pts, a.ld, i, k, (float)a.t1);
     case BL_EMBEDDING: return bl_embedding_edge(a.emb, a.dim, i, k, a.t1);
     case BL_LABELS: return a.cls[k] == a.cls[i];             // class_labels[voxel_map[kk]] == class_labels[i] (benchmarks.py:305)
+    case BL_FPFH: return bl_fpfh_edge(a.unit, i, k, a.t1);
     default:
         return bl_normal_edge(a.normals, i, k, a.t1) && bl_curv_edge(a.curv, i, k, a.t2) &&
                bl_color_edge(a.pts, a.ld, i, k, (float)a.t3);
@@ -488,8 +514,9 @@ static int bl_setup(const float *pts, int ld, const int32_t *room_start, int n_r
     const int n_points = room_start[n_rooms];
     int rc = bl_layout(n_points, n_rooms, min_cluster_size, &L);
     if (rc) return rc;
-    if (mode < BL_NORMAL || mode > BL_LABELS) return LRG_EINVAL - 72;
+    if (mode < BL_NORMAL || mode > BL_FPFH) return LRG_EINVAL - 72;
     if (mode == BL_EMBEDDING && (!emb || dim < 1 || dim > 64)) return LRG_EINVAL - 74;
+    if (mode == BL_FPFH && (dim != BL_FPFH_DIM || (!emb && n_points > 0))) return LRG_EINVAL - 74;
     if (mode == BL_LABELS && !cls && n_points > 0) return LRG_EINVAL - 74;
     if (!ws || !have_outputs) return LRG_EINVAL - 73;
     if (n_points > 0 && (!pts || ld < 6)) return LRG_EINVAL - 73;
@@ -503,7 +530,7 @@ static int bl_setup(const float *pts, int ld, const int32_t *room_start, int n_r
     int32_t *rooms = reinterpret_cast<int32_t *>(w + L.rooms);     // a device copy of room_start (the caller's is host memory)
     LRG_HIP_CHECK(hipMemcpyAsync(rooms, room_start, (size_t)(n_rooms + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
     a.pts = pts; a.ld = ld; a.room_start = rooms; a.n_rooms = n_rooms; a.n = n_points; a.res = resolution; a.mode = mode;
-    a.normals = normals; a.curv = curvatures; a.rank = rank; a.emb = emb; a.dim = dim; a.cls = cls; a.t1 = t1; a.t2 = t2; a.t3 = t3; a.mcs = min_cluster_size;
+    a.normals = normals; a.curv = curvatures; a.rank = rank; a.emb = emb; a.dim = dim; a.cls = cls; a.unit = nullptr; a.t1 = t1; a.t2 = t2; a.t3 = t3; a.mcs = min_cluster_size;
     a.keys = reinterpret_cast<uint64_t *>(w + L.keys); a.vals = reinterpret_cast<int32_t *>(w + L.vals);
     a.room_of = reinterpret_cast<int32_t *>(w + L.room_of); a.parent = reinterpret_cast<int32_t *>(w + L.parent);
     a.size = reinterpret_cast<int32_t *>(w + L.size); a.minkey = reinterpret_cast<unsigned long long *>(w + L.minkey);
@@ -522,6 +549,8 @@ static inline int bl_init_grid(const LrgBaselineLayout &L, int n_points) {
     return (int)((init_n + BL_THREADS - 1) / BL_THREADS);
 }
 
+static inline size_t bl_fpfh_unit_bytes(int n_points) { return lrg_align_up((size_t)n_points * BL_FPFH_DIM * sizeof(double), 256); }
+
 // lrg_baseline_segment and lrg_baseline_segment_embedding: the same checks and the same nine launches
 static int bl_segment_impl(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode,
                            const double *normals, const double *curvatures, const int32_t *rank, const float *emb, int dim, const int32_t *cls, double t1,
@@ -535,6 +564,12 @@ static int bl_segment_impl(const float *pts, int ld, const int32_t *room_start, 
     if (rc) return rc;
     const int n_points = a.n;
     a.labels = labels; a.n_clusters = n_clusters;
+    if (mode == BL_FPFH) {                                     // the normalised histograms, behind the siblings' workspace
+        if (ws_bytes < L.total + bl_fpfh_unit_bytes(n_points)) return LRG_EINVAL - 75;
+        a.unit = reinterpret_cast<double *>(static_cast<char *>(ws) + L.total);
+        if (n_points > 0)
+            hipLaunchKernelGGL(bl_fpfh_unit_kernel, dim3((n_points + BL_THREADS - 1) / BL_THREADS), dim3(BL_THREADS), 0, st, emb, n_points, a.unit);
+    }
     const int gi = bl_init_grid(L, n_points);
     const int gn = (int)(((long)(n_points > n_rooms ? n_points : n_rooms) + BL_THREADS - 1) / BL_THREADS);
     hipLaunchKernelGGL(bl_init_kernel, dim3(gi), dim3(BL_THREADS), 0, st, a);
@@ -572,6 +607,18 @@ int lrg_baseline_segment_embedding(const float *pts, int ld, const int32_t *room
 int lrg_baseline_segment_labels(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const int32_t *cls,
                                 int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream) {
     return bl_segment_impl(pts, ld, room_start, n_rooms, resolution, BL_LABELS, nullptr, nullptr, nullptr, nullptr, 0, cls, 0.0, 0.0, 0.0,
+                           min_cluster_size, ws, ws_bytes, labels, n_clusters, stream);
+}
+
+size_t lrg_baseline_fpfh_workspace_bytes(int n_points, int n_rooms, int min_cluster_size) {
+    LrgBaselineLayout L;
+    if (bl_layout(n_points, n_rooms, min_cluster_size, &L)) return 0;
+    return L.total + bl_fpfh_unit_bytes(n_points);
+}
+
+int lrg_baseline_segment_fpfh(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const float *hist, double t,
+                              int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream) {
+    return bl_segment_impl(pts, ld, room_start, n_rooms, resolution, BL_FPFH, nullptr, nullptr, nullptr, hist, BL_FPFH_DIM, nullptr, t, 0.0, 0.0,
                            min_cluster_size, ws, ws_bytes, labels, n_clusters, stream);
 }
 
