@@ -389,16 +389,21 @@ def lrgnet_variable_shapes(feature_size=13, lite=0):
     return shapes
 
 
-def lrgnet_checkpoint_tensors(weights, adam_m=None, adam_v=None, step=0, beta1=0.9, beta2=0.999):
-    """Everything ``tf.compat.v1.train.Saver().save`` writes for an LrgNet graph -- which is what ``Saver().restore``
-    (test_region_grow.py:92-93) then asks for: the trainable variables, their Adam slots ``<name>/Adam`` (first moment) and
-    ``<name>/Adam_1`` (second moment), ``beta1_power`` / ``beta2_power`` (learn_region_grow_util.py:188: AdamOptimizer) and
-    ``Variable`` (the global step ``batch``, :187, int32) -- 99 entries for lite 0, the key set of models/lrgnet_model5.ckpt.index.
-    weights / adam_m / adam_v: name -> array in the TF shapes (missing slots: zeros, a freshly built optimizer)."""
+def _saver_tensors(network, shapes, weights, adam_m, adam_v, step, beta1, beta2, no_slots=()):
+    """The layout ``tf.compat.v1.train.Saver().save`` writes for a graph trained by AdamOptimizer: every variable of `shapes` (name ->
+    TF shape; `network` names the graph in the errors), for all but `no_slots` its Adam slots ``<name>/Adam`` (first moment) and
+    ``<name>/Adam_1`` (second moment; missing slots: zeros, a freshly built optimizer), ``beta1_power`` / ``beta2_power`` and
+    ``Variable`` (the global step, int32)."""
     out = {}
-    for k, w in weights.items():
-        w = np.asarray(w, dtype=np.float32)
+    for k, shp in shapes.items():
+        if k not in weights:
+            raise KeyError('%s weight %s missing' % (network, k))
+        w = np.asarray(weights[k], dtype=np.float32)
+        if w.shape != tuple(shp):
+            raise BundleError('%s has shape %s, %s needs %s' % (k, w.shape, network, shp))
         out[k] = w
+        if k in no_slots:
+            continue
         out[k + '/Adam'] = np.asarray(adam_m[k], dtype=np.float32).reshape(w.shape) if adam_m is not None else np.zeros_like(w)
         out[k + '/Adam_1'] = np.asarray(adam_v[k], dtype=np.float32).reshape(w.shape) if adam_v is not None else np.zeros_like(w)
     # TF1's AdamOptimizer creates the two accumulators AT beta (not 1) and multiplies them once per applied step, so a
@@ -408,6 +413,17 @@ def lrgnet_checkpoint_tensors(weights, adam_m=None, adam_v=None, step=0, beta1=0
     out['beta2_power'] = np.float32(float(beta2) ** (int(step) + 1))
     out['Variable'] = np.int32(step)
     return out
+
+
+def lrgnet_checkpoint_tensors(weights, adam_m=None, adam_v=None, step=0, beta1=0.9, beta2=0.999):
+    """Everything ``tf.compat.v1.train.Saver().save`` writes for an LrgNet graph -- which is what ``Saver().restore``
+    (test_region_grow.py:92-93) then asks for: the trainable variables, their Adam slots ``<name>/Adam`` (first moment) and
+    ``<name>/Adam_1`` (second moment), ``beta1_power`` / ``beta2_power`` (learn_region_grow_util.py:188: AdamOptimizer) and
+    ``Variable`` (the global step ``batch``, :187, int32) -- 99 entries for lite 0, the key set of models/lrgnet_model5.ckpt.index.
+    weights / adam_m / adam_v: name -> array in the TF shapes (missing slots: zeros, a freshly built optimizer).  Whatever `weights`
+    holds is written in the shapes it has: nothing is checked against an architecture.  The beta powers are beta ** (step + 1)
+    (_saver_tensors says why)."""
+    return _saver_tensors('LrgNet', {k: np.shape(w) for k, w in weights.items()}, weights, adam_m, adam_v, step, beta1, beta2)
 
 
 def load_lrgnet_weights(prefix, feature_size=13, lite=0, verify=True):
@@ -520,20 +536,7 @@ def pointnet2_checkpoint_tensors(weights, adam_m=None, adam_v=None, step=0, beta
     name -> array in the TF shapes of pointnet2_variable_shapes (the variant and the class count are read from them); adam_m / adam_v:
     the slots (missing: zeros, a freshly built optimizer).  The beta powers follow pointnet_checkpoint_tensors: beta ** (step + 1)."""
     shapes = pointnet2_variable_shapes(*pointnet2_variant({k: np.shape(v) for k, v in weights.items()}))
-    out = {}
-    for k, shp in shapes.items():
-        if k not in weights:
-            raise KeyError('PointNet2 weight %s missing' % k)
-        w = np.asarray(weights[k], dtype=np.float32)
-        if w.shape != tuple(shp):
-            raise BundleError('%s has shape %s, PointNet2 needs %s' % (k, w.shape, shp))
-        out[k] = w
-        out[k + '/Adam'] = np.asarray(adam_m[k], dtype=np.float32).reshape(w.shape) if adam_m is not None else np.zeros_like(w)
-        out[k + '/Adam_1'] = np.asarray(adam_v[k], dtype=np.float32).reshape(w.shape) if adam_v is not None else np.zeros_like(w)
-    out['beta1_power'] = np.float32(float(beta1) ** (int(step) + 1))
-    out['beta2_power'] = np.float32(float(beta2) ** (int(step) + 1))
-    out['Variable'] = np.int32(step)
-    return out
+    return _saver_tensors('PointNet2', shapes, weights, adam_m, adam_v, step, beta1, beta2)
 
 
 POINTNET_NUM_POINT = 1024                                           # the row positions of a cell: the batch-norm tables' first axis
@@ -676,19 +679,4 @@ def pointnet_checkpoint_tensors(weights, adam_m=None, adam_v=None, step=0, beta1
     while pointnet_bn_names(j)[2] in shapes:
         averages.update(pointnet_bn_names(j)[2:])
         j += 1
-    out = {}
-    for k, shp in shapes.items():
-        if k not in weights:
-            raise KeyError('PointNet weight %s missing' % k)
-        w = np.asarray(weights[k], dtype=np.float32)
-        if w.shape != tuple(shp):
-            raise BundleError('%s has shape %s, PointNet needs %s' % (k, w.shape, shp))
-        out[k] = w
-        if k in averages:
-            continue
-        out[k + '/Adam'] = np.asarray(adam_m[k], dtype=np.float32).reshape(w.shape) if adam_m is not None else np.zeros_like(w)
-        out[k + '/Adam_1'] = np.asarray(adam_v[k], dtype=np.float32).reshape(w.shape) if adam_v is not None else np.zeros_like(w)
-    out['beta1_power'] = np.float32(float(beta1) ** (int(step) + 1))
-    out['beta2_power'] = np.float32(float(beta2) ** (int(step) + 1))
-    out['Variable'] = np.int32(step)
-    return out
+    return _saver_tensors('PointNet', shapes, weights, adam_m, adam_v, step, beta1, beta2, no_slots=averages)

@@ -18,7 +18,8 @@ points, as the reference sequences it from Python; torch owns the buffers and co
   update     ``lrg_adam_step`` at the constant rate 0.001 (:210).
 
 The gradient of l1_points .. l3_points has two contributors, added in this order: the skip connection of its propagation level
-(written by the product), then the next level's grouping (the scatter's addend).  DESIGN.md §3.14.  There is no CPU fallback.
+(written by the product), then the next level's grouping (the scatter's addend).  The flat parameter buffer, the Adam step, the staging of a batch, ``evaluate``, the checkpoint and the two ordered reductions over
+the rows (``_dW``, ``_colsum`` over this trainer's own plan) are adam_trainer.py's.  DESIGN.md §3.14.  There is no CPU fallback.
 """
 import ctypes
 from math import gcd
@@ -27,11 +28,11 @@ import numpy as np
 import torch
 
 from . import _lib, checkpoint
+from .adam_trainer import CellClassifierTrainer, variance_scaling_uniform
 from .checkpoint import POINTNET2_FP_MLPS as FP_MLPS, POINTNET2_SA_MLPS as SA_MLPS, pointnet2_variable_shapes
 from .pointnet2 import NSAMPLE, NUM_POINT, SA_LEVELS, _device, _ptr, _stream
 
 LEARNING_RATE = 0.001            # train_pointnet.py:210
-DW_WORKGROUPS = 2048             # a weight gradient's reduction over the rows is cut until about this many workgroups share it
 GEMM_ROWS = 65535 * 64           # lrg_gemm_f32: rows of one launch (64-row tiles on the grid's y axis)
 POOL_GROUPS = 65535              # lrg_pool_backward: groups of one launch
 
@@ -45,9 +46,7 @@ def initial_weights(num_class=13, rgb_features=True, seed=0):
     w = {}
     for name, shp in pointnet2_variable_shapes(num_class, rgb_features).items():
         if 'kernel' in name:
-            field = int(np.prod(shp[:-2]))
-            lim = np.sqrt(6.0 / (field * shp[-2] + field * shp[-1]))
-            w[name] = rs.uniform(-lim, lim, shp).astype(np.float32)
+            w[name] = variance_scaling_uniform(rs, shp)
         else:
             w[name] = np.zeros(shp, np.float32)
     return w
@@ -57,7 +56,25 @@ def _widths(mlp):
     return np.array(mlp, dtype=np.int32)
 
 
-class PointNet2Trainer:
+def _colsum_plan(R):
+    """[(segments, rows a segment)] of the stages that reduce R rows to one: segments of gcd(rows, 256) rows (doubled while a
+    stage would have more than 65535 segments), until what is left has no such factor and is added in one stage."""
+    plan = []
+    while R > 1:
+        s = gcd(R, 256)
+        while R // s > 65535 and R % (2 * s) == 0:
+            s *= 2
+        if s == 1 or R // s > 65535:
+            s = R
+        plan.append((R // s, s))
+        R //= s
+    return plan or [(1, 1)]
+
+
+class PointNet2Trainer(CellClassifierTrainer):
+    network = 'PointNet2'
+    checkpoint_tensors = staticmethod(checkpoint.pointnet2_checkpoint_tensors)
+
     def __init__(self, batch_size, num_class=13, rgb_features=True, device=None, learning_rate=LEARNING_RATE, beta1=0.9, beta2=0.999,
                  epsilon=1e-8):
         if batch_size < 1:
@@ -72,9 +89,6 @@ class PointNet2Trainer:
         self.lr, self.b1, self.b2, self.eps = learning_rate, beta1, beta2, epsilon
         self.npts = [NUM_POINT] + [m for m, _ in SA_LEVELS]                       # points of l0 .. l4
         self.feat = [3 if self.rgb_features else 0] + [m[-1] for m in SA_MLPS]    # feature widths of l0 .. l4
-        self.step = 0
-        self.flat = None
-        self._eval_net = None
 
     # ---- variables ----
     def init_weights(self, seed=0):
@@ -83,31 +97,13 @@ class PointNet2Trainer:
 
     def load_weights(self, weights):
         """weights: name -> array in the TF shapes of checkpoint.pointnet2_variable_shapes.  Resets the optimiser (slots zero, step 0)."""
-        for k, shp in self.shapes.items():
-            if k not in weights:
-                raise KeyError('PointNet2 weight %s missing' % k)
-            if tuple(np.shape(weights[k])) != tuple(shp):
-                raise ValueError('%s has shape %s, PointNet2 needs %s' % (k, np.shape(weights[k]), shp))
-        dev, B = self.dev, self.B
-        sizes = [int(np.prod(self.shapes[k])) for k in self.names]
-        self.offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        with torch.cuda.device(dev):
-            host = np.concatenate([np.asarray(weights[k], np.float32).reshape(-1) for k in self.names])
-            self.flat = torch.from_numpy(host).to(dev)
-            self.gflat = torch.zeros_like(self.flat)
-            self.m = torch.zeros_like(self.flat)
-            self.v = torch.zeros_like(self.flat)
-            self.views, self.gviews = {}, {}
-            for k, o, n in zip(self.names, self.offs[:-1], sizes):
-                shp = self.shapes[k]
-                shp2 = (shp[-1],) if len(shp) == 1 else (shp[-2], shp[-1])                       # kernels as [cin, cout]
-                self.views[k] = self.flat[o:o + n].view(shp2)
-                self.gviews[k] = self.gflat[o:o + n].view(shp2)
+        self._check_weights(weights)
+        with torch.cuda.device(self.dev):
+            self._bind(weights)
             if self.flat.data_ptr() % 16:
                 raise _lib.LrgHipError('the parameter buffer is not 16-byte aligned')
             self._allocate()
             torch.cuda.current_stream().synchronize()
-        self.step = 0
         self._eval_net = None
         self._packed_step = -1
         return self
@@ -171,7 +167,7 @@ class PointNet2Trainer:
         for (scope, ids, cin, mlp), R in zip(self._mlps(), self._mlp_rows()):
             for k, n in zip([cin] + list(mlp[:-1]), mlp):
                 dw.append(self._dw_planes(k, n, R)[1] * k * n)
-                cs.append(self._colsum_plan(R)[0][0] * n)
+                cs.append(_colsum_plan(R)[0][0] * n)
         self._dw_part = torch.empty(max(dw), **f32)
         self._cs_part = [torch.empty(max(cs), **f32) for _ in range(2)]
         self._stats = torch.zeros(3, dtype=torch.float64, device=dev)
@@ -180,30 +176,6 @@ class PointNet2Trainer:
         B = self.B
         return [B * self.npts[lv + 1] * NSAMPLE for lv in range(4)] + [B * self.npts[3 - lv] for lv in range(4)] + [B * NUM_POINT]
 
-    def _tf(self, views):
-        return {k: views[k].cpu().numpy().reshape(self.shapes[k]) for k in self.names}
-
-    def weights_numpy(self):
-        """name -> array in the TF shapes (what PointNet2HIP and write_bundle take)."""
-        return self._tf(self.views)
-
-    def grads_numpy(self):
-        return self._tf(self.gviews)
-
-    def slots_numpy(self):
-        """(m, v): Adam's slots of the trainables in the TF shapes."""
-        def cut(buf):
-            return {k: buf[o:o + self.views[k].numel()].cpu().numpy().reshape(self.shapes[k]) for k, o in zip(self.names, self.offs[:-1])}
-        return cut(self.m), cut(self.v)
-
-    def checkpoint_numpy(self):
-        """Everything the reference's ``Saver`` (:367, :438) stores: checkpoint.pointnet2_checkpoint_tensors."""
-        m, v = self.slots_numpy()
-        return checkpoint.pointnet2_checkpoint_tensors(self.weights_numpy(), m, v, self.step, self.b1, self.b2)
-
-    def save(self, prefix):
-        checkpoint.write_bundle(prefix, self.checkpoint_numpy())
-
     def level_indices(self):
         """The index computations of the last forward as NumPy: dict(sa=[4 x dict(fps [B,m], idx [B,m,32])],
         fp=[4 x dict(nn_idx [B,n,3], weight [B,n,3])]), levels in forward order (fa_layer1 first)."""
@@ -211,9 +183,6 @@ class PointNet2Trainer:
                     fp=[dict(nn_idx=self._nn[lv].cpu().numpy(), weight=self._nnw[lv].cpu().numpy()) for lv in range(4)])
 
     # ---- kernels ----
-    def _check(self, rc, what):
-        _lib.check(rc, what)
-
     def _gemm(self, M, N, K, A, lda, B, ldb, C, ldc, mask=None):
         """C[M,N] = A[M,K] B[N,K]^T (dX = dZ W^T), zero where mask <= 0; launches of at most GEMM_ROWS rows."""
         at = lambda t, floats: ctypes.c_void_p(t.data_ptr() + 4 * floats)
@@ -221,45 +190,6 @@ class PointNet2Trainer:
             rows = min(GEMM_ROWS, M - r0)
             self._check(self.lib.lrg_gemm_f32(rows, N, K, at(A, r0 * lda), lda, 0, _ptr(B), ldb, 1, at(C, r0 * ldc), ldc, None,
                                               at(mask, r0 * ldc) if mask is not None else None, 1, _stream()), 'lrg_gemm_f32')
-
-    def _dw_planes(self, K, N, R):
-        """Into how many slices the R rows of a [K, N] weight gradient are cut: enough for about DW_WORKGROUPS workgroups of 64 x 64
-        tiles, never under 256 rows a slice.  A function of the shapes alone, so a step always adds in the same order."""
-        tiles = -(-K // 64) * -(-N // 64)
-        split = max(1, min(R // 256, -(-DW_WORKGROUPS // tiles)))
-        return split, self.lib.lrg_gemm_f32_planes_count(R, split)
-
-    def _dW(self, X, dZ, K, N, R, out):
-        """out[K,N] = X[R,K]^T dZ[R,N]: the rows cut into slices whose partial products are stored side by side
-        (lrg_gemm_f32_planes) and then added in ascending order (lrg_segment_colsum); nothing is added atomically."""
-        split, planes = self._dw_planes(K, N, R)
-        self._check(self.lib.lrg_gemm_f32_planes(K, N, R, _ptr(X), K, 1, _ptr(dZ), N, 0, _ptr(self._dw_part), split, _stream()),
-                    'lrg_gemm_f32_planes')
-        self._check(self.lib.lrg_segment_colsum(_ptr(self._dw_part), 1, planes, K * N, _ptr(out), _stream()), 'lrg_segment_colsum')
-
-    @staticmethod
-    def _colsum_plan(R):
-        """[(segments, rows a segment)] of the stages that reduce R rows to one: segments of gcd(rows, 256) rows (doubled while a
-        stage would have more than 65535 segments), until what is left has no such factor and is added in one stage."""
-        plan = []
-        while R > 1:
-            s = gcd(R, 256)
-            while R // s > 65535 and R % (2 * s) == 0:
-                s *= 2
-            if s == 1 or R // s > 65535:
-                s = R
-            plan.append((R // s, s))
-            R //= s
-        return plan or [(1, 1)]
-
-    def _colsum(self, x, R, N, out):
-        """out[N] = the column sums of x[R,N] in the stages of _colsum_plan, each in ascending row order."""
-        plan = self._colsum_plan(R)
-        src = x
-        for i, (segs, rows) in enumerate(plan):
-            dst = out if i == len(plan) - 1 else self._cs_part[i & 1]
-            self._check(self.lib.lrg_segment_colsum(_ptr(src), segs, rows, N, _ptr(dst), _stream()), 'lrg_segment_colsum')
-            src = dst
 
     def _scatter(self, n, q, per, c, grad, ldg, col0, idx, weight, drop, addend, mask, out):
         self._check(self.lib.lrg_pointnet2_scatter_grad(self.B, n, q, per, c, _ptr(grad), ldg, col0, _ptr(idx), _ptr(weight), drop, _ptr(addend),
@@ -276,23 +206,6 @@ class PointNet2Trainer:
                                                               _ptr(packed[off:]), _stream()), 'lrg_pointnet2_pack_layer')
                 off += size
         self._packed_step = self.step
-
-    def _upload(self, points, labels):
-        points = np.ascontiguousarray(points, dtype=np.float32)
-        if points.shape != (self.B, NUM_POINT, 6):
-            raise ValueError('points must be [%d, %d, 6]' % (self.B, NUM_POINT))
-        labels = np.asarray(labels)
-        if labels.shape != (self.B, NUM_POINT):
-            raise ValueError('labels must be [%d, %d]' % (self.B, NUM_POINT))
-        self._x.copy_(torch.from_numpy(points))
-        self._labels.copy_(torch.from_numpy(np.ascontiguousarray(labels.astype(np.int32))).view(-1))
-
-    def _scalars(self):
-        s = self._stats.cpu().numpy()
-        if s[2]:
-            raise ValueError('%d labels are outside [0, %d)' % (int(s[2]), self.num_class))
-        R = self.B * NUM_POINT
-        return dict(loss=float(s[0] / R), acc=float(s[1] / R))
 
     def _forward(self, mark):
         lib, B, st = self.lib, self.B, _stream()
@@ -359,10 +272,10 @@ class PointNet2Trainer:
             # ---- the head (:193-202) ----
             fp4 = self._fp_out[3].view(R0, 128)
             self._dW(self._fc1, self._dlogits, 128, ncls, R0, G['kernel2'])
-            self._colsum(self._dlogits, R0, ncls, G['bias2'])
+            self._colsum(self._dlogits, ncls, G['bias2'], _colsum_plan(R0))
             self._gemm(R0, 128, ncls, self._dlogits, ncls, V['kernel2'], ncls, cur, 128, mask=self._fc1)
             self._dW(fp4, cur, 128, 128, R0, G['kernel1'])
-            self._colsum(cur, R0, 128, G['bias1'])
+            self._colsum(cur, 128, G['bias1'], _colsum_plan(R0))
             self._gemm(R0, 128, 128, cur, 128, V['kernel1'], 128, nxt, 128, mask=fp4)
             cur, nxt = nxt, cur
             mark('head_backward')
@@ -374,7 +287,7 @@ class PointNet2Trainer:
                 for i in range(len(mlp) - 1, 0, -1):
                     X, k = self._fp_keep[lv][i - 1], mlp[i - 1]
                     self._dW(X, cur, k, mlp[i], R, G['%skernel%d' % (scope, i)])
-                    self._colsum(cur, R, mlp[i], G['%sbias%d' % (scope, i)])
+                    self._colsum(cur, mlp[i], G['%sbias%d' % (scope, i)], _colsum_plan(R))
                     self._gemm(R, k, mlp[i], cur, mlp[i], V['%skernel%d' % (scope, i)], mlp[i], nxt, k, mask=X)
                     cur, nxt = nxt, cur
                 c_up, c_skip, w0 = self._interp[lv].shape[2], self.feat[dst], mlp[0]
@@ -382,7 +295,7 @@ class PointNet2Trainer:
                 self._dW(self._interp[lv], cur, c_up, w0, R, G0[:c_up])
                 if c_skip:
                     self._dW(self._feat[dst], cur, c_skip, w0, R, G0[c_up:])
-                self._colsum(cur, R, w0, G[scope + 'bias0'])
+                self._colsum(cur, w0, G[scope + 'bias0'], _colsum_plan(R))
                 if dst >= 1:                                                   # the skip's block: the first contributor of l<dst>_points
                     self._gemm(R, c_skip, w0, cur, w0, W0[c_up:], w0, self._dfeat[dst].view(-1), c_skip)
                 self._gemm(R, c_up, w0, cur, w0, W0, w0, nxt, c_up)            # the interpolated block
@@ -404,11 +317,11 @@ class PointNet2Trainer:
                                                       _ptr(cur[g0 * NSAMPLE * w3:]), st), 'lrg_pool_backward')
                 for i, (X, k, wd) in ((2, (keep[1], w2, w3)), (1, (keep[0], w1, w2))):
                     self._dW(X, cur, k, wd, R, G['%skernel%d' % (scope, i)])
-                    self._colsum(cur, R, wd, G['%sbias%d' % (scope, i)])
+                    self._colsum(cur, wd, G['%sbias%d' % (scope, i)], _colsum_plan(R))
                     self._gemm(R, k, wd, cur, wd, V['%skernel%d' % (scope, i)], wd, nxt, k, mask=X)
                     cur, nxt = nxt, cur
                 self._dW(self._sa_rows[lv], cur, k0, w1, R, G[scope + 'kernel0'])
-                self._colsum(cur, R, w1, G[scope + 'bias0'])
+                self._colsum(cur, w1, G[scope + 'bias0'], _colsum_plan(R))
                 mark('sa_backward')
                 if lv >= 1:                                                    # layer1's inputs are data
                     self._gemm(R, k0, w1, cur, w1, V[scope + 'kernel0'], w1, nxt, k0)
@@ -420,15 +333,10 @@ class PointNet2Trainer:
     def train_step(self, points, labels, mark=None):
         """``sess.run([net.class_acc, net.class_loss, net.train_op], feed)`` (:408) -> dict(loss, acc)."""
         sc = self.backward(points, labels, mark=mark)
-        t = self.step + 1
-        lr_t = self.lr * np.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
         with torch.cuda.device(self.dev):
-            self._check(self.lib.lrg_adam_step(_ptr(self.flat), _ptr(self.gflat), _ptr(self.m), _ptr(self.v), self.flat.numel(), ctypes.c_float(lr_t),
-                                               ctypes.c_float(self.b1), ctypes.c_float(self.b2), ctypes.c_float(self.eps), _stream()),
-                        'lrg_adam_step')
+            self._adam_update(self.lr)
             if mark:
                 mark('update')
-        self.step += 1
         self._eval_net = None
         return sc
 
@@ -436,29 +344,6 @@ class PointNet2Trainer:
         """The logits [B,1024,num_class] (a device tensor) of the last backward / train_step's forward."""
         return self._logits.view(self.B, NUM_POINT, self.num_class)
 
-    def eval_logits(self, points):
-        """The logits [b,1024,num_class] (a device tensor) of the validation loop (:432): PointNet2HIP on the trainer's current
-        weights, built once per update.  Any number of cells, all in one pass."""
+    def _inference_net(self):
         from .pointnet2 import PointNet2HIP
-        if self._eval_net is None:
-            self._eval_net = PointNet2HIP(self.weights_numpy(), device=self.dev)
-        points = np.ascontiguousarray(points, dtype=np.float32)
-        with torch.cuda.device(self.dev):
-            return self._eval_net._forward(torch.from_numpy(points).to(self.dev))
-
-    def evaluate(self, points, labels):
-        """dict(loss, acc) of a batch in the validation loop (:419-436)."""
-        labels = np.ascontiguousarray(np.asarray(labels).astype(np.int32)).reshape(-1)
-        with torch.cuda.device(self.dev):
-            out = self.eval_logits(points)
-            rows = out.shape[0] * NUM_POINT
-            if labels.size != rows:
-                raise ValueError('labels must be [%d, %d]' % (out.shape[0], NUM_POINT))
-            lab = torch.from_numpy(labels).to(self.dev)
-            stats = torch.zeros(3, dtype=torch.float64, device=self.dev)
-            self._check(self.lib.lrg_pointnet_softmax_ce_grad(_ptr(out), _ptr(lab), rows, self.num_class, None, _ptr(stats), _stream()),
-                        'lrg_pointnet_softmax_ce_grad')
-            s = stats.cpu().numpy()
-        if s[2]:
-            raise ValueError('%d labels are outside [0, %d)' % (int(s[2]), self.num_class))
-        return dict(loss=float(s[0] / rows), acc=float(s[1] / rows))
+        return PointNet2HIP(self.weights_numpy(), device=self.dev)

@@ -16,7 +16,8 @@ points, as the reference sequences it from Python; torch owns the buffers and co
   update     ``lrg_pointnet_ema_update`` on the moving averages (:71-78), ``lrg_adam_step`` at the scheduled rate (:109-110).
 
 ``stage_cells`` and ``jitter`` are :327-350 and :235-246 on the host in NumPy with the script's own draws in the script's own order.
-DESIGN.md §3.13.  There is no CPU fallback.
+The flat parameter buffer, the Adam step, the staging of a batch, ``evaluate``, the checkpoint and the two ordered reductions over
+the rows (``_dW``, ``_colsum`` over this trainer's own plan) are adam_trainer.py's.  DESIGN.md §3.13.  There is no CPU fallback.
 """
 import ctypes
 
@@ -24,12 +25,12 @@ import numpy as np
 import torch
 
 from . import _lib, checkpoint
+from .adam_trainer import CellClassifierTrainer, variance_scaling_uniform
 from .checkpoint import POINTNET_NUM_POINT as NUM_POINT, pointnet_bn_names, pointnet_variable_shapes, pointnet_variant
 from .pointnet2 import _device, _ptr, _stream
 
 ARCHITECTURES = {'today': ((64, 64, 64, 128, 1024), (512, 256)),          # NUM_FEATURE_CHANNELS, NUM_FC_CHANNELS of train_pointnet.py:20-22
                  'shipped': ((64, 64, 128, 512), (512,))}                  # models/pointnet_model5.ckpt.index
-DW_WORKGROUPS = 2048             # a weight gradient's reduction over the rows is cut until about this many workgroups share it
 
 
 def learning_rate(step, base=2e-4, decay_steps=500, decay_rate=0.5):
@@ -96,9 +97,7 @@ def initial_weights(conv_widths, fc_widths, num_class, seed=0):
     w = {}
     for name, shp in pointnet_variable_shapes(conv_widths, fc_widths, num_class).items():
         if name.startswith('kernel') or name.startswith('fc_weights'):
-            field = int(np.prod(shp[:-2]))
-            lim = np.sqrt(6.0 / (field * shp[-2] + field * shp[-1]))
-            w[name] = rs.uniform(-lim, lim, shp).astype(np.float32)
+            w[name] = variance_scaling_uniform(rs, shp)
         elif name.endswith('gamma'):
             w[name] = np.ones(shp, np.float32)
         else:
@@ -106,7 +105,10 @@ def initial_weights(conv_widths, fc_widths, num_class, seed=0):
     return w
 
 
-class PointNetTrainer:
+class PointNetTrainer(CellClassifierTrainer):
+    network = 'PointNet'
+    checkpoint_tensors = staticmethod(checkpoint.pointnet_checkpoint_tensors)
+
     def __init__(self, batch_size, conv_widths=ARCHITECTURES['today'][0], fc_widths=ARCHITECTURES['today'][1], num_class=13, device=None,
                  base_learning_rate=2e-4, decay_steps=500, decay_rate=0.5, beta1=0.9, beta2=0.999, epsilon=1e-8, ema_decay=0.9):
         self.conv, self.fc, self.num_class = tuple(int(c) for c in conv_widths), tuple(int(c) for c in fc_widths), int(num_class)
@@ -123,9 +125,7 @@ class PointNetTrainer:
         self.base_lr, self.decay_steps, self.decay_rate = base_learning_rate, decay_steps, decay_rate
         self.b1, self.b2, self.eps, self.ema_decay = beta1, beta2, epsilon, ema_decay
         self.names = trainable_names(self.conv, self.fc)
-        self.step = 0
-        self.flat = None
-        self._eval_net = None
+        self._plan = [(self.B, NUM_POINT), (1, self.B)]          # a column sum: per cell, then over the cells (one row at B = 1)
 
     # ---- variables ----
     def init_weights(self, seed=0):
@@ -135,28 +135,11 @@ class PointNetTrainer:
     def load_weights(self, weights):
         """weights: name -> array in the TF shapes under the names of checkpoint.pointnet_variable_shapes (the moving averages
         included).  Resets the optimiser (slots zero, step 0)."""
-        for k, shp in self.shapes.items():
-            if k not in weights:
-                raise KeyError('PointNet weight %s missing' % k)
-            if tuple(np.shape(weights[k])) != tuple(shp):
-                raise ValueError('%s has shape %s, PointNet needs %s' % (k, np.shape(weights[k]), shp))
+        self._check_weights(weights)
         dev, B, R = self.dev, self.B, self.B * NUM_POINT
-        sizes = [int(np.prod(self.shapes[k])) for k in self.names]
-        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        self.offs = offs
         ema_names = [n for j in range(len(self.fc)) for n in pointnet_bn_names(j)[2:]]
         with torch.cuda.device(dev):
-            host = np.concatenate([np.asarray(weights[k], np.float32).reshape(-1) for k in self.names])
-            self.flat = torch.from_numpy(host).to(dev)
-            self.gflat = torch.zeros_like(self.flat)
-            self.m = torch.zeros_like(self.flat)
-            self.v = torch.zeros_like(self.flat)
-            self.views, self.gviews = {}, {}
-            for k, o, n in zip(self.names, offs[:-1], sizes):
-                shp = self.shapes[k]
-                shp2 = (shp[-1],) if len(shp) == 1 else (int(np.prod(shp[:-1])), shp[-1])          # kernels as [cin, cout]
-                self.views[k] = self.flat[o:o + n].view(shp2)
-                self.gviews[k] = self.gflat[o:o + n].view(shp2)
+            self._bind(weights)
             # moving averages and the batch's moments: per block j mean [1024, c] then variance [1024, c], in both buffers
             self.ema = torch.from_numpy(np.concatenate([np.asarray(weights[k], np.float32).reshape(-1) for k in ema_names])).to(dev)
             self.moments = torch.zeros_like(self.ema)
@@ -181,53 +164,29 @@ class PointNetTrainer:
             wmax = max(self.conv + self.fc)
             self._dz = [torch.empty(R * wmax, **f32) for _ in range(2)]
             self._dskip = torch.empty((R, self.conv[1]), **f32)
-            self._tmp = torch.empty(B * max(wmax, self.num_class), **f32)
+            self._cs_part = [torch.empty(B * max(wmax, self.num_class), **f32)]
             dw = [(6 if i == 0 else self.conv[i - 1], c) for i, c in enumerate(self.conv)]
             dw += [(self.conv[-1], self.fc[0]), (self.conv[1], self.fc[0])]
             dw += [(k, n) for k, n in zip(self.fc, self.fc[1:] + (self.num_class,))]
-            self._dw_part = torch.empty(max(self._dw_planes(k, n)[1] * k * n for k, n in dw), **f32)
+            self._dw_part = torch.empty(max(self._dw_planes(k, n, R)[1] * k * n for k, n in dw), **f32)
             self._bn_ws_bytes = self.lib.lrg_pointnet_bn_backward_workspace_bytes(max(self.fc))
             self._bn_ws = torch.empty(self._bn_ws_bytes // 4, **f32)
             self._stats = torch.zeros(3, dtype=torch.float64, device=dev)
             torch.cuda.current_stream().synchronize()
-        self.step = 0
         self._eval_net = None
         return self
 
-    def _tf(self, views, names):
-        return {k: views[k].cpu().numpy().reshape(self.shapes[k]) for k in names}
-
     def weights_numpy(self):
         """name -> array in the TF shapes: the trainables and the moving averages (what PointNetHIP and write_bundle take)."""
-        out = self._tf(self.views, self.names)
+        out = self._tf(self.views)
         out.update(self._tf(self.ema_views, list(self.ema_views)))
         return out
-
-    def grads_numpy(self):
-        return self._tf(self.gviews, self.names)
 
     def moments_numpy(self):
         """The last training batch's moments under the moving averages' names."""
         return self._tf(self.moment_views, list(self.moment_views))
 
-    def slots_numpy(self):
-        """(m, v): Adam's slots of the trainables in the TF shapes."""
-        def cut(buf):
-            return {k: buf[o:o + self.views[k].numel()].cpu().numpy().reshape(self.shapes[k]) for k, o in zip(self.names, self.offs[:-1])}
-        return cut(self.m), cut(self.v)
-
-    def checkpoint_numpy(self):
-        """Everything the reference's ``Saver`` (:367, :438) stores: checkpoint.pointnet_checkpoint_tensors."""
-        m, v = self.slots_numpy()
-        return checkpoint.pointnet_checkpoint_tensors(self.weights_numpy(), m, v, self.step, self.b1, self.b2)
-
-    def save(self, prefix):
-        checkpoint.write_bundle(prefix, self.checkpoint_numpy())
-
     # ---- kernels ----
-    def _check(self, rc, what):
-        _lib.check(rc, what)
-
     def _gemm(self, M, N, K, A, lda, tA, B, ldb, tB, C, ldc, addend=None, mask=None):
         self._check(self.lib.lrg_gemm_f32(M, N, K, _ptr(A), lda, tA, _ptr(B), ldb, tB, _ptr(C), ldc, _ptr(addend), _ptr(mask), 1, _stream()),
                     'lrg_gemm_f32')
@@ -235,44 +194,6 @@ class PointNetTrainer:
     def _layer(self, x, cin, w, ldw, bias, y, cout, relu):
         self._check(self.lib.lrg_pointwise_layer(_ptr(x), cin, _ptr(w), ldw, _ptr(bias), _ptr(y), self.B * NUM_POINT, cin, cout, relu, 0, 0, None,
                                                  0, _stream()), 'lrg_pointwise_layer')
-
-    def _dw_planes(self, K, N):
-        """Into how many slices the B * 1024 rows of a [K, N] weight gradient are cut: enough for about DW_WORKGROUPS workgroups
-        of 64 x 64 tiles, never under 256 rows a slice.  A function of the shapes alone, so a step always adds in the same order."""
-        tiles = -(-K // 64) * -(-N // 64)
-        split = max(1, min(self.B * NUM_POINT // 256, -(-DW_WORKGROUPS // tiles)))
-        return split, self.lib.lrg_gemm_f32_planes_count(self.B * NUM_POINT, split)
-
-    def _dW(self, X, dZ, K, N, out):
-        """out[K,N] = X[R,K]^T dZ[R,N]: the rows cut into slices whose partial products are stored side by side
-        (lrg_gemm_f32_planes) and then added in ascending order (lrg_segment_colsum); nothing is added atomically."""
-        split, planes = self._dw_planes(K, N)
-        self._check(self.lib.lrg_gemm_f32_planes(K, N, self.B * NUM_POINT, _ptr(X), K, 1, _ptr(dZ), N, 0, _ptr(self._dw_part), split, _stream()),
-                    'lrg_gemm_f32_planes')
-        self._check(self.lib.lrg_segment_colsum(_ptr(self._dw_part), 1, planes, K * N, _ptr(out), _stream()), 'lrg_segment_colsum')
-
-    def _colsum(self, x, N, out):
-        """out[N] = the column sums of x[R,N]: per cell, then over the cells, both in ascending order."""
-        part = self._tmp[:self.B * N]
-        self._check(self.lib.lrg_segment_colsum(_ptr(x), self.B, NUM_POINT, N, _ptr(part), _stream()), 'lrg_segment_colsum')
-        self._check(self.lib.lrg_segment_colsum(_ptr(part), 1, self.B, N, _ptr(out), _stream()), 'lrg_segment_colsum')
-
-    def _upload(self, points, labels):
-        points = np.ascontiguousarray(points, dtype=np.float32)
-        if points.shape != (self.B, NUM_POINT, 6):
-            raise ValueError('points must be [%d, %d, 6]' % (self.B, NUM_POINT))
-        labels = np.asarray(labels)
-        if labels.shape != (self.B, NUM_POINT):
-            raise ValueError('labels must be [%d, %d]' % (self.B, NUM_POINT))
-        self._x.copy_(torch.from_numpy(points).view(-1, 6))
-        self._labels.copy_(torch.from_numpy(np.ascontiguousarray(labels.astype(np.int32))).view(-1))
-
-    def _scalars(self):
-        s = self._stats.cpu().numpy()
-        if s[2]:
-            raise ValueError('%d labels are outside [0, %d)' % (int(s[2]), self.num_class))
-        R = self.B * NUM_POINT
-        return dict(loss=float(s[0] / R), acc=float(s[1] / R))
 
     # ---- one step ----
     def backward(self, points, labels, loss_only=False, mark=None):
@@ -318,23 +239,23 @@ class PointNetTrainer:
                 return self._scalars()
             # ---- the fc stack backwards ----
             cur, nxt = self._dz
-            self._dW(self._y[-1], self._dlogits, fc[-1], ncls, G['fc_weights%d' % nf])
-            self._colsum(self._dlogits, ncls, G['fc_bias%d' % nf])
+            self._dW(self._y[-1], self._dlogits, fc[-1], ncls, R, G['fc_weights%d' % nf])
+            self._colsum(self._dlogits, ncls, G['fc_bias%d' % nf], self._plan)
             self._gemm(R, fc[-1], ncls, self._dlogits, ncls, 0, V['fc_weights%d' % nf], ncls, 1, cur, fc[-1])
             for j in range(nf - 1, -1, -1):
                 beta, gamma, mean, var = pointnet_bn_names(j)
                 self._check(lib.lrg_pointnet_bn_backward(_ptr(self._z[j]), _ptr(self._y[j]), _ptr(cur), _ptr(self.moment_views[mean]),
                                                          _ptr(self.moment_views[var]), _ptr(V[gamma]), B, fc[j], _ptr(cur), _ptr(G[gamma]),
                                                          _ptr(G[beta]), _ptr(self._bn_ws), self._bn_ws_bytes, st), 'lrg_pointnet_bn_backward')
-                self._colsum(cur, fc[j], G['fc_bias%d' % j])
+                self._colsum(cur, fc[j], G['fc_bias%d' % j], self._plan)
                 if j > 0:
-                    self._dW(self._y[j - 1], cur, fc[j - 1], fc[j], G['fc_weights%d' % j])
+                    self._dW(self._y[j - 1], cur, fc[j - 1], fc[j], R, G['fc_weights%d' % j])
                     self._gemm(R, fc[j - 1], fc[j], cur, fc[j], 0, V['fc_weights%d' % j], fc[j], 1, nxt, fc[j - 1])
                     cur, nxt = nxt, cur
             # the first fc layer in its two blocks: rows [:c_last] read t, rows [c_last:] read conv[1]
             g0 = G['fc_weights0']
-            self._dW(self._t, cur, c_last, fc[0], g0[:c_last])
-            self._dW(skip, cur, c_skip, fc[0], g0[c_last:])
+            self._dW(self._t, cur, c_last, fc[0], R, g0[:c_last])
+            self._dW(skip, cur, c_skip, fc[0], R, g0[c_last:])
             self._gemm(R, c_skip, fc[0], cur, fc[0], 0, W0[c_last:], fc[0], 1, self._dskip, c_skip)
             self._gemm(R, c_last, fc[0], cur, fc[0], 0, W0, fc[0], 1, nxt, c_last)
             cur, nxt = nxt, cur
@@ -345,8 +266,8 @@ class PointNetTrainer:
             # ---- the convolutions backwards ----
             for i in range(nc - 1, -1, -1):
                 K = 6 if i == 0 else conv[i - 1]
-                self._dW(acts[i], cur, K, conv[i], G['kernel%d' % i])
-                self._colsum(cur, conv[i], G['bias%d' % i])
+                self._dW(acts[i], cur, K, conv[i], R, G['kernel%d' % i])
+                self._colsum(cur, conv[i], G['bias%d' % i], self._plan)
                 if i > 0:
                     extra = self._dskip if (i == 2 and nc > 2) else None           # acts[2] = conv[1] also feeds the head
                     self._gemm(R, K, conv[i], cur, conv[i], 0, V['kernel%d' % i], conv[i], 1, nxt, K, addend=extra, mask=acts[i])
@@ -360,43 +281,16 @@ class PointNetTrainer:
     def train_step(self, points, labels, mark=None):
         """``sess.run([net.class_acc, net.class_loss, net.train_op], feed)`` (:408) -> dict(loss, acc)."""
         sc = self.backward(points, labels, mark=mark)
-        t = self.step + 1
-        lr_t = self.learning_rate() * np.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
         with torch.cuda.device(self.dev):
             self._check(self.lib.lrg_pointnet_ema_update(_ptr(self.ema), _ptr(self.moments), self.ema.numel(),
                                                          ctypes.c_float(np.float32(1 - self.ema_decay)), _stream()), 'lrg_pointnet_ema_update')
-            self._check(self.lib.lrg_adam_step(_ptr(self.flat), _ptr(self.gflat), _ptr(self.m), _ptr(self.v), self.flat.numel(), ctypes.c_float(lr_t),
-                                               ctypes.c_float(self.b1), ctypes.c_float(self.b2), ctypes.c_float(self.eps), _stream()),
-                        'lrg_adam_step')
+            self._adam_update(self.learning_rate())
             if mark:
                 mark('update')
-        self.step += 1
         self._eval_net = None
         return sc
 
-    def eval_logits(self, points):
-        """The logits [b,1024,num_class] (a device tensor) of ``is_training_pl: False`` (:432): PointNetHIP's two kernels on the
-        trainer's current weights, the batch norm reading the moving averages."""
+    def _inference_net(self):
+        """PointNetHIP's two kernels on the current weights, the batch norm reading the moving averages."""
         from .pointnet import PointNetHIP
-        if self._eval_net is None:
-            self._eval_net = PointNetHIP(self.weights_numpy(), device=self.dev)
-        points = np.ascontiguousarray(points, dtype=np.float32)
-        with torch.cuda.device(self.dev):
-            return self._eval_net._forward(torch.from_numpy(points).to(self.dev))
-
-    def evaluate(self, points, labels):
-        """dict(loss, acc) of a batch with ``is_training_pl: False`` (the validation loop, :419-436)."""
-        labels = np.ascontiguousarray(np.asarray(labels).astype(np.int32)).reshape(-1)
-        with torch.cuda.device(self.dev):
-            out = self.eval_logits(points)
-            rows = out.shape[0] * NUM_POINT
-            if labels.size != rows:
-                raise ValueError('labels must be [%d, %d]' % (out.shape[0], NUM_POINT))
-            lab = torch.from_numpy(labels).to(self.dev)
-            stats = torch.zeros(3, dtype=torch.float64, device=self.dev)
-            self._check(self.lib.lrg_pointnet_softmax_ce_grad(_ptr(out), _ptr(lab), rows, self.num_class, None, _ptr(stats), _stream()),
-                        'lrg_pointnet_softmax_ce_grad')
-            s = stats.cpu().numpy()
-        if s[2]:
-            raise ValueError('%d labels are outside [0, %d)' % (int(s[2]), self.num_class))
-        return dict(loss=float(s[0] / rows), acc=float(s[1] / rows))
+        return PointNetHIP(self.weights_numpy(), device=self.dev)

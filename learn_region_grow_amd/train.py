@@ -6,7 +6,9 @@ train_region_grow.py:175.  The forward pass is the inference path's own (``lrg_f
 the backward pass runs through the C-ABI entry points of csrc/lrg_train.hip -- ``lrg_gemm_f32`` on the fp32 matrix cores
 for dX = dZ W^T (ReLU gradient in the epilogue) and dW = X^T dZ (reduction over the B*512 rows split over workgroups),
 ``lrg_ce_grad``, ``lrg_pool_backward`` (tf.reduce_max's tie rule), ``lrg_segment_colsum`` and ``lrg_adam_step`` --
-sequenced here, as the reference sequences its step from Python.  torch owns the buffers; it computes nothing.
+sequenced here, as the reference sequences its step from Python.  torch owns the buffers; it computes nothing.  The flat parameter buffer and the
+Adam step are adam_trainer.AdamTrainer's; the weight gradients here add atomically over the split (``_dW``) and the column sums go per
+instance (``_colsum``), which is other arithmetic than the PointNet trainers' and stays here.
 
 The first head layer is differentiated in the hoisted form the forward uses (:128-141): with S[b] = the sum of dZ0 over
 instance b's rows, dW0[:P] = pooled^T S, d(pooled) += S W0[:P]^T, dW0[P:] = conv[1]^T dZ0, d(conv[1]) += dZ0 W0[P:]^T.
@@ -17,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .adam_trainer import AdamTrainer
 from .lrgnet import LrgNetHIP, _ptr, _stream_ptr
 
 
@@ -25,7 +28,7 @@ def variable_order(net):
     return sorted(net.variable_shapes())
 
 
-class LrgNetTrainer:
+class LrgNetTrainer(AdamTrainer):
     def __init__(self, batch_size, num_inlier_points=512, num_neighbor_points=512, feature_size=13, lite=0, device='cuda:0',
                  learning_rate=1e-3, beta1=0.9, beta2=0.999, epsilon=1e-8):
         if num_inlier_points % 64 or num_neighbor_points % 64:
@@ -36,28 +39,14 @@ class LrgNetTrainer:
         self.dev = self.net.device
         self.B, self.Ni, self.Nn, self.F = batch_size, num_inlier_points, num_neighbor_points, feature_size
         self.lr, self.b1, self.b2, self.eps = learning_rate, beta1, beta2, epsilon
-        self.t = 0
-        self.flat = None
+        self.shapes, self.names = self.net.variable_shapes(), variable_order(self.net)
 
-    # ---- variables: one flat buffer, the network's tensors are views into it ----
+    # ---- variables: one flat buffer (AdamTrainer), the network's tensors are views into it ----
     def load_weights(self, weights):
         net = self.net
         net.load_weights(weights)
-        names = variable_order(net)
-        sizes = [net.weights[k].numel() for k in names]
-        offs = np.concatenate([[0], np.cumsum(sizes)])
-        self.names, self.offs = names, offs
-        self.flat = torch.empty(int(offs[-1]), dtype=torch.float32, device=self.dev)
-        self.gflat = torch.zeros_like(self.flat)
-        self.m = torch.zeros_like(self.flat)
-        self.v = torch.zeros_like(self.flat)
-        self.views, self.gviews = {}, {}
-        for k, o, n in zip(names, offs[:-1], sizes):
-            shp = net.weights[k].shape
-            self.flat[o:o + n].copy_(net.weights[k].reshape(-1))
-            self.views[k] = self.flat[o:o + n].view(shp)
-            self.gviews[k] = self.gflat[o:o + n].view(shp)
-            net.weights[k] = self.views[k]
+        self._bind(weights)
+        net.weights.update(self.views)
         w = net._w
         cc, c2 = net.conv_channels, net.conv2_channels
         for i in range(len(cc)):
@@ -71,7 +60,6 @@ class LrgNetTrainer:
             w.rmv_w[i] = self.views['lrg_remove_kernel%d' % i].data_ptr()
             w.rmv_b[i] = self.views['lrg_remove_bias%d' % i].data_ptr()
         net.pack_weights()
-        self.t = 0
         Rm = self.B * max(self.Ni, self.Nn)
         wmax = max(list(cc) + list(c2) + [2])
         self._dz = [torch.empty(Rm * wmax, dtype=torch.float32, device=self.dev) for _ in range(2)]
@@ -83,19 +71,12 @@ class LrgNetTrainer:
         self._stats = torch.zeros((2, 8), dtype=torch.float64, device=self.dev)
         return self
 
-    def weights_numpy(self):
-        """name -> array with the checkpoint's TF shapes ([1,Cin,Cout] kernels)."""
-        shapes = self.net.variable_shapes()
-        return {k: self.views[k].cpu().numpy().reshape(shapes[k]) for k in self.names}
-
     def checkpoint_numpy(self):
         """name -> array of everything the reference's ``Saver`` stores for this graph: variables, Adam slots, beta powers and the
         global step (checkpoint.lrgnet_checkpoint_tensors), so that ``Saver().restore`` (test_region_grow.py:92-93) finds every key."""
         from . import checkpoint
-        shapes = self.net.variable_shapes()
-        m = {k: self.m[o:o + self.views[k].numel()].cpu().numpy().reshape(shapes[k]) for k, o in zip(self.names, self.offs[:-1])}
-        v = {k: self.v[o:o + self.views[k].numel()].cpu().numpy().reshape(shapes[k]) for k, o in zip(self.names, self.offs[:-1])}
-        return checkpoint.lrgnet_checkpoint_tensors(self.weights_numpy(), m, v, self.t, self.b1, self.b2)
+        m, v = self.slots_numpy()
+        return checkpoint.lrgnet_checkpoint_tensors(self.weights_numpy(), m, v, self.step, self.b1, self.b2)
 
     def evaluate(self, inlier, neighbor, add_mask, rmv_mask):
         """Loss, precision and recall of a batch without the backward pass (the validation loop, train_region_grow.py:186-219, runs
@@ -211,18 +192,10 @@ class LrgNetTrainer:
             self._eye_n = n
         return self._eye_t
 
-    def grads_numpy(self):
-        shapes = self.net.variable_shapes()
-        return {k: self.gviews[k].cpu().numpy().reshape(shapes[k]) for k in self.names}
-
     def train_step(self, inlier, neighbor, add_mask, rmv_mask):
         """``sess.run([net.train_op, net.loss, net.add_prc, net.add_rcl, net.remove_prc, net.remove_rcl], feed)``."""
         sc = self.backward(inlier, neighbor, add_mask, rmv_mask)
-        self.t += 1
-        lr_t = self.lr * np.sqrt(1.0 - self.b2 ** self.t) / (1.0 - self.b1 ** self.t)
         with torch.cuda.device(self.dev):
-            _lib.check(self.lib.lrg_adam_step(_ptr(self.flat), _ptr(self.gflat), _ptr(self.m), _ptr(self.v), self.flat.numel(),
-                                              ctypes.c_float(lr_t), ctypes.c_float(self.b1), ctypes.c_float(self.b2), ctypes.c_float(self.eps),
-                                              _stream_ptr(self.dev)), 'lrg_adam_step')
+            self._adam_update(self.lr)
             self.net.pack_weights()
         return sc['loss'], sc['add_prc'], sc['add_rcl'], sc['remove_prc'], sc['remove_rcl']

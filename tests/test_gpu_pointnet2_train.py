@@ -18,16 +18,13 @@ from conftest import REPO
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pointnet2_ref as R              # noqa: E402
 import pointnet2_train_ref as ref      # noqa: E402
+from trainer_helpers import adam_f32, bits, three_cells      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 EINVAL = -1000
 P = 1024
 I32P = ctypes.POINTER(ctypes.c_int32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def ptr(t):
@@ -244,19 +241,6 @@ TRAINER_CASES = {'rgb-13': (13, True), 'xyz-13': (13, False), 'rgb-260': (260, T
 _cases = {}
 
 
-def three_cells(seed):
-    """1024 distinct points; about 300 distinct points drawn with replacement (ball-query padding and pool ties are routine); one
-    point 1024 times."""
-    rs = np.random.RandomState(seed)
-    def cloud(n):
-        p = rs.uniform(-0.5, 0.5, (n, 6)).astype(f32)
-        p[:, 2] = rs.uniform(0, 2.5, n)
-        p[:, 3:] = rs.uniform(0, 1, (n, 3))
-        return p
-    few = cloud(300)
-    return np.stack([cloud(P), few[np.concatenate([np.arange(300), rs.randint(0, 300, P - 300)])], np.repeat(cloud(1), P, axis=0)])
-
-
 def trainer_case(name):
     """Weights, a batch, the restatement's own level indices and its answers on them (float64 and float32), computed once per case and
     left unchanged."""
@@ -314,14 +298,6 @@ def test_backward_matches_the_restatement(cuda_device, name):
     tr.gflat.fill_(-777.25)
     assert tr.backward(case['pts'], case['lab'], loss_only=True) == sc
     assert (tr.gflat == -777.25).all()
-
-
-def adam_f32(p, g, m, v, lr_t, b1, b2, eps):
-    """lrg_adam_kernel's expression, operation by operation, in NumPy float32 -> (p, m, v)."""
-    lr_t, b1, b2, eps, one = f32(lr_t), f32(b1), f32(b2), f32(eps), f32(1)
-    m2 = m + (g - m) * (one - b1)
-    v2 = v + (g * g - v) * (one - b2)
-    return p - lr_t * m2 / (np.sqrt(v2) + eps), m2, v2
 
 
 def test_train_step_is_adam_at_a_constant_rate_on_the_trainers_own_gradients(cuda_device):

@@ -17,15 +17,12 @@ from conftest import REPO
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pointnet_ref                    # noqa: E402
 import pointnet_train_ref as ref       # noqa: E402
+from trainer_helpers import adam_f32, bits      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 EINVAL = -1000
 P = 1024
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def ptr(t):
@@ -338,14 +335,6 @@ def test_labels_out_of_range_raise(cuda_device):
     lab[1, 7] = 3
     with pytest.raises(ValueError):
         tr.backward(case['pts'], lab)
-
-
-def adam_f32(p, g, m, v, lr_t, b1, b2, eps):
-    """lrg_adam_kernel's expression, operation by operation, in NumPy float32 -> (p, m, v)."""
-    lr_t, b1, b2, eps, one = f32(lr_t), f32(b1), f32(b2), f32(eps), f32(1)
-    m2 = m + (g - m) * (one - b1)
-    v2 = v + (g * g - v) * (one - b2)
-    return p - lr_t * m2 / (np.sqrt(v2) + eps), m2, v2
 
 
 @pytest.mark.parametrize('name', ['tiny-3', 'shipped-13'])

@@ -496,11 +496,11 @@ def test_trainer_matches_the_oracle(cuda_device, shape):
     assert (sc['add_prc'], sc['add_rcl'], sc['remove_prc'], sc['remove_rcl']) == (a_prc, a_rcl, r_prc, r_rcl)
     assert (sc['add_acc'], sc['remove_acc']) == (case['scalars']['add_acc'], case['scalars']['remove_acc'])
     # evaluate(): the validation loop's call
-    w_before, t_before = tr.flat.clone(), tr.t
+    w_before, t_before = tr.flat.clone(), tr.step
     tr.gflat.fill_(-777.25)
     ev = tr.evaluate(xi, xn, am, rm)
     assert ev == sc
-    assert (tr.gflat == -777.25).all() and np.array_equal(_bits(tr.flat.cpu().numpy()), _bits(w_before.cpu().numpy())) and tr.t == t_before
+    assert (tr.gflat == -777.25).all() and np.array_equal(_bits(tr.flat.cpu().numpy()), _bits(w_before.cpu().numpy())) and tr.step == t_before
 
 
 @pytest.mark.parametrize('remove', [0, 1])
@@ -534,7 +534,7 @@ def test_train_step_is_adam_on_the_trainers_own_gradients(cuda_device, shape):
     p, m, v = flat(tr.weights_numpy()), np.zeros(tr.flat.numel(), np.float32), np.zeros(tr.flat.numel(), np.float32)
     for t in range(1, 4):
         tr.train_step(*case['batch'])
-        assert tr.t == t
+        assert tr.step == t
         g = flat(tr.grads_numpy())
         p, m, v = adam_f32(p, g, m, v, adam_lr_t(tr.lr, tr.b1, tr.b2, t), tr.b1, tr.b2, tr.eps)
         for name, got, want in (('weights', tr.flat, p), ('m', tr.m, m), ('v', tr.v, v)):

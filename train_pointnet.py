@@ -114,17 +114,12 @@ def run_epoch(trainer, points, labels, rs, batch_size, train):
     return np.mean(np.array(rows, dtype=np.float64), axis=0) if rows else np.array([np.nan, np.nan])
 
 
-def main(argv=None):
-    args = parse(argv)
-    if args.mode == 'pointnet2':
-        raise SystemExit('train_pointnet.py: --mode pointnet2 is not supported here: training PointNet++ needs the gradients of the whole '
-                         'sampling and interpolation stack and has a driver of its own, train_pointnet2.py (DESIGN.md §7); use --mode pointnet')
-    if args.mode != 'pointnet':
-        raise SystemExit("train_pointnet.py: unknown --mode %r (only 'pointnet')" % args.mode)
+def run(args, make_trainer, script):
+    """Everything after the arguments are parsed, for this driver and train_pointnet2.py: make_trainer(classes) builds the trainer once
+    the cells are staged; script is the driver's name in the message of a machine without a GPU."""
     import torch
-    from learn_region_grow_amd.pointnet_train import ARCHITECTURES, PointNetTrainer
     if not torch.cuda.is_available():
-        raise SystemExit('train_pointnet.py needs a GPU (the HIP path has no CPU fallback)')
+        raise SystemExit('%s needs a GPU (the HIP path has no CPU fallback)' % script)
     out = model_path(args)
     classes = num_classes(args.train_area)
     print('train', args.train_area.split(','), 'val', args.val_area.split(','), 'model', out, 'classes', classes)
@@ -137,8 +132,7 @@ def main(argv=None):
     if len(data['train_labels']) < args.batch_size:
         raise SystemExit('%d training cells are fewer than one batch of %d: nothing trained, no checkpoint written'
                          % (len(data['train_labels']), args.batch_size))
-    conv, fc = ARCHITECTURES[args.arch]
-    trainer = PointNetTrainer(args.batch_size, conv, fc, classes, device=args.device).init_weights(args.seed)
+    trainer = make_trainer(classes).init_weights(args.seed)
     for epoch in range(args.epochs):
         idx = np.arange(len(data['train_labels']))
         rs.shuffle(idx)                                                                   # :380-383
@@ -151,6 +145,21 @@ def main(argv=None):
     trainer.save(out)
     print('Saved %s' % out)
     return 0
+
+
+def main(argv=None):
+    args = parse(argv)
+    if args.mode == 'pointnet2':
+        raise SystemExit('train_pointnet.py: --mode pointnet2 is not supported here: training PointNet++ needs the gradients of the whole '
+                         'sampling and interpolation stack and has a driver of its own, train_pointnet2.py (DESIGN.md §7); use --mode pointnet')
+    if args.mode != 'pointnet':
+        raise SystemExit("train_pointnet.py: unknown --mode %r (only 'pointnet')" % args.mode)
+
+    def make_trainer(classes):
+        from learn_region_grow_amd.pointnet_train import ARCHITECTURES, PointNetTrainer
+        conv, fc = ARCHITECTURES[args.arch]
+        return PointNetTrainer(args.batch_size, conv, fc, classes, device=args.device)
+    return run(args, make_trainer, 'train_pointnet.py')
 
 
 if __name__ == '__main__':

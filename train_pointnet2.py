@@ -17,8 +17,6 @@ import argparse
 import os
 import sys
 
-import numpy as np
-
 REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
@@ -46,35 +44,11 @@ def parse(argv=None):
 
 def main(argv=None):
     args = parse(argv)
-    import torch
-    from learn_region_grow_amd.pointnet2_train import PointNet2Trainer
-    if not torch.cuda.is_available():
-        raise SystemExit('train_pointnet2.py needs a GPU (the HIP path has no CPU fallback)')
-    out = host.model_path(args)
-    classes = host.num_classes(args.train_area)
-    print('train', args.train_area.split(','), 'val', args.val_area.split(','), 'model', out, 'classes', classes)
-    rs = np.random.RandomState(args.seed)
-    data = host.stage(args, rs)
-    for name, key in (('Train', 'train'), ('Validation', 'val')):
-        lab = data[key + '_labels']
-        print('%s Points' % name, data[key + '_points'].shape)
-        print('%s Labels' % name, lab.shape, *((lab.min(), lab.max()) if lab.size else ()))
-    if len(data['train_labels']) < args.batch_size:
-        raise SystemExit('%d training cells are fewer than one batch of %d: nothing trained, no checkpoint written'
-                         % (len(data['train_labels']), args.batch_size))
-    trainer = PointNet2Trainer(args.batch_size, classes, rgb_features=args.features == 'rgb', device=args.device).init_weights(args.seed)
-    for epoch in range(args.epochs):
-        idx = np.arange(len(data['train_labels']))
-        rs.shuffle(idx)                                                                   # :380-383
-        loss, acc = host.run_epoch(trainer, data['train_points'][idx], data['train_labels'][idx], rs, args.batch_size, True)
-        print('Epoch: %d Loss: %.3f (cls %.3f)' % (epoch, loss, acc))                     # :411
-        if epoch % args.val_step == args.val_step - 1 and len(data['val_labels']) >= args.batch_size:
-            loss, acc = host.run_epoch(trainer, data['val_points'], data['val_labels'], rs, args.batch_size, False)
-            print('Validation: %d Loss: %.3f (cls %.3f)' % (epoch, loss, acc))            # :436
-    os.makedirs(os.path.dirname(out) or '.', exist_ok=True)
-    trainer.save(out)
-    print('Saved %s' % out)
-    return 0
+
+    def make_trainer(classes):
+        from learn_region_grow_amd.pointnet2_train import PointNet2Trainer
+        return PointNet2Trainer(args.batch_size, classes, rgb_features=args.features == 'rgb', device=args.device)
+    return host.run(args, make_trainer, 'train_pointnet2.py')
 
 
 if __name__ == '__main__':
