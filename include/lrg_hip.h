@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 18
+#define LRG_ABI_VERSION 19
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -743,6 +743,54 @@ int lrg_baseline_segment_labels(const float *pts, int ld, const int32_t *room_st
 size_t lrg_baseline_fpfh_workspace_bytes(int n_points, int n_rooms, int min_cluster_size);
 int lrg_baseline_segment_fpfh(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const float *hist, double t,
                               int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream);
+
+/* ABI 19.  Components of edges the caller has decided (benchmarks.py:353 edges = E[criteria], then :406-416).  The 26 offsets are numbered
+ * 0 .. 25 in itertools.product([-1, 0, 1], repeat=3) order without (0, 0, 0), so that offsets o and 25 - o are opposite; the edge between a
+ * point and its neighbour at offset 13 + s is bit s of the point's word in keep [n] uint32 (device), and is the only place that edge is
+ * stored.  Bits of missing neighbours are not read.  Numbering, min_cluster_size, workspace and status as lrg_baseline_segment_embedding. */
+int lrg_baseline_segment_mask(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const uint32_t *keep,
+                              int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 19.  The edge-classifier baseline, benchmarks.py --mode edge (:308-353 features, classifier and criteria, :406-436 components and
+ * the fallback search; csrc/lrg_edge.hip).  Rooms as for lrg_baseline_segment: equalised, room_start in HOST memory.
+ * Per-edge arrays are [n, 13] float64: slot [i, s] is the edge between i and its neighbour at offset 13 + s (numbering as
+ * lrg_baseline_segment_mask), NaN where there is none; each edge of the voxel graph has exactly one slot.
+ * ---------------------------------------------------------------------------------------------- */
+#define LRG_EDGE_WEIGHTS 9451          /* doubles: W0 [30,100] | b0 | W1 [100,50] | b1 | W2 [50,25] | b2 | W3 [25,1] | b3, [in, out] row-major */
+/* Workspace of lrg_edge_segment (lrg_edge_logits needs less and accepts it): 0 when an argument is out of range
+ * (1 <= min_cluster_size <= 64, 1 <= search_cap <= 2^20). */
+size_t lrg_edge_workspace_bytes(int n_points, int n_rooms, int min_cluster_size, int search_cap);
+/* :325-345 up to the logit.  nmin / nmax [n, 6] float32 (device, may be NULL): minimum and maximum of columns 0-5 over the point and its
+ * neighbours (:333-339).  z [n, 13] float64 (device): for every existing edge the 30 float32 features of :309-324 (mean, min, max of
+ * columns 2-5; |p1 - p2| of columns 0-5; the nmin term; the nmax term; each one or two rounded float32 operations) through the four
+ * layers of the reference's MLPClassifier (30-100-50-25-1, relu) in float64: acc = 0, acc = acc + x[k] * W[k][j] for k ascending with the
+ * product and the sum each rounded, then + b[j], then max(., 0); the last layer's sum plus its bias is z, the value before the
+ * logistic function of predict_proba (:345).  weights: LRG_EDGE_WEIGHTS float64 on the device. */
+int lrg_edge_logits(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const double *weights, void *ws,
+                    size_t ws_bytes, double *z, float *nmin, float *nmax, void *stream);
+/* p = 1 / (1 + exp(-z)) for count float64 values on the device, NaN kept.  Not bit-identical to scipy.special.expit. */
+int lrg_edge_sigmoid(const double *z, long count, double *p, void *stream);
+/* :346-353 and :406-436 from p [n, 13] (device, values in [0, 1] or NaN where there is no edge).  An edge is kept when
+ * p > rel * pmax[i] && p > rel * pmax[k] && p > floor (:351-352: rel 0.99, floor 0.9), pmax = the maximum of 0 and the p of the point's
+ * edges, the products rounded in float64.  Components of the kept edges with more than min_cluster_size points are the clusters
+ * (lrg_baseline_segment_mask; n_clusters [n_rooms]).  Every unlabelled point of a voxel-graph component that holds a cluster is then
+ * searched from as :424-436 does, one wavefront per search, and takes the label of the point its search stopped at.
+ * Outputs (device): labels [n] int32; stop [n] int32: the point the search from i stopped at (its index in the batch), -1 where none ran (clustered points and
+ * components without a cluster, whose points keep label 0), -2 where the search would have visited more than search_cap nodes (the
+ * point keeps label 0, as does every point whose chain ends there: the caller finishes them); counters [4] int32: points in components
+ * without a cluster, searches, searches that overflowed, the largest number of nodes a search visited (its start included);
+ * keep [n] uint32 and cluster_labels [n] int32 (either may be NULL): the keep words and the labels before the fallback.
+ * prepared != 0: ws is the workspace the last lrg_edge_logits ran on with these pts, room_start and resolution, and nothing else has
+ * written it since; its hash, neighbour table and status are used as they stand instead of being built again.
+ * Errors found on the device go to lrg_edge_status. */
+int lrg_edge_segment(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const double *p, double rel, double floor,
+                     int min_cluster_size, int search_cap, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, int32_t *stop,
+                     int32_t *counters, uint32_t *keep, int32_t *cluster_labels, int prepared, void *stream);
+/* Error bits of the last lrg_edge_logits / lrg_edge_segment on this workspace (synchronises the stream): 1 a voxel outside the 21-bit
+ * window, 2 two points of one room in one voxel (the room is not equalised), 4 a label chain was not resolved (not reachable: a
+ * chain has fewer links than points).  The outputs are not valid when it is non-zero. */
+int lrg_edge_status(const void *ws, int32_t *host_status, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * ABI 18.  Fast Point Feature Histograms for benchmarks.py --mode fpfh (:354-358) without PCL: the arithmetic of PCL's

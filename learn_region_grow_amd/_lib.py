@@ -12,9 +12,9 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
            'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip', 'lrg_pointnet_train.hip',
-           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip']
+           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip']
 
-LRG_ABI_VERSION = 18      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 19      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -279,6 +279,14 @@ _SIGS = {
     'lrg_baseline_fpfh_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3),
     'lrg_baseline_segment_fpfh': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_float, _fp, ctypes.c_double, ctypes.c_int, _fp,
                                                  ctypes.c_size_t, _fp, _fp, _fp]),
+    'lrg_baseline_segment_mask': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_float, _fp, ctypes.c_int, _fp, ctypes.c_size_t,
+                                                 _fp, _fp, _fp]),
+    'lrg_edge_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
+    'lrg_edge_logits': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_float, _fp, _fp, ctypes.c_size_t, _fp, _fp, _fp, _fp]),
+    'lrg_edge_sigmoid': (ctypes.c_int, [_fp, ctypes.c_long, _fp, _fp]),
+    'lrg_edge_segment': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_float, _fp, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                        ctypes.c_int, _fp, ctypes.c_size_t, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.c_int, _fp]),
+    'lrg_edge_status': (ctypes.c_int, [_fp, ctypes.POINTER(ctypes.c_int32), _fp]),
     'lrg_fpfh_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3),
     'lrg_fpfh': (ctypes.c_int, [_fp, ctypes.c_int, _fp, _fp, _fp, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int, _fp, ctypes.c_size_t,
                                 _fp, _fp, _fp, _fp]),

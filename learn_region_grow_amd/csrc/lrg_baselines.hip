@@ -18,6 +18,9 @@
 // lrg_baseline_segment_fpfh (benchmarks.py --mode fpfh) puts one launch in front of these: the normalised histograms
 // u [n, 33] in float64, which its edge predicate reads; the descriptor itself is lrg_fpfh.hip's.
 //
+// lrg_baseline_segment_mask (benchmarks.py --mode edge) runs the same launches on edges the caller has decided: a 13-bit
+// word per point, bit s = the edge to the neighbour at offset 13 + s (the positive half of the 26 offsets) is kept.
+//
 // Features solved on the device (DESIGN §3.8 "verified"): lrg_baseline_eig is prep_jacobi3 on every covariance with a bound on each
 // value's distance from LAPACK's, and lrg_baseline_certify (init, insert, certify, tally) flags both ends of every edge whose
 // predicate could come out differently within those bounds, so that only they go through LAPACK on the host.
@@ -30,11 +33,13 @@
 // flags, scans) is separated from its writes by a launch boundary.
 #include "lrg_common.h"
 #include "lrg_eig3.h"
+#include "lrg_union.h"
+#include "lrg_room_hash.h"
 
 #define BL_THREADS 256
 #define BL_SCAN_ITEMS 8                       // per thread: 2048 elements per block
 
-enum { BL_NORMAL = 0, BL_CURVATURE = 1, BL_COLOR = 2, BL_FEATURE = 3, BL_SMOOTHNESS = 4, BL_EMBEDDING = 5, BL_LABELS = 6, BL_FPFH = 7 };   // 5: lrg_baseline_segment_embedding only, 6: lrg_baseline_segment_labels only, 7: lrg_baseline_segment_fpfh only
+enum { BL_NORMAL = 0, BL_CURVATURE = 1, BL_COLOR = 2, BL_FEATURE = 3, BL_SMOOTHNESS = 4, BL_EMBEDDING = 5, BL_LABELS = 6, BL_FPFH = 7, BL_MASK = 8 };   // 5: lrg_baseline_segment_embedding only, 6: lrg_baseline_segment_labels only, 7: lrg_baseline_segment_fpfh only, 8: lrg_baseline_segment_mask only
 // status bits (lrg_baseline_status)
 enum { BL_ST_WINDOW = 1, BL_ST_DUPLICATE = 2, BL_ST_RANK = 4, BL_ST_STACK = 8 };
 
@@ -82,6 +87,7 @@ struct BlArgs {
     const double *normals, *curv; const int32_t *rank;
     const float *emb; int dim;
     const int32_t *cls;
+    const uint32_t *keep;                                              // lrg_baseline_segment_mask only: [n] 13-bit keep words
     double *unit;                                                      // lrg_baseline_segment_fpfh only: [n, 33] normalised histograms
     double t1, t2, t3; int mcs;
     uint64_t *keys; int32_t *vals, *room_of, *parent, *size; unsigned long long *minkey;
@@ -92,19 +98,11 @@ struct BlArgs {
 };
 
 // Bounds of room r (room_start was checked on the host: this only keeps a bad word from turning into an address)
-__device__ __forceinline__ bool bl_room(const BlArgs &a, int r, int *s, int *e) {
-    const int s0 = a.room_start[r], e0 = a.room_start[r + 1];
-    if (s0 < 0 || e0 < s0 || e0 > a.n) return false;
-    *s = s0; *e = e0;
-    return true;
-}
+__device__ __forceinline__ bool bl_room(const BlArgs &a, int r, int *s, int *e) { return lrg_room_bounds(a.room_start, a.n, r, s, e); }
 
 // the room's hash segment: capacity the smallest power of two >= max(64, 2 n_room) (< 4 n_room + 64), at 4 start + 64 r
 __device__ __forceinline__ void bl_segment(const BlArgs &a, int r, int s, int e, uint64_t **keys, int32_t **vals, int *mask) {
-    int cap = 64;
-    while (cap < 2 * (e - s)) cap <<= 1;
-    const long off = 4L * s + 64L * r;
-    *keys = a.keys + off; *vals = a.vals + off; *mask = cap - 1;
+    lrg_room_segment(a.keys, a.vals, r, s, e, keys, vals, mask);
 }
 
 // normals[k].dot(normals[i]) as OpenBLAS's ddot computes it for n = 3: fma(a2, b2, fma(a1, b1, a0 * b0))
@@ -157,8 +155,15 @@ __global__ __launch_bounds__(BL_THREADS) void bl_fpfh_unit_kernel(const float *h
     for (int c = 0; c < BL_FPFH_DIM; ++c) unit[(long)i * BL_FPFH_DIM + c] = __ddiv_rn((double)h[c], nrm);
 }
 
-__device__ __forceinline__ bool bl_edge(const BlArgs &a, int i, int k) {
+// the caller's decision on the edge from i to its neighbour k at offset o (0 .. 25 in itertools.product order without the centre;
+// o and 25 - o are opposite): the edge is stored once, at the end whose offset to the other is one of 13 .. 25, as bit o - 13
+__device__ __forceinline__ bool bl_mask_edge(const uint32_t *keep, int i, int k, int o) {
+    return o >= 13 ? (keep[i] >> (o - 13)) & 1u : (keep[k] >> (12 - o)) & 1u;
+}
+
+__device__ __forceinline__ bool bl_edge(const BlArgs &a, int i, int k, int o) {
     switch (a.mode) {
+    case BL_MASK: return bl_mask_edge(a.keep, i, k, o);
     case BL_NORMAL: case BL_SMOOTHNESS: return bl_normal_edge(a.normals, i, k, a.t1);
     case BL_CURVATURE: return bl_curv_edge(a.curv, i, k, a.t1);
     case BL_COLOR: return bl_color_edge(a.pts, a.ld, i, k, (float)a.t1);
@@ -171,34 +176,6 @@ __device__ __forceinline__ bool bl_edge(const BlArgs &a, int i, int k) {
     }
 }
 
-__device__ __forceinline__ int bl_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// root of x with path halving (x's parent replaced by its grandparent by CAS: still an ancestor, still smaller)
-__device__ __forceinline__ int bl_find(int32_t *parent, int x) {
-    int p = bl_load(parent + x);
-    while (p != x) {
-        const int g = bl_load(parent + p);
-        if (g == p) return p;
-        int expect = p;
-        __hip_atomic_compare_exchange_strong(parent + x, &expect, g, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = p;
-        p = g;
-    }
-    return x;
-}
-
-__device__ __forceinline__ void bl_union(int32_t *parent, int x, int y) {
-    int rx = bl_find(parent, x), ry = bl_find(parent, y);
-    while (rx != ry) {
-        const int hi = rx > ry ? rx : ry, lo = rx > ry ? ry : rx;
-        int seen = hi;
-        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            return;
-        // hi was linked meanwhile: continue from the parent the CAS returned, not from a fresh load of parent[hi]
-        rx = bl_find(parent, seen);
-        ry = bl_find(parent, lo);
-    }
-}
 
 __global__ __launch_bounds__(BL_THREADS) void bl_init_kernel(BlArgs a) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -211,12 +188,7 @@ __global__ __launch_bounds__(BL_THREADS) void bl_init_kernel(BlArgs a) {
     }
     if (t >= a.n) return;
     const int i = (int)t;
-    int lo = 0, hi = a.n_rooms - 1;                // the last r with room_start[r] <= i
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.room_start[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    a.room_of[i] = lo;
+    a.room_of[i] = lrg_room_of(a.room_start, a.n_rooms, i);
     a.parent[i] = i;
     a.size[i] = 0;
     a.minkey[i] = ~0ULL;
@@ -239,14 +211,7 @@ __global__ __launch_bounds__(BL_THREADS) void bl_insert_kernel(BlArgs a) {
     if (key == LRG_HASH_EMPTY) { atomicOr(&a.scal[0], BL_ST_WINDOW); a.room_of[i] = -1; return; }
     uint64_t *keys; int32_t *vals; int mask;
     bl_segment(a, r, s, e, &keys, &vals, &mask);
-    unsigned h = (unsigned)lrg_fmix64(key) & (unsigned)mask;
-    for (int probe = 0; probe <= mask; ++probe) {
-        const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&keys[h]), (unsigned long long)LRG_HASH_EMPTY,
-                                                  (unsigned long long)key);
-        if (prev == LRG_HASH_EMPTY) { vals[h] = i; return; }
-        if (prev == key) { atomicOr(&a.scal[0], BL_ST_DUPLICATE); return; }      // the room is not equalised
-        h = (h + 1) & (unsigned)mask;
-    }
+    if (!lrg_room_insert(keys, vals, mask, key, i)) atomicOr(&a.scal[0], BL_ST_DUPLICATE);      // the room is not equalised
 }
 
 __global__ __launch_bounds__(BL_THREADS) void bl_union_kernel(BlArgs a) {
@@ -260,13 +225,15 @@ __global__ __launch_bounds__(BL_THREADS) void bl_union_kernel(BlArgs a) {
     bl_segment(a, r, s, e, &keys, &vals, &mask);
     const float *p = a.pts + (long)i * a.ld;
     const int vx = lrg_voxel_of(p[0], a.res), vy = lrg_voxel_of(p[1], a.res), vz = lrg_voxel_of(p[2], a.res);
+    int o = 0;                                     // the offset's number, the centre left out
     for (int dx = -1; dx <= 1; ++dx)
         for (int dy = -1; dy <= 1; ++dy)
             for (int dz = -1; dz <= 1; ++dz) {
                 if (!dx && !dy && !dz) continue;
+                const int at = o++;
                 const int k = lrg_hash_lookup(keys, vals, mask, lrg_pack_voxel(vx + dx, vy + dy, vz + dz));
                 if (k < 0 || k >= i) continue;
-                if (bl_edge(a, i, k)) bl_union(a.parent, i, k);
+                if (bl_edge(a, i, k, at)) bl_union(a.parent, i, k);
             }
 }
 
@@ -514,7 +481,7 @@ static int bl_setup(const float *pts, int ld, const int32_t *room_start, int n_r
     const int n_points = room_start[n_rooms];
     int rc = bl_layout(n_points, n_rooms, min_cluster_size, &L);
     if (rc) return rc;
-    if (mode < BL_NORMAL || mode > BL_FPFH) return LRG_EINVAL - 72;
+    if (mode < BL_NORMAL || mode > BL_MASK) return LRG_EINVAL - 72;
     if (mode == BL_EMBEDDING && (!emb || dim < 1 || dim > 64)) return LRG_EINVAL - 74;
     if (mode == BL_FPFH && (dim != BL_FPFH_DIM || (!emb && n_points > 0))) return LRG_EINVAL - 74;
     if (mode == BL_LABELS && !cls && n_points > 0) return LRG_EINVAL - 74;
@@ -530,7 +497,7 @@ static int bl_setup(const float *pts, int ld, const int32_t *room_start, int n_r
     int32_t *rooms = reinterpret_cast<int32_t *>(w + L.rooms);     // a device copy of room_start (the caller's is host memory)
     LRG_HIP_CHECK(hipMemcpyAsync(rooms, room_start, (size_t)(n_rooms + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
     a.pts = pts; a.ld = ld; a.room_start = rooms; a.n_rooms = n_rooms; a.n = n_points; a.res = resolution; a.mode = mode;
-    a.normals = normals; a.curv = curvatures; a.rank = rank; a.emb = emb; a.dim = dim; a.cls = cls; a.unit = nullptr; a.t1 = t1; a.t2 = t2; a.t3 = t3; a.mcs = min_cluster_size;
+    a.normals = normals; a.curv = curvatures; a.rank = rank; a.emb = emb; a.dim = dim; a.cls = cls; a.keep = nullptr; a.unit = nullptr; a.t1 = t1; a.t2 = t2; a.t3 = t3; a.mcs = min_cluster_size;
     a.keys = reinterpret_cast<uint64_t *>(w + L.keys); a.vals = reinterpret_cast<int32_t *>(w + L.vals);
     a.room_of = reinterpret_cast<int32_t *>(w + L.room_of); a.parent = reinterpret_cast<int32_t *>(w + L.parent);
     a.size = reinterpret_cast<int32_t *>(w + L.size); a.minkey = reinterpret_cast<unsigned long long *>(w + L.minkey);
@@ -555,15 +522,16 @@ static inline size_t bl_fpfh_unit_bytes(int n_points) { return lrg_align_up((siz
 static int bl_segment_impl(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, int mode,
                            const double *normals, const double *curvatures, const int32_t *rank, const float *emb, int dim, const int32_t *cls, double t1,
                            double t2, double t3, int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters,
-                           void *stream) {
+                           void *stream, const uint32_t *keep = nullptr) {
     LrgBaselineLayout L;
     BlArgs a;
     hipStream_t st = (hipStream_t)stream;
+    if (mode == BL_MASK && !keep && room_start && n_rooms >= 1 && room_start[n_rooms] > 0) return LRG_EINVAL - 74;
     int rc = bl_setup(pts, ld, room_start, n_rooms, resolution, mode, normals, curvatures, rank, emb, dim, cls, t1, t2, t3, min_cluster_size, ws,
                       ws_bytes, true, labels && n_clusters, st, &L, &a);
     if (rc) return rc;
     const int n_points = a.n;
-    a.labels = labels; a.n_clusters = n_clusters;
+    a.labels = labels; a.n_clusters = n_clusters; a.keep = keep;
     if (mode == BL_FPFH) {                                     // the normalised histograms, behind the siblings' workspace
         if (ws_bytes < L.total + bl_fpfh_unit_bytes(n_points)) return LRG_EINVAL - 75;
         a.unit = reinterpret_cast<double *>(static_cast<char *>(ws) + L.total);
@@ -608,6 +576,12 @@ int lrg_baseline_segment_labels(const float *pts, int ld, const int32_t *room_st
                                 int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream) {
     return bl_segment_impl(pts, ld, room_start, n_rooms, resolution, BL_LABELS, nullptr, nullptr, nullptr, nullptr, 0, cls, 0.0, 0.0, 0.0,
                            min_cluster_size, ws, ws_bytes, labels, n_clusters, stream);
+}
+
+int lrg_baseline_segment_mask(const float *pts, int ld, const int32_t *room_start, int n_rooms, float resolution, const uint32_t *keep,
+                              int min_cluster_size, void *ws, size_t ws_bytes, int32_t *labels, int32_t *n_clusters, void *stream) {
+    return bl_segment_impl(pts, ld, room_start, n_rooms, resolution, BL_MASK, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0.0, 0.0, 0.0,
+                           min_cluster_size, ws, ws_bytes, labels, n_clusters, stream, keep);
 }
 
 size_t lrg_baseline_fpfh_workspace_bytes(int n_points, int n_rooms, int min_cluster_size) {
