@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 19
+#define LRG_ABI_VERSION 20
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -914,6 +914,30 @@ int lrg_mcp_pack_weights(const float *k1, const float *b1, const float *k2, cons
  * [0, n) (that row then uses the point itself). */
 int lrg_mcp_embed(const float *pts, int ld, int n_points, const int32_t *nbr, const float *packed, float *emb, int32_t *status,
                   void *stream);
+
+/* ---- training MCPNet (ABI 20; train_mcpnet.py, metric_loss_ops.py:40-81 and :119-236; csrc/lrg_mcpnet_train.hip) ---- */
+#define LRG_MCP_TRAIN_POINTS 2   /* points per workgroup of lrg_mcp_embed_train */
+#define LRG_MCP_TRIPLET_MAX_B 1024
+/* lrg_mcp_embed with every layer kept (learn_region_grow_util.py:210-225 as train_mcpnet.py:197 runs it): x [n, 50, 6] the staged
+ * rows (already the float32 differences neighbour - point), c [n, 4] the centre features (z, r, g, b), packed as lrg_mcp_pack_weights
+ * left it.  h1, h2 [n * 50, 200] (after ReLU), cat [n, 204], fc3 [n, 200], fc4 [n, 10], emb [n, 10]; any of h1, h2, cat, fc3, fc4 may
+ * be NULL (all NULL: the validation forward).  emb carries the bits lrg_mcp_embed gives for points whose differences are x. */
+int lrg_mcp_embed_train(const float *x, const float *c, int n, const float *packed, float *h1, float *h2, float *cat, float *fc3,
+                        float *fc4, float *emb, void *stream);
+/* Doubles of the workspace of lrg_mcp_triplet_semihard for a batch of B. */
+size_t lrg_mcp_triplet_workspace_doubles(int B);
+/* triplet_semihard_loss (metric_loss_ops.py:157-236, pairwise_distance(squared=True) :40-81) of emb [B, 10] = l2_normalize(fc4 [B, 10])
+ * with labels [B] (int32, any values), 2 <= B <= LRG_MCP_TRIPLET_MAX_B, and its gradient by TensorFlow's registered rules:
+ *   D [B, B]     max((sq_i + sq_j) - 2 dot_ij, 0), diagonal 0; sq and dot summed over the 10 columns in ascending order, products
+ *                rounded (no FMA)
+ *   dD [B, B]    d(loss)/d(squared distance before the clamp): zero on the diagonal and where D <= 0
+ *   dfc4 [B, 10] dE_i = 2 sum_j (dD_ij + dD_ji)(e_i - e_j) in ascending j, then l2_normalize's backward
+ *   stats [4]    doubles: the loss numerator, num_positives, the positive pairs with a gradient (margin + D_ap - S_ap >= 0), the
+ *                positive pairs that took negatives_inside
+ * Nothing is added atomically: the same inputs give the same bits.  ws: lrg_mcp_triplet_workspace_doubles(B) doubles.
+ * LRG_EINVAL - 91: B outside the range (nothing is launched). */
+int lrg_mcp_triplet_semihard(const float *fc4, const float *emb, const int32_t *labels, int B, float margin, float *D, float *dD,
+                             float *dfc4, double *stats, double *ws, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training side: the pieces of the backward pass and of AdamOptimizer

@@ -12,9 +12,9 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
            'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip', 'lrg_pointnet_train.hip',
-           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip']
+           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip', 'lrg_mcpnet_train.hip']
 
-LRG_ABI_VERSION = 19      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 20      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -319,6 +319,9 @@ _SIGS = {
     'lrg_mcp_packed_floats': (ctypes.c_size_t, []),
     'lrg_mcp_pack_weights': (ctypes.c_int, [_fp] * 10),
     'lrg_mcp_embed': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _fp]),
+    'lrg_mcp_embed_train': (ctypes.c_int, [_fp, _fp, ctypes.c_int] + [_fp] * 8),
+    'lrg_mcp_triplet_workspace_doubles': (ctypes.c_size_t, [ctypes.c_int]),
+    'lrg_mcp_triplet_semihard': (ctypes.c_int, [_fp, _fp, _fp, ctypes.c_int, ctypes.c_float] + [_fp] * 6),
     'lrg_gemm_f32': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int,
                                     _fp, ctypes.c_int, _fp, _fp, ctypes.c_int, _fp]),
     'lrg_gemm_f32_planes_count': (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),

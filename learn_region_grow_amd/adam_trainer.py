@@ -1,4 +1,4 @@
-"""What the trainers share (train.py, pointnet_train.py, pointnet2_train.py), on two levels and nothing else.
+"""What the trainers share (train.py, pointnet_train.py, pointnet2_train.py, mcpnet_train.py), on two levels and nothing else.
 
 ``AdamTrainer``              every trainable in one flat float32 buffer with its gradient and Adam's two slots beside it, the NumPy
                              views out of them, the step counter and the one call of ``lrg_adam_step``.

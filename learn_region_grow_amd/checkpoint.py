@@ -460,6 +460,12 @@ def load_mcpnet_weights(prefix, verify=True):
     return load_bundle(prefix, names=list(MCPNET_SHAPES), verify=verify)
 
 
+def mcpnet_checkpoint_tensors(weights, adam_m=None, adam_v=None, step=0, beta1=0.9, beta2=0.999):
+    """Everything ``tf.compat.v1.train.Saver().save`` (train_mcpnet.py:227) writes for the MCPNet graph: the eight trainables, their
+    Adam slots, the beta powers and ``Variable`` -- the 27 entries of the shipped models/mcpnet_model5.ckpt.index."""
+    return _saver_tensors('MCPNet', MCPNET_SHAPES, weights, adam_m, adam_v, step, beta1, beta2)
+
+
 POINTNET2_SA_MLPS = ((32, 32, 64), (64, 64, 128), (128, 128, 256), (256, 256, 512))     # train_pointnet.py:181-184
 POINTNET2_FP_MLPS = ((256, 256), (256, 256), (256, 128), (128, 128, 128))               # :187-190
 

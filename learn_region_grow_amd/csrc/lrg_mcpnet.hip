@@ -25,20 +25,8 @@
 
 #define MCP_THREADS 256
 #define MCP_SCAN_ITEMS 8
-#define MCP_K LRG_MCP_NEIGHBORS      // 50 rows per point
-#define MCP_H 200
-#define MCP_E 10
+#include "lrg_mcp_layout.h"
 #define MCP_PTS 16                   // points per wavefront: 800 rows = 25 tiles of 32
-#define MCP_NT 7                     // 32-column tiles of layer 2
-#define MCP_KG 25                    // float4 k-groups of layer 2 (100 k-steps of two)
-#define MCP_FD 5                     // depth of the weight ring (groups)
-#define MCP_OFF_K1 0                 // [200][8]: K1[0..5][c], b1[c], b2[c]
-#define MCP_OFF_K2 1600              // [7][25][64] float4: lane l, component q of group g of tile t = K2[8 g + 2 q + (l >> 5)][32 t + (l & 31)]
-#define MCP_OFF_K3 46400             // [204][200]
-#define MCP_OFF_B3 87200             // [200]
-#define MCP_OFF_K4 87400             // [200][10]
-#define MCP_OFF_B4 89400             // [16]
-#define MCP_PACKED 89416
 
 // status bits (lrg_mcp_status)
 enum { MCP_ST_WINDOW = 1, MCP_ST_POSITION = 2 };
@@ -296,7 +284,6 @@ __global__ __launch_bounds__(MCP_THREADS) void mcp_neighbor_kernel(McpArgs a) {
 }
 
 // ---- the embedding network ----
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ __launch_bounds__(64) void mcp_embed_kernel(const float *__restrict__ pts, int ld, int n, const int32_t *__restrict__ nbr,
                                                        const float *__restrict__ W, float *__restrict__ emb, int32_t *status) {
