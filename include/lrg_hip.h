@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 20
+#define LRG_ABI_VERSION 21
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -247,7 +247,8 @@ typedef struct LrgGrowParams {
     int32_t scoring;         /* restart score (test_random_restart.py:171-174): 0 = 'np' points of the mask, 1 = 'ml' summed
                                 log-likelihood of the sampled add / remove masks, one scalar per restart (upstream resets the
                                 accumulator to a list at :194-196, which breaks it from the second restart on; implemented as
-                                evidently intended).  'ml' is computed by lrg_grow_step_packed only.                        */
+                                evidently intended).  For restarts 'ml' is computed by lrg_grow_step_packed only.  The beam search
+                                (lrg_beam_level) reads the same switch for the score of its queue: see LrgBeamGroup.       */
 } LrgGrowParams;
 
 /* Bind the slots [first_slot, first_slot + group_size) to room `room` (-1: leave them idle), on the device: every slot
@@ -569,10 +570,25 @@ int lrg_stream_destroy(void *stream);
  * Beam search (test_beam_search.py:143-290) with the queue on the device.
  * A room in flight is a group of beam_width * search_width consecutive slots (child (qid, search id) = slot qid * search_width
  * + search id).  lrg_beam_level = one level of every room in flight: lrg_beam_advance (children of the last level -> next queue
- * by size, :275-287; stall test / commit of the head, :188-198,:289-293; next seed, :154-174; next children into the slots),
- * then the loop's kernels over all slots (box query, median, sampling, gather, LrgNet on the distinct rows, mask update, scan of
- * the updated masks).  No host decision in between; finished rooms appear in the stats ring (first slot of the group).
+ * by score, :275-287; stall test / commit of the head, :188-198,:289-293; next seed, :154-174; next children into the slots),
+ * then the loop's kernels over all slots (box query, median, sampling, gather, LrgNet on the distinct rows, the 'ml' score where
+ * asked for, mask update, scan of the updated masks).  No host decision in between; finished rooms appear in the stats ring
+ * (first slot of the group).
+ * The score (LrgGrowParams.scoring, test_beam_search.py:275-280) is the sort key of every level: 0 = 'np', the points of the child's
+ * mask; 1 = 'ml', the parent's score plus the log-likelihood of the masks the child sampled (lrg_beam_ml_score, :237-257,:273),
+ * carried from level to level in q_score / LrgSlot.ml_score.  The best beam_width children by that key (descending, ties in child
+ * order) form the next queue, and emptied masks are dropped from it AFTERWARDS (csrc/lrg_beam_select.h).
  * ---------------------------------------------------------------------------------------------- */
+/* One record of the optional trace: what lrg_beam_advance chose at one evaluated level of one seed. */
+typedef struct LrgBeamTraceRec {
+    int32_t room;            /* index into rooms[]                                                                       */
+    int32_t seed;            /* seed point                                                                               */
+    int32_t level;           /* level of the queue whose children were evaluated                                         */
+    int32_t n;               /* entries below: the best beam_width children BEFORE the emptied masks are dropped         */
+    int32_t ordinal[16];     /* child ordinal qid * search_width + search id                                             */
+    int32_t size[16];        /* points of its mask; 0 = emptied, dropped from the queue                                  */
+    double score[16];        /* its key: 'ml' the log-likelihood, 'np' the size as a double                              */
+} LrgBeamTraceRec;
 typedef struct LrgBeamGroup {
     uint8_t *parent;         /* [beam_width, cap] masks of the queue entries                                             */
     int32_t cap;             /* row stride of parent                                                                     */
@@ -584,13 +600,26 @@ typedef struct LrgBeamGroup {
     int32_t seq_mn[3], seq_mx[3];
     int32_t q_count[16], q_parent[16];       /* queue entries: mask size, parent buffer (-1 = the seed alone)            */
     int32_t q_mn[16][3], q_mx[16][3];        /* their bounding boxes                                                      */
-    int32_t pad;
+    int32_t trace_cap;       /* records `trace` holds                                                                    */
+    double q_score[16];      /* their 'ml' scores (0 for the seed-only head, :164; 0 under 'np')                          */
+    LrgBeamTraceRec *trace;  /* nullable, device: one record per (group, evaluated level), written at index atomicAdd(trace_count, 1) --  */
+    int32_t *trace_count;    /*   in level order within a room; records beyond trace_cap are counted, not written (all groups may share both) */
 } LrgBeamGroup;
 int lrg_beam_advance(LrgBeamGroup *groups, LrgSlot *slots, LrgRoom *rooms, int n_groups, int beam_width, int search_width,
                      const LrgGrowParams *params, int64_t *stats, void *stream);
 int lrg_beam_level(LrgBeamGroup *groups, LrgSlot *slots, LrgRoom *rooms, int n_groups, int beam_width, int search_width, int max_points,
                    const LrgGrowParams *params, const LrgWeights *weights, const LrgStepBuffers *buffers, unsigned forward_flags,
                    void *stream);
+/* The 'ml' score of one evaluated level alone (what lrg_beam_level runs between the network and the mask update when
+ * params->scoring == 1): for every ACTIVE slot, slot.ml_score = (slot.ml_score + add side) + remove side, where a side is the sum over
+ * ALL sample rows (padded copies included) of log(conf_i) / n_neighbor if the row's un-centred, re-voxelised point lies in a voxel
+ * whose draw fired, else log(1 - conf_i) / n_neighbor -- both sides divide by n_neighbor (:255,:257).  float32 terms as NumPy computes
+ * them, each side summed in float64 in a fixed order (no atomics: the same bits every run).  The draws are those lrg_mask_update takes
+ * next (same keys, same policy switch; slot.step must still be the level's).  Reads buffers->center, inlier, neighbor, add_logits,
+ * rmv_logits, gt_add / gt_remove (policy 2), and sample_in / sample_nb where rows_in and rows_nb are set (the network then ran on the
+ * distinct leading rows only, and a padded row's logits are its source row's).  n_inlier, n_neighbor <= 1024.  Idle slots are left alone. */
+int lrg_beam_ml_score(LrgSlot *slots, const LrgRoom *rooms, int n_slots, const LrgGrowParams *params, const LrgStepBuffers *buffers,
+                      void *stream);
 
 /* 1-NN fill-in of unlabeled points in all F feature dims, first-min ties (:308-316). */
 int lrg_nn1_fill(const float *points, int n, int F, const int32_t *label_in, int32_t *label_out, void *stream);

@@ -14,7 +14,7 @@ SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', '
            'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip', 'lrg_pointnet_train.hip',
            'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip', 'lrg_mcpnet_train.hip']
 
-LRG_ABI_VERSION = 20      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 21      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -108,7 +108,13 @@ class LrgBeamGroup(ctypes.Structure):
                 ('stuck', ctypes.c_int32), ('steps', ctypes.c_int32), ('nq', ctypes.c_int32), ('pending', ctypes.c_int32),
                 ('done', ctypes.c_int32), ('seq_mn', ctypes.c_int32 * 3), ('seq_mx', ctypes.c_int32 * 3),
                 ('q_count', ctypes.c_int32 * 16), ('q_parent', ctypes.c_int32 * 16), ('q_mn', ctypes.c_int32 * 48),
-                ('q_mx', ctypes.c_int32 * 48), ('pad', ctypes.c_int32)]
+                ('q_mx', ctypes.c_int32 * 48), ('trace_cap', ctypes.c_int32), ('q_score', ctypes.c_double * 16), ('trace', _fp),
+                ('trace_count', _fp)]
+
+
+class LrgBeamTraceRec(ctypes.Structure):
+    _fields_ = [('room', ctypes.c_int32), ('seed', ctypes.c_int32), ('level', ctypes.c_int32), ('n', ctypes.c_int32),
+                ('ordinal', ctypes.c_int32 * 16), ('size', ctypes.c_int32 * 16), ('score', ctypes.c_double * 16)]
 
 
 LRG_ROW_TILE = 32
@@ -238,6 +244,7 @@ _SIGS = {
     'lrg_stream_create_cu_mask': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     'lrg_stream_destroy': (ctypes.c_int, [_fp]),
     'lrg_beam_advance': (ctypes.c_int, [_fp, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(LrgGrowParams), _fp, _fp]),
+    'lrg_beam_ml_score': (ctypes.c_int, [_fp, _fp, ctypes.c_int, ctypes.POINTER(LrgGrowParams), ctypes.POINTER(LrgStepBuffers), _fp]),
     'lrg_beam_level': (ctypes.c_int, [_fp, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(LrgGrowParams),
                                       ctypes.POINTER(LrgWeights), ctypes.POINTER(LrgStepBuffers), ctypes.c_uint, _fp]),
     'lrg_nn1_fill': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp]),

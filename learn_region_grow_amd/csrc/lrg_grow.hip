@@ -1580,6 +1580,26 @@ int lrg_beam_advance(LrgBeamGroup *groups, LrgSlot *slots, LrgRoom *rooms, int n
     return 0;
 }
 
+static int beam_ml_score_impl(LrgSlot *slots, const LrgRoom *rooms, int n_slots, const LrgGrowParams *params, const LrgStepBuffers *b,
+                              bool rows, void *stream) {
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (!slots || !rooms || !b || n_slots <= 0) return LRG_EINVAL - 1;
+    if (!b->center || !b->inlier || !b->neighbor || !b->add_logits || !b->rmv_logits) return LRG_EINVAL - 2;
+    if (params->policy == 2 && (!b->gt_remove || !b->gt_add)) return LRG_EINVAL - 2;
+    if (rows && (!b->sample_in || !b->sample_nb)) return LRG_EINVAL - 2;
+    if (params->n_inlier > LRG_BEAM_ML_MAXSAMPLE || params->n_neighbor > LRG_BEAM_ML_MAXSAMPLE) return LRG_EINVAL - 3;
+    hipLaunchKernelGGL(lrg_beam_ml_score_kernel, dim3(n_slots), dim3(LRG_BEAM_ML_THREADS), 0, (hipStream_t)stream, slots, rooms, *params,
+                       b->inlier, b->neighbor, b->center, b->add_logits, b->rmv_logits, b->gt_remove, b->gt_add,
+                       rows ? b->sample_in : nullptr, rows ? b->sample_nb : nullptr);
+    LRG_LAUNCH_CHECK();
+    return 0;
+}
+
+int lrg_beam_ml_score(LrgSlot *slots, const LrgRoom *rooms, int n_slots, const LrgGrowParams *params, const LrgStepBuffers *b, void *stream) {
+    return beam_ml_score_impl(slots, rooms, n_slots, params, b, b && b->rows_in && b->rows_nb, stream);
+}
+
 int lrg_beam_level(LrgBeamGroup *groups, LrgSlot *slots, LrgRoom *rooms, int n_groups, int beam_width, int search_width, int max_points,
                    const LrgGrowParams *params, const LrgWeights *weights, const LrgStepBuffers *b, unsigned forward_flags, void *stream) {
     int rc = lrg_beam_advance(groups, slots, rooms, n_groups, beam_width, search_width, params, b ? b->stats : nullptr, stream);
@@ -1602,6 +1622,8 @@ int lrg_beam_level(LrgBeamGroup *groups, LrgSlot *slots, LrgRoom *rooms, int n_g
                                rows ? b->rows_nb : nullptr, b->add_logits, b->rmv_logits, b->workspace, b->workspace_bytes, forward_flags,
                                stream)))
         return rc;
+    // --scoring ml: the children's scores, from the draws the mask update is about to take (it moves slot.step, a word of their key, on)
+    if (params->scoring == 1 && (rc = beam_ml_score_impl(slots, rooms, n_slots, params, b, rows, stream))) return rc;
     if ((rc = lrg_mask_update(slots, rooms, n_slots, params, b->inlier, b->neighbor, b->center, b->add_logits, b->rmv_logits, b->gt_remove,
                               b->gt_add, nullptr, nullptr, rows ? b->sample_in : nullptr, rows ? b->sample_nb : nullptr, b->stats, stream)))
         return rc;

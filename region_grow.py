@@ -11,7 +11,9 @@ reference's per-region, per-room and aggregate lines and its timing table, optio
 
 Options of the reference that are kept: --area, --save, --resolution, --lite, --cross-domain/--train-area (model path
 only).  ``--beam B`` selects the beam search of test_beam_search.py (B = BEAM_WIDTH, ``--search-width`` = SEARCH_WIDTH);
-``--restarts R`` (R >= 2) the random-restart search of test_random_restart.py with ``--scoring np`` (its default) or ``ml``.
+``--restarts R`` (R >= 2) the random-restart search of test_random_restart.py; both with ``--scoring np`` (the default) or ``ml``:
+
+    python region_grow.py --area 5 --beam 3 --scoring ml   # test_beam_search.py --area 5 --scoring ml
 
 Random streams.  ``--rng counter`` (default): a counter-based stream keyed by (seed, room, seed point, restart, step) -- the
 rooms of the file grow side by side on the GPU and results do not depend on batching or on the number of GPUs.
@@ -59,9 +61,10 @@ def parse(argv=None):
     ap.add_argument('--feature-size', type=int, default=13, choices=[6, 9, 12, 13])
     ap.add_argument('--restarts', type=int, default=1)
     ap.add_argument('--scoring', default='np', choices=['np', 'ml'],
-                    help="restart score (test_random_restart.py:171-174): 'np' = points of the mask; 'ml' = accumulated log-likelihood of "
-                         "the sampled masks, one scalar per restart (upstream's list reset at :194 breaks it from the second restart on)")
-    ap.add_argument('--beam', type=int, default=0, help='beam width: > 0 selects the beam search of test_beam_search.py (--scoring np)')
+                    help="score of --restarts (test_random_restart.py:171-174) or --beam (test_beam_search.py:275-282): 'np' = points of the mask; "
+                         "'ml' = accumulated log-likelihood of the sampled masks -- one scalar per restart (upstream's list reset at :194 breaks it "
+                         "from the second restart on), or the sort key of every beam level, carried from parent to child")
+    ap.add_argument('--beam', type=int, default=0, help='beam width: > 0 selects the beam search of test_beam_search.py (--scoring np or ml)')
     ap.add_argument('--search-width', type=int, default=3, help='children per beam entry (SEARCH_WIDTH)')
     ap.add_argument('--rng', default='counter', choices=['counter', 'legacy'])
     ap.add_argument('--shared-stream', action='store_true', help='--rng legacy with ONE RandomState(seed) for all rooms, in file order')
@@ -96,18 +99,21 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.beam > 0:
         bad = [o for o, on in (('--rng legacy', args.rng != 'counter'), ('--restarts', args.restarts > 1), ('--lanes', args.lanes > 1),
-                               ('--timing', args.timing), ('--scoring ml', args.scoring != 'np')) if on]
+                               ('--timing', args.timing)) if on]
         if bad:
             ap.error('--beam drives the levels of test_beam_search.py itself; it does not combine with %s' % ', '.join(bad))
     if args.shared_stream and args.rng != 'legacy':
         ap.error('--shared-stream needs --rng legacy')
     if args.timing and (args.rng != 'counter' or args.restarts > 1):
         ap.error('--timing times the greedy loop under the counter stream')
-    if args.scoring == 'ml' and (args.rng != 'counter' or args.restarts < 2):
-        ap.error('--scoring ml needs --restarts R >= 2 and the counter stream')
+    if args.scoring == 'ml' and (args.rng != 'counter' or (args.restarts < 2 and args.beam <= 0)):
+        ap.error('--scoring ml needs --restarts R >= 2 or --beam B, and the counter stream')
     if args.room_list and not args.room_names:
         ap.error('--room-list needs --room-names')
     return args
+
+
+parse_args = parse
 
 
 def model_path(args, area):
@@ -263,7 +269,7 @@ def main(argv=None):
         elif args.beam > 0:
             from learn_region_grow_amd.beam import BeamSearchGrower
             results = BeamSearchGrower(net, rooms_in_flight=in_flight, beam_width=args.beam, search_width=args.search_width, seed=args.seed,
-                                       policy=args.policy, resolution=args.resolution).run(rooms)
+                                       policy=args.policy, resolution=args.resolution, scoring=args.scoring).run(rooms)
         elif args.timing:
             kw['rooms_in_flight'] = 1
             results, buckets = RegionGrower(net, **kw).run_timed(rooms)
