@@ -775,27 +775,7 @@ LRG_ASYNC_ROLE void lrg_async_gemv_unit(lrg_kargs_ptr kp_, int unit_, long long 
 // over k = 8g + 0, 4, 1, 5, 2, 6, 3, 7; the eight partial sums in order; the bias last).
 #define LRG_GEMV_UNIT2_TEAM_FLOATS(P) ((P) / 2 + 8 * LRG_GEMV_UNIT_COLS + 32)      // half a pooled row, partial sums, task words + barrier counter
 #define LRG_GEMV_UNIT2_FLOATS(P) ((P) * LRG_GEMV_UNIT_COLS + 8 * LRG_GEMV_UNIT2_TEAM_FLOATS(P) + 4)
-struct LrgLdsPair {          // two wavefronts meeting at a counter in LDS (LrgLdsTeam's scheme)
-    int *cnt;
-    mutable int target;
-    int *gave_up;
-    __device__ __forceinline__ void sync() const {
-        target += 2;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if ((threadIdx.x & 63) == 0) {
-            __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            long long t_long = 0;
-            for (unsigned spin = 1; __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target; ++spin) {
-                if ((spin & 4095u) == 0) {
-                    const long long now = (long long)wall_clock64();
-                    if (!t_long) t_long = now;
-                    else if (now - t_long > 500000000LL) { if (gave_up) __hip_atomic_store(gave_up, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-                }
-            }
-        }
-        asm volatile("" ::: "memory");
-    }
-};
+// (LrgLdsPair, the two wavefronts' meeting: lrg_fused_tile.inl, beside LrgLdsTeam -- the register branch tiles' wave pairs use it too)
 
 LRG_ASYNC_ROLE void lrg_async_gemv_unit2(lrg_kargs_ptr kp_, int unit_, long long t_launch) {
     const lrg_kargs_ptr kp = lrg_uniform(kp_);
@@ -1779,6 +1759,10 @@ __device__ __forceinline__ void lrg_async_reg_tile_team(lrg_kargs_ptr kp, long l
     int *word = reinterpret_cast<int *>(sm - LRG_ASYNC_CTL_FLOATS);
     int *ticket_word = &A.queue[LRG_AQ_HEAD];
     int next_ticket = -1;
+    // the tile's wave pairs {0, 1}, {2, 3}: a counter each behind the exchange buffer's regions, zeroed here -- ahead of the team's first meeting below
+    LrgLdsPair pair;
+    pair.cnt = reinterpret_cast<int *>(sm + LRG_RT_PAIR_CNT) + (wave >> 1); pair.target = 0; pair.gave_up = &A.queue[LRG_AQ_ABORT];
+    if (tid < 2) reinterpret_cast<int *>(sm + LRG_RT_PAIR_CNT)[tid] = 0;
     for (;;) {
         long long t_task = 0;
         if (tid == 0) {
@@ -1809,10 +1793,10 @@ __device__ __forceinline__ void lrg_async_reg_tile_team(lrg_kargs_ptr kp, long l
         const long r0 = (long)slot * A.front.row_stride + (long)idx * 32;
         if (A.branch_parts == 2)
             lrg_team_branch_tile_reg<2>(P.x, P.center, P.L[1].gout, P.pool + (long)slot * P.pool_stride, P.L[3].w, P.L[4].w, r0, slot, side * LRG_RT_SIDE,
-                                        region + LRG_ASYNC_CTL_FLOATS, team, wave, lane, part);
+                                        region + LRG_ASYNC_CTL_FLOATS, team, pair, wave, lane, part);
         else
             lrg_team_branch_tile_reg<1>(P.x, P.center, P.L[1].gout, P.pool + (long)slot * P.pool_stride, P.L[3].w, P.L[4].w, r0, slot, side * LRG_RT_SIDE,
-                                        region + LRG_ASYNC_CTL_FLOATS, team, wave, lane, 0);
+                                        region + LRG_ASYNC_CTL_FLOATS, team, pair, wave, lane, 0);
         if (LRG_TICKET_EARLY && tid == 0) next_ticket = __hip_atomic_fetch_add(ticket_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         lrg_drain_stores();                                  // conv[1] rows and the pooled maxima are out before the arrival
         team.sync();

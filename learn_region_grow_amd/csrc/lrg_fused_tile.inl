@@ -66,6 +66,29 @@ struct LrgLdsTeam {
         asm volatile("" ::: "memory");
     }
 };
+// Two wavefronts meeting at a counter in LDS: LrgLdsTeam's scheme, the same give-up path (the pooled-product units' half-teams, lrg_async.inl; the wave pairs of
+// a register branch tile, lrg_wave_tile.inl)
+struct LrgLdsPair {
+    int *cnt;
+    mutable int target;
+    int *gave_up;
+    __device__ __forceinline__ void sync() const {
+        target += 2;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if ((threadIdx.x & 63) == 0) {
+            __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            long long t_long = 0;
+            for (unsigned spin = 1; __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target; ++spin) {
+                if ((spin & 4095u) == 0) {
+                    const long long now = (long long)wall_clock64();
+                    if (!t_long) t_long = now;
+                    else if (now - t_long > 500000000LL) { if (gave_up) __hip_atomic_store(gave_up, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+                }
+            }
+        }
+        asm volatile("" ::: "memory");
+    }
+};
 
 // words handed from workgroup to workgroup inside a launch (COH)
 __device__ __forceinline__ float lrg_ld_coh(const float *p) {

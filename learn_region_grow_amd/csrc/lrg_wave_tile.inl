@@ -252,13 +252,15 @@ __device__ __forceinline__ void lrg_wave_pool_tile(const float *h3in, float *poo
 // spread over four pipes (profiles/r06_wave_sweep_*.txt).  The team tile's time, by its cycle stamps (profiles/r04_delay_and_stamps.txt: 52 k cycles for 23 k of MFMA
 // issue), is barriers, LDS round trips and epilogues of the NARROW layers: 25 k cycles before the pooled layer starts, for 272 MFMAs of which every wave issues a
 // quarter or a half.  Here:
-//   layers 0 - 2 (13 -> 64 -> 64 -> 64, 144 MFMAs): every wavefront computes them for ITSELF, in registers (kernels from LDS) -- 9 k cycles of matrix pipe on four
-//     pipes at once, no barrier, no LDS round trip, instead of three passes of ~5 k cycles each with two waves idle;
+//   layers 0 - 2 (13 -> 64 -> 64 -> 64): in registers (kernels from LDS), by WAVE PAIRS -- a wavefront computes one of a layer's two 32-channel blocks (72 MFMAs for
+//     the three layers) and swaps it with its partner's through LDS, lane to lane, after one meeting of the two; no team barrier, no wave idle.  (First form: every
+//     wavefront computed both blocks for itself, 144 MFMAs and nothing shared -- 9 k cycles of each of the four matrix pipes for the same 32 points.)
 //   layer 3 (64 -> 128): wavefront w computes column block w (its kernel columns prefetched from L2 at the task's start), the four blocks meet in LDS -- the tile's ONE
 //     barrier -- and every wavefront takes all 128 channels back as its B operands;
-//   layer 4 (128 -> 512, pooled): wavefront w computes column blocks 4w .. 4w + 3, the kernel columns requested from L2 one whole block (sixteen k-groups) ahead;
-//     the max over the points by the transposing DPP reduction, one atomicMax instruction per pair of blocks.
-// ~190 VGPRs: a tile of lrg_grow_async_worker_kernel (512 threads) only.  Same sums in the same order: bit-identical to the team tile.
+//   layer 4 (128 -> 512, pooled): wavefront w computes column blocks 4w .. 4w + 3 on two accumulators in turn, the kernel columns requested from L2 one whole block
+//     (sixteen k-groups) ahead; the max over the points by the transposing DPP reduction, one atomicMax instruction per pair of blocks -- a block's epilogue issued
+//     behind the next block's MFMAs.
+// ~230 VGPRs: a tile of lrg_grow_async_worker_kernel (512 threads) only.  Same sums in the same order: bit-identical to the team tile.
 #define LRG_RT_W0 0                    // per side: layer 0 (1024 floats), 1, 2 (4096 each); biases of layers 0 - 4 (64, 64, 64, 128, 512)
 #define LRG_RT_W1 1024
 #define LRG_RT_W2 5120
@@ -269,8 +271,8 @@ __device__ __forceinline__ void lrg_wave_pool_tile(const float *h3in, float *poo
 #define LRG_RT_B4 9536
 #define LRG_RT_SIDE 10048
 #define LRG_RT_WEIGHT_FLOATS (2 * LRG_RT_SIDE)
-#define LRG_RT_XCH_LD 132              // floats between two points' rows of the layer-3 exchange (128 + 4: conflict-free 16-byte accesses)
-#define LRG_RT_XCH_FLOATS (32 * LRG_RT_XCH_LD)
+#define LRG_RT_XCH_LD 132              // (the exchange buffer's size is that of its first layout, 32 rows of 128 + 4 floats: the launch plan's LDS sizes stand)
+#define LRG_RT_XCH_FLOATS (32 * LRG_RT_XCH_LD)      // four regions of 1024 floats + the wave pairs' counters: see lrg_rt_xch_region below
 
 // 16 bytes of a kernel image through a buffer descriptor on a wave-uniform base: the lane's offset in ONE register, the k-group's in a scalar -- as global loads every
 // one of a tile's 72 kernel loads had a 64-bit address of its own in registers (offsets beyond the instruction's 4 KB immediate), and the tile spilled
@@ -285,12 +287,12 @@ struct lrg_rt_host_rsrc {};
 #define __builtin_amdgcn_make_buffer_rsrc(...) lrg_rt_host_rsrc()
 __device__ __forceinline__ float4 lrg_rt_ldw(const lrg_rt_host_rsrc &, unsigned, unsigned) { return make_float4(0.f, 0.f, 0.f, 0.f); }
 #endif
-// one 32-channel block over NG k-groups, kernel operands from registers (a[g]), activations h (NG / 4 blocks)
-template <int NG, int NBI>
-__device__ __forceinline__ void lrg_rt_mfma1(f32x16 &acc, const f32x16 (&h)[NBI], const float4 (&a)[NG]) {
+// one 32-channel block of a layer with 64 inputs: k-groups 0 - 3 read the previous layer's block `lo` (channels 0 - 31), 4 - 7 its block `hi`; kernel operands from
+// registers (a[g]) ...
+__device__ __forceinline__ void lrg_rt_mfma_reg(f32x16 &acc, const f32x16 &lo, const f32x16 &hi, const float4 (&a)[8]) {
 #pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        const f32x16 &hb = h[g >> 2];
+    for (int g = 0; g < 8; ++g) {
+        const f32x16 &hb = g < 4 ? lo : hi;
         const int r = 4 * (g & 3);
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].x, hb[r + 0], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].y, hb[r + 1], acc, 0, 0, 0);
@@ -298,14 +300,115 @@ __device__ __forceinline__ void lrg_rt_mfma1(f32x16 &acc, const f32x16 (&h)[NBI]
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].w, hb[r + 3], acc, 0, 0, 0);
     }
 }
+// ... or from LDS (w: float offset of the lane's float4 of the block's k-group 0), requested one k-group ahead
+__device__ __forceinline__ void lrg_rt_mfma_lds(f32x16 &acc, const f32x16 &lo, const f32x16 &hi, int w) {
+    float4 a = lrg_wb_lds4(w);
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+        float4 n = a;
+        if (g + 1 < 8) n = lrg_wb_lds4(w + (g + 1) * 256);
+        const f32x16 &hb = g < 4 ? lo : hi;
+        const int r = 4 * (g & 3);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, hb[r + 0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, hb[r + 1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, hb[r + 2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, hb[r + 3], acc, 0, 0, 0);
+        a = n;
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
 
-// wn: the wavefront's number in its team (0 .. 3); ws: LDS offset (floats) of the side's kernels (LRG_RT_*); xch: LDS offset of the team's exchange buffer;
+// ---- the exchange buffer of a register tile: four regions of 1024 floats, one output block (16 registers x 64 lanes) each, register-major: float4 j of lane l at
+//      256 j + 4 l -- every lane of every wavefront of the team holds the same (point, half), so a block goes lane to lane by linear, conflict-free 16-byte
+//      accesses.  Behind the regions (floats 4096 .. 4223): the two pairs' meeting counters, zero before the team's first tile. ----
+#define LRG_RT_PAIR_CNT 4096           // float offset in the exchange buffer of pair 0's counter (pair 1's: + 1)
+__device__ __forceinline__ int lrg_rt_xch_region(int region, int lane) { return 1024 * region + 4 * lane; }
+// where the tile leaves layer 3's output for its pooled layer (tools/wave_tile_probe.hip reads it there): channels 32 b + 8 j + 4 (lane >> 5) + 0 .. 3 of point
+// lane & 31 are the float4 at this offset of the exchange buffer
+__device__ __forceinline__ int lrg_rt_xch_l3(int b, int j, int lane) { return lrg_rt_xch_region(b ^ 1, lane) + 256 * j; }
+// this wavefront's block out to region `put`, the partner's in from region `get` (both: LDS float offsets of the lane's float4 0)
+template <class PAIR>
+__device__ __forceinline__ void lrg_rt_pair_swap(const f32x16 &mine, f32x16 &theirs, int put, int get, const PAIR &pair) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        *reinterpret_cast<float4 *>(&LRG_WB_SMEM[put + 256 * j]) = make_float4(mine[4 * j], mine[4 * j + 1], mine[4 * j + 2], mine[4 * j + 3]);
+    pair.sync();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4 v = lrg_wb_lds4(get + 256 * j);
+        theirs[4 * j] = v.x; theirs[4 * j + 1] = v.y; theirs[4 * j + 2] = v.z; theirs[4 * j + 3] = v.w;
+    }
+}
+
+// one step of a pooled block's epilogue (st = 0 .. LRG_RT_EPI_STEPS - 1), cut so that each piece fits under one k-group's MFMAs of the NEXT block: the transposing
+// maximum of lrg_wb_rowmax16 level by level (the same operations in the same order), then -- behind an odd block -- the merge with its even partner, the bias and the
+// atomicMax
+#define LRG_RT_EPI_STEPS 10
+struct LrgRtEpi {
+    float l1[8], l2[4], l3[2], m, m_even, mm;
+};
+template <int ST>
+__device__ __forceinline__ void lrg_rt_epi_step(LrgRtEpi &e, const f32x16 &c, bool odd_block, int ch, int bias_off, float *pool, int lane) {
+    const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8, row1 = (lane & 16) != 0;
+    if constexpr (ST < 4) {
+#pragma unroll
+        for (int i = 2 * ST; i < 2 * ST + 2; ++i) {
+            const int r = (i & 3) + 8 * (i >> 2);
+            e.l1[i] = lrg_wb_level<0x141>(c[r], c[r + 4], b2);
+        }
+    } else if constexpr (ST < 6) {
+#pragma unroll
+        for (int i = 2 * (ST - 4); i < 2 * (ST - 4) + 2; ++i) e.l2[i] = lrg_wb_level<0xB1>(e.l1[2 * i], e.l1[2 * i + 1], b0);
+    } else if constexpr (ST == 6) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) e.l3[i] = lrg_wb_level<0x4E>(e.l2[2 * i], e.l2[2 * i + 1], b1);
+    } else if constexpr (ST == 7) {
+        e.m = lrg_wb_level<0x128>(e.l3[0], e.l3[1], b3);
+        if (!odd_block) e.m_even = e.m;
+    } else if constexpr (ST == 8) {
+        if (odd_block) {
+            // rows 0 / 1 of a half hold the maxima over lanes 0-15 / 16-31 of the same channels: the even row keeps the even block, the odd row the odd one
+            const float keep = row1 ? e.m : e.m_even, send = row1 ? e.m_even : e.m;
+            e.mm = fmaxf(keep, __shfl_xor(send, 16));
+        }
+    } else {
+        if (odd_block) {
+            const float v = fmaxf(e.mm + LRG_WB_SMEM[bias_off + ch], 0.f);
+            const int bits = __float_as_int(v);
+            if (bits > 0) atomicMax(reinterpret_cast<int *>(pool + ch), bits);
+        }
+    }
+}
+template <int ST = 0>
+__device__ __forceinline__ void lrg_rt_epi_step_n(int st, LrgRtEpi &e, const f32x16 &c, bool odd_block, int ch, int bias_off, float *pool, int lane) {
+    if constexpr (ST < LRG_RT_EPI_STEPS) {
+        if (st == ST) lrg_rt_epi_step<ST>(e, c, odd_block, ch, bias_off, pool, lane);
+        else lrg_rt_epi_step_n<ST + 1>(st, e, c, odd_block, ch, bias_off, pool, lane);
+    }
+}
+
+// wn: the wavefront's number in its team (0 .. 3), wave-uniform; ws: LDS offset (floats) of the side's kernels (LRG_RT_*); xch: LDS offset of the team's exchange
+// buffer; pair: the meeting of wavefronts {wn, wn ^ 1} (LrgLdsPair on the counter LRG_RT_PAIR_CNT + (wn >> 1) of the exchange buffer, its target kept from tile to tile);
 // w3 / w4: the packed images of layers 3 and 4 in global memory (lrg_pack_weights layout)
 // part / nparts (1 or 2): the tile as two tasks on two teams that each run layers 0 - 3 and HALF of every wavefront's column blocks of the pooled layer (blocks
 // 4 wn + 2 part, + 1): where CUs idle (few slots in flight) the pooled layer's 20 k cycles are what a tile's latency is made of; part 0 alone stores conv[1].
-template <int NPARTS, class TEAM>
+//
+// Layers 0 - 2 BY WAVE PAIRS.  The wavefronts of a team hold the same 32 points, and until this form each of the four computed both output blocks of layers 0 - 2 for
+// itself (144 MFMAs; no barrier, nothing shared).  Here wavefront wn computes block wn & 1 only (72 MFMAs, the same chain per output) and swaps it with its partner's
+// after each layer; pairs {0, 1} and {2, 3} share nothing before layer 3.  Region r of the exchange buffer is used by the pair that r belongs to only, and its
+// writer ALTERNATES:
+//     layer 0: wn writes region wn,     meets, reads region wn ^ 1
+//     layer 1: wn writes region wn ^ 1, meets, reads region wn
+//     layer 2: wn writes region wn,     meets, reads region wn ^ 1
+//     layer 3: wn writes region wn ^ 1 (its column block wn of the layer's four), the TEAM meets, everybody reads all four regions
+// so whoever overwrites a region is the wavefront that read it last -- its only reader since the previous write -- and a wavefront's LDS operations complete in
+// order: ONE meeting per layer and no second one "after the reads", by program order.  The other direction: a region's reader reads behind the meeting at which its
+// writer arrived after an s_waitcnt lgkmcnt(0) (LrgLdsPair::sync).  Layer 3's writes need no meeting of the two pairs either: wn overwrites the region that it alone
+// read.  The tile's callers meet as a team behind the tile, before the next tile's layer 0 writes into the regions that the pooled layer's operands came from.
+// (What the pairs cost against what they save, and the pooled layer's two accumulators: profiles/branch_tile_pairs.txt.)
+template <int NPARTS, class TEAM, class PAIR>
 __device__ __forceinline__ void lrg_team_branch_tile_reg(const float *x, const float *center, float *conv1, float *pool, const float *w3, const float *w4, long r0, int slot,
-                                                         int ws, int xch, const TEAM &team, int wn, int lane, int part = 0) {
+                                                         int ws, int xch, const TEAM &team, const PAIR &pair, int wn, int lane, int part = 0) {
     static_assert(NPARTS == 1 || NPARTS == 2, "one or two tasks per tile");
     const int li = lane & 31, lh = lane >> 5;
     // ---- what comes from memory, requested first: the rows, the centre, this wavefront's columns of layer 3 and its first block of layer 4 ----
@@ -325,57 +428,56 @@ __device__ __forceinline__ void lrg_team_branch_tile_reg(const float *x, const f
     h0[0][4] = __fsub_rn(x1.x, c1.x); h0[0][5] = __fsub_rn(x1.y, c1.y); h0[0][6] = __fsub_rn(x1.z, c1.z); h0[0][7] = __fsub_rn(x1.w, c1.w);
 #pragma unroll
     for (int i = 8; i < 16; ++i) h0[0][i] = 0.f;
-    const int lw = ws + 4 * lane, lb = ws + 4 * lh;
-    f32x16 ha[2], hb[2];
+    const int blk = wn & 1;                        // this wavefront's output block of layers 0 - 2; its partner (wn ^ 1) computes the other
+    const int lw = ws + 4 * lane, lb = ws + 4 * lh + 32 * blk;
+    const int own = xch + lrg_rt_xch_region(wn, lane), par = xch + lrg_rt_xch_region(wn ^ 1, lane);
+    f32x16 mine, theirs, acc;
     // ---- layer 0 ----
     {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) { ha[0][i] = 0.f; ha[1][i] = 0.f; }
-        float4 a0 = lrg_wb_lds4(LRG_RT_W0 + lw), a1 = lrg_wb_lds4(LRG_RT_W0 + 2 * 256 + lw);
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            float4 n0 = a0, n1 = a1;
-            if (g == 0) { n0 = lrg_wb_lds4(LRG_RT_W0 + 256 + lw); n1 = lrg_wb_lds4(LRG_RT_W0 + 3 * 256 + lw); }
-            const int r = 4 * g;
-            ha[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, h0[0][r + 0], ha[0], 0, 0, 0);
-            ha[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, h0[0][r + 0], ha[1], 0, 0, 0);
-            ha[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, h0[0][r + 1], ha[0], 0, 0, 0);
-            ha[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, h0[0][r + 1], ha[1], 0, 0, 0);
-            ha[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, h0[0][r + 2], ha[0], 0, 0, 0);
-            ha[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, h0[0][r + 2], ha[1], 0, 0, 0);
-            ha[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, h0[0][r + 3], ha[0], 0, 0, 0);
-            ha[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, h0[0][r + 3], ha[1], 0, 0, 0);
-            a0 = n0; a1 = n1;
-        }
-        lrg_wb_bias_relu(ha[0], LRG_RT_B0 + lb);
-        lrg_wb_bias_relu(ha[1], LRG_RT_B0 + 32 + lb);
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        const int w = LRG_RT_W0 + 2 * 256 * blk + lw;
+        const float4 a0 = lrg_wb_lds4(w), a1 = lrg_wb_lds4(w + 256);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, h0[0][0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, h0[0][1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, h0[0][2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, h0[0][3], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, h0[0][4], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, h0[0][5], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, h0[0][6], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, h0[0][7], acc, 0, 0, 0);
+        lrg_wb_bias_relu(acc, LRG_RT_B0 + lb);
+        mine = acc;
+        lrg_rt_pair_swap(mine, theirs, own, par, pair);
     }
-    // ---- layer 1 (+ conv[1] for the heads, by the team's first wavefront) ----
+    // ---- layer 1 (+ conv[1] for the heads: the first pair, a block each) ----
     {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) { hb[0][i] = 0.f; hb[1][i] = 0.f; }
-        lrg_wb_mfma2<8, 2>(hb[0], hb[1], ha, LRG_RT_W1 + lw, LRG_RT_W1 + 8 * 256 + lw);
-        lrg_wb_bias_relu(hb[0], LRG_RT_B1 + lb);
-        lrg_wb_bias_relu(hb[1], LRG_RT_B1 + 32 + lb);
-        if (wn == 0 && part == 0) {
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        if (blk) lrg_rt_mfma_lds(acc, theirs, mine, LRG_RT_W1 + 8 * 256 + lw);
+        else lrg_rt_mfma_lds(acc, mine, theirs, LRG_RT_W1 + lw);
+        lrg_wb_bias_relu(acc, LRG_RT_B1 + lb);
+        mine = acc;
+        if (wn < 2 && part == 0) {
             float *gb = conv1 + r0 * LRG_WB_C1;
 #pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    lrg_st_coh4(gb, (unsigned)(li * LRG_WB_C1 + 32 * b + 8 * j + 4 * lh) * 4u, make_float4(hb[b][4 * j], hb[b][4 * j + 1], hb[b][4 * j + 2], hb[b][4 * j + 3]));
+            for (int j = 0; j < 4; ++j)
+                lrg_st_coh4(gb, (unsigned)(li * LRG_WB_C1 + 32 * blk + 8 * j + 4 * lh) * 4u, make_float4(mine[4 * j], mine[4 * j + 1], mine[4 * j + 2], mine[4 * j + 3]));
         }
+        lrg_rt_pair_swap(mine, theirs, par, own, pair);
     }
     // ---- layer 2 ----
     {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) { ha[0][i] = 0.f; ha[1][i] = 0.f; }
-        lrg_wb_mfma2<8, 2>(ha[0], ha[1], hb, LRG_RT_W2 + lw, LRG_RT_W2 + 8 * 256 + lw);
-        lrg_wb_bias_relu(ha[0], LRG_RT_B2 + lb);
-        lrg_wb_bias_relu(ha[1], LRG_RT_B2 + 32 + lb);
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        if (blk) lrg_rt_mfma_lds(acc, theirs, mine, LRG_RT_W2 + 8 * 256 + lw);
+        else lrg_rt_mfma_lds(acc, mine, theirs, LRG_RT_W2 + lw);
+        lrg_wb_bias_relu(acc, LRG_RT_B2 + lb);
+        mine = acc;
+        lrg_rt_pair_swap(mine, theirs, own, par, pair);
     }
     // ---- layer 3: this wavefront's column block, then all four through LDS ----
-    // (the first block of layer 4's kernel columns starts its trip here: behind layers 0 - 2, whose 96 live registers it would have sat beside, and ahead of this
+    // (the first block of layer 4's kernel columns starts its trip here: behind layers 0 - 2, whose live registers it would have sat beside, and ahead of this
     //  layer's 32 MFMAs, the exchange and the barrier -- ~4 k cycles)
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -386,28 +488,35 @@ __device__ __forceinline__ void lrg_team_branch_tile_reg(const float *x, const f
         f32x16 c;
 #pragma unroll
         for (int i = 0; i < 16; ++i) c[i] = 0.f;
-        lrg_rt_mfma1<8, 2>(c, ha, a3);
-        lrg_wb_bias_relu(c, LRG_RT_B3 + 32 * wn + lb);
+        if (blk) lrg_rt_mfma_reg(c, theirs, mine, a3);
+        else lrg_rt_mfma_reg(c, mine, theirs, a3);
+        lrg_wb_bias_relu(c, LRG_RT_B3 + 32 * wn + 4 * lh + ws);
+        // (block wn goes where the partner's layer-2 block was: this wavefront was that region's only reader and is done with it)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            *reinterpret_cast<float4 *>(&LRG_WB_SMEM[xch + li * LRG_RT_XCH_LD + 32 * wn + 8 * j + 4 * lh]) = make_float4(c[4 * j], c[4 * j + 1], c[4 * j + 2], c[4 * j + 3]);
+            *reinterpret_cast<float4 *>(&LRG_WB_SMEM[par + 256 * j]) = make_float4(c[4 * j], c[4 * j + 1], c[4 * j + 2], c[4 * j + 3]);
     }
     team.sync();
 #pragma unroll
     for (int b = 0; b < 4; ++b)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float4 v = lrg_wb_lds4(xch + li * LRG_RT_XCH_LD + 32 * b + 8 * j + 4 * lh);
+            const float4 v = lrg_wb_lds4(xch + lrg_rt_xch_region(b ^ 1, lane) + 256 * j);
             h3[b][4 * j] = v.x; h3[b][4 * j + 1] = v.y; h3[b][4 * j + 2] = v.z; h3[b][4 * j + 3] = v.w;
         }
     // ---- layer 4: column blocks 4 wn .. 4 wn + 3; a k-group's kernel operand is replaced by the NEXT block's right behind its last MFMA (sixteen k-groups = 4 k
     //      cycles of lead over a trip to L2: one load per four MFMAs in the stream, 64 registers instead of the 128 of two whole blocks -- which spilled) ----
+    // Two accumulators take turns: block q's epilogue (the maximum over the points, the merge with its even partner, bias, atomicMax) is issued in pieces BEHIND the
+    // k-groups of block q + 1, whose MFMAs the matrix pipe is then busy with -- with one accumulator the pipe stood still for every block's epilogue; now for the last
+    // block's only.
     const bool row1 = (lane & 16) != 0;
     const int t = lane & 15;
-    float m_even = 0.f;
+    const int ch0 = 32 * (4 * wn + q_lo + (row1 ? 1 : 0)) + 8 * (t >> 2) + 4 * lh + (t & 3);      // the lane's channel of the pair of blocks (q_lo + 0, 1); the next pair's: + 64
+    LrgRtEpi epi;
+    f32x16 cc[2];
 #pragma unroll
     for (int q = 0; q < q_n; ++q) {
-        f32x16 c;
+        f32x16 &c = cc[q & 1];
 #pragma unroll
         for (int i = 0; i < 16; ++i) c[i] = 0.f;
 #pragma unroll
@@ -419,20 +528,13 @@ __device__ __forceinline__ void lrg_team_branch_tile_reg(const float *x, const f
             c = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[g].z, hb4[r + 2], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[g].w, hb4[r + 3], c, 0, 0, 0);
             if (q + 1 < q_n) wa[g] = lrg_rt_ldw(r4, lo, (unsigned)((q + 1) * 16 + g) * 1024u);
+            if (q > 0 && g < LRG_RT_EPI_STEPS) lrg_rt_epi_step_n(g, epi, cc[(q - 1) & 1], ((q - 1) & 1) != 0, ch0 + 32 * ((q - 1) & ~1), ws + LRG_RT_B4, pool, lane);
             __builtin_amdgcn_sched_barrier(0);
         }
-        const float m = lrg_wb_rowmax16(c, lane);
-        if (!(q & 1)) m_even = m;
-        else {
-            // rows 0 / 1 of a half hold the maxima over lanes 0-15 / 16-31 of the same channels: the even row keeps block q - 1, the odd row block q
-            const float keep = row1 ? m : m_even, send = row1 ? m_even : m;
-            const float mm = fmaxf(keep, __shfl_xor(send, 16));
-            const int ch = 32 * (4 * wn + q_lo + q - 1 + (row1 ? 1 : 0)) + 8 * (t >> 2) + 4 * lh + (t & 3);
-            const float v = fmaxf(mm + LRG_WB_SMEM[ws + LRG_RT_B4 + ch], 0.f);
-            const int bits = __float_as_int(v);
-            if (bits > 0) atomicMax(reinterpret_cast<int *>(pool + ch), bits);
-        }
     }
+#pragma unroll
+    for (int st = 0; st < LRG_RT_EPI_STEPS; ++st)
+        lrg_rt_epi_step_n(st, epi, cc[(q_n - 1) & 1], ((q_n - 1) & 1) != 0, ch0 + 32 * ((q_n - 1) & ~1), ws + LRG_RT_B4, pool, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I learn_region_grow_amd/csrc tools/wave_tile_probe.hip -o gpurun_out/wave_tile_probe
 // Checks conv[1] and the pooled maxima bit for bit against a host evaluation in the MFMA formulation's summation order (per output a chain of FMAs over
 // k = 8g + 0, 4, 1, 5, 2, 6, 3, 7, then bias, then ReLU: lrg_fused_tile.inl), and times a task with 1 .. 16 wavefronts per CU on 1 / 64 / 200 CUs.
+// `wave_tile_probe pairs`: the register branch tile on the teams of a 512-thread workgroup, as the free-running worker kernel runs it (pairs_kernel below).
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -68,14 +69,19 @@ __global__ __launch_bounds__(512) void probe_kernel(Args a) {
             for (int l = 0; l < 5; ++l)
                 for (int i = tid; i < bs[l]; i += blockDim.x) lrg_async_smem[side * LRG_RT_SIDE + bo[l] + i] = a.b[l][i];
         }
+        int *pair_cnt = reinterpret_cast<int *>(lrg_async_smem + LRG_RT_WEIGHT_FLOATS + LRG_RT_PAIR_CNT);
+        if (tid < 2) pair_cnt[tid] = 0;
         __syncthreads();
         LrgWgTeam team;
+        const int wn = __builtin_amdgcn_readfirstlane(wave);
+        LrgLdsPair pair;
+        pair.cnt = pair_cnt + (wn >> 1); pair.target = 0; pair.gave_up = nullptr;
         const long long t0 = (long long)__builtin_readcyclecounter();
         for (int it = 0; it < a.iters; ++it) {
             const int tile = (blockIdx.x + it * 7) % a.n_tiles;
             const long r0 = (long)tile * 32;
             lrg_team_branch_tile_reg<1>(a.x, a.center, a.conv1, a.pool + (r0 / a.rows_per_slot) * 512, a.w[3], a.w[4], r0, (int)(r0 / a.rows_per_slot), (tile & 1) * LRG_RT_SIDE,
-                                     LRG_RT_WEIGHT_FLOATS, team, wave, lane);
+                                     LRG_RT_WEIGHT_FLOATS, team, pair, wn, lane);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();                                  // (as the task does before its arrival; the exchange buffer is free again)
         }
@@ -132,7 +138,249 @@ static void layer_ref(const std::vector<float> &in, int rows, int K, const std::
         }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+// `wave_tile_probe pairs`: the register branch tile as the free-running worker kernel runs it (tests/test_gpu_branch_tile_pairs.py) -- teams of a 512-thread
+// workgroup meeting at LDS counters (LrgLdsTeam, LrgLdsPair), two branches with kernels of their own at the two `ws` offsets, one or two parts per tile, tiles back to
+// back, a second branch team or a head team on the workgroup's other half.  The LDS is the worker's: [kernels of both sides][team 0: control words, exchange
+// buffer][team 1: control words, a head tile's buffers].
+#define P_CTL 24
+#define P_TEAM0 (P_CTL + LRG_RT_XCH_FLOATS)
+#define P_TEAM1 (P_CTL + LRG_RH_FLOATS)
+#define P_LDS_FLOATS (LRG_RT_WEIGHT_FLOATS + P_TEAM0 + P_TEAM1)
+struct PArgs {
+    const float *w[2][5], *b[2][5];      // per side: packed images, biases
+    const float *x, *center;
+    float *conv1, *h3, *pool;            // h3: nullable (timing)
+    long long *cycles;                   // [workgroups][2]
+    int tile0, tile_mod, tiles_per_team, tiles_per_slot, nparts, iters, head_beside;      // tile = tile0 + (its number in the launch) % tile_mod
+    LrgFusedProb head;
+};
+__global__ __launch_bounds__(512) void pairs_kernel(PArgs a) {
+    const int tid = threadIdx.x, lane = tid & 63, nteams = (int)blockDim.x >> 8;
+    // (wave-uniform, and known to the compiler as such: the tile's kernel pointers depend on them -- a buffer load whose descriptor is not uniform becomes a loop)
+    const int t = __builtin_amdgcn_readfirstlane(tid >> 8), wn = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);
+    {
+        const int sizes[3] = {1024, 4096, 4096}, offs[3] = {LRG_RT_W0, LRG_RT_W1, LRG_RT_W2};
+        const int bs[5] = {64, 64, 64, 128, 512}, bo[5] = {LRG_RT_B0, LRG_RT_B1, LRG_RT_B2, LRG_RT_B3, LRG_RT_B4};
+        for (int side = 0; side < 2; ++side) {
+            for (int l = 0; l < 3; ++l)
+                for (int i = tid; i < sizes[l] / 4; i += blockDim.x) reinterpret_cast<float4 *>(lrg_async_smem + side * LRG_RT_SIDE + offs[l])[i] = reinterpret_cast<const float4 *>(a.w[side][l])[i];
+            for (int l = 0; l < 5; ++l)
+                for (int i = tid; i < bs[l]; i += blockDim.x) lrg_async_smem[side * LRG_RT_SIDE + bo[l] + i] = a.b[side][l][i];
+        }
+    }
+    const int region = LRG_RT_WEIGHT_FLOATS + t * P_TEAM0, xch = region + P_CTL;
+    int *word = reinterpret_cast<int *>(lrg_async_smem + region);      // [0] the head team's 'go on', [4] the team's counter, [6] team 0: 'done'
+    int *pair_cnt = reinterpret_cast<int *>(lrg_async_smem + xch + LRG_RT_PAIR_CNT);
+    if ((tid & 255) == 0) { word[0] = 1; word[4] = 0; word[6] = 0; }
+    if ((tid & 255) < 2) pair_cnt[tid & 255] = 0;
+    __syncthreads();
+    LrgLdsTeam team;
+    team.cnt = &word[4]; team.target = 0; team.base = t * 256; team.gave_up = nullptr;
+    if (a.head_beside && t == 1) {
+        // head tiles until the branch team is through (bounded)
+        volatile int *done = reinterpret_cast<volatile int *>(lrg_async_smem + LRG_RT_WEIGHT_FLOATS) + 6;
+        struct { __device__ void operator()() const {} } nowait;
+        for (int it = 0; it < 16 * a.iters * a.tiles_per_team; ++it) {
+            if (tid == 256) word[0] = !*done;
+            team.sync();
+            const int go = word[0];
+            if (!go) break;
+            lrg_team_head_tile_reg(a.head, (long)(it % a.tiles_per_team) * 32, 0, xch, team, nowait, wn, lane);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            team.sync();
+        }
+        return;
+    }
+    LrgLdsPair pair;
+    pair.cnt = pair_cnt + (wn >> 1); pair.target = 0; pair.gave_up = nullptr;
+    const int li = lane & 31, lh = lane >> 5;
+    const long long t0 = (long long)__builtin_readcyclecounter();
+    for (int it = 0; it < a.iters * a.tiles_per_team; ++it) {
+        const int tile = a.tile0 + (((int)blockIdx.x * nteams + t) * a.tiles_per_team + it % a.tiles_per_team) % a.tile_mod;
+        const int slot = tile / a.tiles_per_slot, side = slot & 1;
+        const long r0 = (long)tile * 32;
+        for (int part = 0; part < a.nparts; ++part) {
+            if (a.nparts == 2)
+                lrg_team_branch_tile_reg<2>(a.x, a.center, a.conv1, a.pool + (long)slot * 512, a.w[side][3], a.w[side][4], r0, slot, side * LRG_RT_SIDE, xch, team, pair, wn, lane, part);
+            else
+                lrg_team_branch_tile_reg<1>(a.x, a.center, a.conv1, a.pool + (long)slot * 512, a.w[side][3], a.w[side][4], r0, slot, side * LRG_RT_SIDE, xch, team, pair, wn, lane, 0);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            team.sync();                                      // (as the task does before its arrival)
+            if (a.h3 && part == 0) {
+                // layer 3's rows as the tile left them in the exchange buffer: wavefront wn copies block wn
+                for (int j = 0; j < 4; ++j)
+                    *reinterpret_cast<float4 *>(a.h3 + (r0 + li) * 128 + 32 * wn + 8 * j + 4 * lh) = lrg_wb_lds4(xch + lrg_rt_xch_l3(wn, j, lane));
+            }
+            team.sync();                                      // (the next task's first meeting)
+        }
+    }
+    const long long t1 = (long long)__builtin_readcyclecounter();
+    if ((tid & 255) == 0) {
+        a.cycles[blockIdx.x * 2 + t] = t1 - t0;
+        if (t == 0) word[6] = 1;
+    }
+}
+
+// one layer in the MFMA formulation's order; pre (nullable): the value before the ReLU
+static void layer_ref2(const float *in, int rows, int K, const std::vector<float> &w, const std::vector<float> &b, int N, std::vector<float> &out, std::vector<float> *pre) {
+    const int ng = (K + 7) / 8;
+    out.assign((size_t)rows * N, 0.f);
+    if (pre) pre->assign((size_t)rows * N, 0.f);
+    for (int n = 0; n < rows; ++n)
+        for (int c = 0; c < N; ++c) {
+            float acc = 0.f;
+            for (int g = 0; g < ng; ++g)
+                for (int s = 0; s < 4; ++s)
+                    for (int h = 0; h < 2; ++h) {
+                        const int k = 8 * g + 4 * h + s;
+                        const float xv = k < K ? in[(size_t)n * K + k] : 0.f, wv = k < K ? w[(size_t)k * N + c] : 0.f;
+                        acc = fmaf(wv, xv, acc);
+                    }
+            if (pre) (*pre)[(size_t)n * N + c] = acc + b[c];
+            out[(size_t)n * N + c] = fmaxf(acc + b[c], 0.f);
+        }
+}
+static size_t differ(const std::vector<float> &g, const std::vector<float> &r, size_t first, size_t n) {
+    size_t bad = 0;
+    for (size_t i = first; i < first + n; ++i) bad += memcmp(&g[i], &r[i], 4) != 0;
+    return bad;
+}
+
+static int pairs_main() {
+    const int n_tiles = 130, rows = n_tiles * 32, F = 13;      // tiles 0, 1: the single tiles and the two of one slot; 2 .. 129: the two teams' 64 each
+    const int Ks[5] = {F, 64, 64, 64, 128}, Ns[5] = {64, 64, 64, 128, 512};
+    srand(4711);
+    auto rnd = []() { return (float)rand() / RAND_MAX * 2.f - 1.f; };
+    std::vector<float> w[2][5], b[2][5], pk[2][5];
+    for (int side = 0; side < 2; ++side)
+        for (int l = 0; l < 5; ++l) {
+            w[side][l].resize((size_t)Ks[l] * Ns[l]); b[side][l].resize(Ns[l]);
+            const float sc = 1.5f / sqrtf((float)Ks[l]);
+            for (auto &v : w[side][l]) v = rnd() * sc;
+            for (auto &v : b[side][l]) v = rnd() * 0.1f;
+            // every few columns of the pooled layer far below zero: no point's value is positive there, the pooled feature stays 0 (the path without an atomicMax)
+            if (l == 4) for (int c = 0; c < 512; ++c) if (c % (side ? 5 : 7) == 3) b[side][l][c] = -1000.f;
+            pack(w[side][l], Ks[l], Ns[l], pk[side][l]);
+        }
+    std::vector<float> x16((size_t)rows * 16, 0.f), cen((size_t)n_tiles * 16, 0.f);
+    for (auto &v : cen) v = 0.f;
+    for (int s = 0; s < n_tiles; ++s)
+        for (int c = 0; c < F; ++c) cen[s * 16 + c] = (c < 2 || c >= 6) ? rnd() : 0.f;
+    for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < F; ++c) x16[(size_t)r * 16 + c] = rnd() * 2.f;
+    // host chain of tiles [t_lo, t_hi) with `tps` tiles per slot (slot = tile / tps gives the centre, the side and the pooled row); rows of conv[1], layer 3 and
+    // layer 4 are indexed by the global row, pooled rows by tile (NOT merged over a slot's tiles)
+    std::vector<float> r1((size_t)rows * 64), r3((size_t)rows * 128), rp((size_t)n_tiles * 512);
+    int mixed = 0, dead_cols[2] = {0, 0};
+    auto host = [&](int t_lo, int t_hi, int tps, bool stats) {
+        for (int t = t_lo; t < t_hi; ++t) {
+            const int slot = t / tps, side = slot & 1;
+            std::vector<float> xc((size_t)32 * F), h[5], pre[5];
+            for (int n = 0; n < 32; ++n)
+                for (int c = 0; c < F; ++c) xc[(size_t)n * F + c] = x16[((size_t)t * 32 + n) * 16 + c] - cen[slot * 16 + c];
+            layer_ref2(xc.data(), 32, F, w[side][0], b[side][0], 64, h[0], &pre[0]);
+            for (int l = 1; l < 5; ++l) layer_ref2(h[l - 1].data(), 32, Ks[l], w[side][l], b[side][l], Ns[l], h[l], &pre[l]);
+            memcpy(&r1[(size_t)t * 32 * 64], h[1].data(), 32 * 64 * 4);
+            memcpy(&r3[(size_t)t * 32 * 128], h[3].data(), 32 * 128 * 4);
+            for (int c = 0; c < 512; ++c) {
+                float m = 0.f;
+                bool pos = false;
+                for (int n = 0; n < 32; ++n) { m = fmaxf(m, h[4][(size_t)n * 512 + c]); pos |= pre[4][(size_t)n * 512 + c] > 0.f; }
+                rp[(size_t)t * 512 + c] = m;
+                if (stats && !pos) ++dead_cols[t & 1];
+            }
+            if (stats)
+                for (int l = 0; l < 3; ++l)
+                    for (int n = 0; n < 32; ++n) {
+                        bool neg[2] = {false, false}, pos[2] = {false, false};
+                        for (int c = 0; c < 64; ++c) { const float v = pre[l][(size_t)n * 64 + c]; (v < 0.f ? neg : pos)[c >> 5] |= v != 0.f; }
+                        mixed += (neg[0] && pos[1]) || (neg[1] && pos[0]);
+                    }
+        }
+    };
+    PArgs a;
+    memset(&a, 0, sizeof(a));
+    auto up = [&](const std::vector<float> &v) { float *dd; CK(hipMalloc(&dd, v.size() * 4)); CK(hipMemcpy(dd, v.data(), v.size() * 4, hipMemcpyHostToDevice)); return dd; };
+    for (int side = 0; side < 2; ++side)
+        for (int l = 0; l < 5; ++l) { a.w[side][l] = up(pk[side][l]); a.b[side][l] = up(b[side][l]); }
+    a.x = up(x16); a.center = up(cen);
+    float *conv1, *pool, *h3;
+    CK(hipMalloc(&conv1, (size_t)rows * 64 * 4)); CK(hipMalloc(&h3, (size_t)rows * 128 * 4)); CK(hipMalloc(&pool, (size_t)n_tiles * 512 * 4));
+    long long *cyc;
+    CK(hipMalloc(&cyc, 256 * 2 * 8));
+    a.conv1 = conv1; a.h3 = h3; a.pool = pool; a.cycles = cyc; a.iters = 1; a.tile_mod = 128;
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(pairs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    std::vector<float> g1((size_t)rows * 64), g3((size_t)rows * 128), gp((size_t)n_tiles * 512);
+    auto run = [&](int grid, int threads) {
+        CK(hipMemset(conv1, 0xFF, (size_t)rows * 64 * 4)); CK(hipMemset(h3, 0xFF, (size_t)rows * 128 * 4)); CK(hipMemset(pool, 0, (size_t)n_tiles * 512 * 4));
+        hipLaunchKernelGGL(pairs_kernel, dim3(grid), dim3(threads), P_LDS_FLOATS * 4, 0, a);
+        CK(hipDeviceSynchronize());
+        CK(hipMemcpy(g1.data(), conv1, g1.size() * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(g3.data(), h3, g3.size() * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(gp.data(), pool, gp.size() * 4, hipMemcpyDeviceToHost));
+    };
+    size_t bad = 0;
+    // ---- single tiles: tile 0 on side 0, tile 1 on side 1 (a slot each), one workgroup (one team) per tile ----
+    host(0, 2, 1, true);
+    printf("single tile inputs: %d of %d (point, layer) of layers 0 - 2 have a negative pre-activation in one block and a positive one in the other; "
+           "%d + %d pooled columns are non-positive for every point\n", mixed, 2 * 3 * 32, dead_cols[0], dead_cols[1]);
+    for (int nparts = 1; nparts <= 2; ++nparts) {
+        a.tile0 = 0; a.tiles_per_team = 1; a.tiles_per_slot = 1; a.nparts = nparts;
+        run(2, 256);
+        const size_t b1 = differ(g1, r1, 0, 2 * 32 * 64), b3 = differ(g3, r3, 0, 2 * 32 * 128), bp = differ(gp, rp, 0, 2 * 512);
+        printf("single tile, %d part(s): conv[1] %zu of %d differ; layer 3 %zu of %d; pooled %zu of %d\n", nparts, b1, 2 * 32 * 64, b3, 2 * 32 * 128, bp, 2 * 512);
+        bad += b1 + b3 + bp;
+    }
+    // ---- two tiles of one slot: one pooled row, the column-wise maximum of the two tiles' host rows ----
+    {
+        host(0, 2, 2, false);
+        std::vector<float> want(512);
+        size_t from0 = 0, from1 = 0;
+        for (int c = 0; c < 512; ++c) { want[c] = fmaxf(rp[c], rp[512 + c]); from0 += rp[c] > rp[512 + c]; from1 += rp[512 + c] > rp[c]; }
+        a.tile0 = 0; a.tiles_per_team = 1; a.tiles_per_slot = 2; a.nparts = 1;
+        run(2, 256);
+        const size_t bp = differ(gp, want, 0, 512), b1 = differ(g1, r1, 0, 2 * 32 * 64);
+        printf("two tiles, one pooled row: pooled %zu of 512 differ from the column-wise maximum of the two host rows (%zu columns from tile 0, %zu from tile 1); conv[1] %zu differ\n",
+               bp, from0, from1, b1);
+        bad += bp + b1;
+    }
+    // ---- both teams of one workgroup, 64 different tiles each, back to back ----
+    {
+        host(2, 130, 1, false);
+        a.tile0 = 2; a.tiles_per_team = 64; a.tiles_per_slot = 1; a.nparts = 1;
+        run(1, 512);
+        const size_t b1 = differ(g1, r1, (size_t)2 * 32 * 64, (size_t)128 * 32 * 64), b3 = differ(g3, r3, (size_t)2 * 32 * 128, (size_t)128 * 32 * 128), bp = differ(gp, rp, 2 * 512, 128 * 512);
+        printf("both teams, 64 tiles each: conv[1] %zu of %d differ; layer 3 %zu of %d; pooled %zu of %d\n", b1, 128 * 32 * 64, b3, 128 * 32 * 128, bp, 128 * 512);
+        bad += b1 + b3 + bp;
+    }
+    // ---- timing: a team of a 512-thread workgroup alone, beside a second branch team, beside a head team (counter ticks per tile, 64 tiles x 8) ----
+    {
+        std::vector<float> hx((size_t)64 * 32 * 64), hw0((size_t)64 * 256), hw1((size_t)256 * 128), hb0(256), hb1(128), fw(256), fb(2), pk0, pk1;
+        for (auto *v : {&hx, &hw0, &hw1, &hb0, &hb1, &fw, &fb}) for (auto &e : *v) e = rnd() * 0.2f;
+        pack(hw0, 64, 256, pk0); pack(hw1, 256, 128, pk1);
+        LrgFusedProb &H = a.head;
+        H.x = up(hx); H.L[0].w = up(pk0); H.L[0].bias = up(hb0); H.L[1].w = up(pk1); H.L[1].bias = up(hb1); H.fw = up(fw); H.fb = up(fb);
+        float *lout; CK(hipMalloc(&lout, (size_t)64 * 32 * 2 * 4)); H.fout = lout;
+        a.h3 = nullptr; a.tile0 = 2; a.tiles_per_team = 64; a.tiles_per_slot = 1; a.nparts = 1; a.iters = 8;
+        const char *names[3] = {"alone", "beside a second branch team", "beside a head team"};
+        for (int mode = 0; mode < 3; ++mode)
+            for (int grid : {1, 200}) {
+                a.head_beside = mode == 2;
+                hipLaunchKernelGGL(pairs_kernel, dim3(grid), dim3(mode ? 512 : 256), P_LDS_FLOATS * 4, 0, a);
+                CK(hipDeviceSynchronize());
+                std::vector<long long> c((size_t)grid * 2);
+                CK(hipMemcpy(c.data(), cyc, c.size() * 8, hipMemcpyDeviceToHost));
+                double sum = 0;
+                for (int g = 0; g < grid; ++g) sum += (double)c[g * 2] / (a.iters * a.tiles_per_team);
+                printf("REGISTER TILE as a worker's team, %s, grid %3d: %8.0f counter ticks per tile\n", names[mode], grid, sum / grid);
+            }
+    }
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "pairs")) return pairs_main();
     const int n_slots = 6, rows_per_slot = 96, rows = n_slots * rows_per_slot, n_tiles = rows / 32, F = 13;
     const int Ks[5] = {F, 64, 64, 64, 128}, Ns[5] = {64, 64, 64, 128, 512};
     srand(12345);
