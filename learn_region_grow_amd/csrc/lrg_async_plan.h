@@ -150,7 +150,7 @@ struct LrgAsyncKArgs {
 // The free-running launch's switches (A/B runs and test hooks; none changes a label), read from the environment on every call.
 // The shape of a launch that the Python host chooses -- front workgroups, teams, units, parts, CUs, fill-in workgroups, branch_waves -- is set in LrgAsyncBuffers.
 struct LrgAsyncSwitches {
-    int unit_pairs;              // LRG_ASYNC_UNIT_PAIRS: 0 / non-zero forces the units' half-teams off / on; unset: on from 84 slots
+    int unit_pairs;              // LRG_ASYNC_UNIT_PAIRS: 0 / non-zero forces the units' half-teams off / on; unset: on from 84 slots (never on unless the pooled feature has 1024 columns)
     int gemv_batch;              // LRG_ASYNC_GEMV_BATCH: > 0 batched pooled products where they fit (a launch without units); -1: off
     double gemv_batch_us;        // LRG_ASYNC_GEMV_BATCH_US: how long a batch waits for more slots, in us; 1.5
     int tail_heads;              // LRG_ASYNC_TAIL_HEADS: 0 = a head tile of the slot's own per tail; 1: the heads of the tails on the shared tiles too

@@ -23,10 +23,13 @@ size_t lrg_grow_async_queue_bytes(int n_slots) {
     return (LRG_AQ_RING + 2 * async_ring_entries(n_slots) + async_unit_ring_entries(n_slots) + LRG_ASYNC_FILL_RING + 256 + 8 * async_wave_ring_entries(n_slots)) * sizeof(int32_t);
 }
 
-// the network lrg_wave_tile.inl is written for: 9 .. 16 features, branch layers 64, 64, 64, 128, 512 (the LrgNet of the paper, lite 0)
+// the network lrg_wave_tile.inl is written for: 9 .. 16 features, branch layers 64, 64, 64, 128, 512 and heads 256, 128, 2 (the LrgNet of the paper, lite 0).
+// The heads too: lrg_team_head_tile_reg reads the pooled product at a stride of 256, 8 / 32 k-groups and a bias of 128 -- packed_shapes accepts other head stacks
+// on the paper's branches, and those keep the one-kernel launch, whose team tiles are general.  The one test of the network that both async_reg_candidate and
+// async_two_kernels_fit read, so that the units' slot limit follows the launch that is made.
 static bool lrg_wave_branch_fits(const LrgWeights *w) {
     return w->feature_size > 8 && w->feature_size <= LRG_WB_K0 && w->n_conv == 5 && w->conv_ch[0] == LRG_WB_C0 && w->conv_ch[1] == LRG_WB_C1 && w->conv_ch[2] == LRG_WB_C2 &&
-           w->conv_ch[3] == LRG_WB_C3 && w->conv_ch[4] == LRG_WB_C4;
+           w->conv_ch[3] == LRG_WB_C3 && w->conv_ch[4] == LRG_WB_C4 && w->n_head == 3 && w->head_ch[0] == 256 && w->head_ch[1] == 128 && w->head_ch[2] == 2;
 }
 
 // the side stream and the two events of a wave-branch launch (per device; created once)
@@ -224,7 +227,10 @@ static void plan_units(const LrgAsyncBuffers *ab, const LrgWeights *weights, con
     // (half-teams in the units, lrg_async_gemv_unit2: eight tasks in flight per unit, each a little longer.  68 / 100 / 136 slots with register tiles: 992 -> 975,
     //  1 147 -> 1 189, 1 156 -> 1 206 k instance-steps/s (profiles/r06_unit_pairs.txt): on from 84 slots, where the units' capacity is what a slot queues for;
     //  LRG_ASYNC_UNIT_PAIRS=0 / 1 forces)
-    A->unit_pairs = sw.unit_pairs != LRG_ENV_UNSET ? (sw.unit_pairs ? 1 : 0) : (units && n_slots >= 84 ? 1 : 0);
+    // ... of the paper's 2 x 512 pooled features only, forced or not: lrg_async_gemv_unit2 fetches a slot's row as two loads of 512 floats and stages half a row of
+    // P / 2 = 512 -- lite 2 (P = 512) keeps the four-wavefront units, which are general in P
+    const bool pairs_fit = g.P == 1024;
+    A->unit_pairs = !pairs_fit ? 0 : sw.unit_pairs != LRG_ENV_UNSET ? (sw.unit_pairs ? 1 : 0) : (units && n_slots >= 84 ? 1 : 0);
     // without the units: the pooled products in batches (lrg_async.inl, LRG_GEMV_BATCH) where slots become ready faster than a batch's patience --
     // LRG_ASYNC_GEMV_BATCH=0 / =1: off / on whatever the slot count; LRG_ASYNC_GEMV_BATCH_US: the patience
     const int batch_us10 = (int)(10.0 * sw.gemv_batch_us);
@@ -302,7 +308,8 @@ static int plan_pool_rows(const LrgAsyncBuffers *ab, int n_slots, int row_stride
 // beside the front workgroups' and units' kernel.  LrgAsyncBuffers.branch_waves: 1 = REGISTER TILES (a branch tile by a team of four wavefronts, layers 0 - 2 per
 // wavefront in registers, one barrier: the default from LRG_REG_TILE_AUTO_MIN to LRG_REG_TILE_AUTO_MAX slots), 4 / 8 = one-wavefront PREFIX / POOL tasks on CUs that
 // keep the kernels of their stage in LDS, -1 = one kernel.  Needs the rows at a 64-byte stride, the paper's network, no shared tail tiles / per-tile pool rows, and the
-// whole chip (the two grids are sized per shader engine: a CU-masked launch keeps the one-kernel form).
+// whole chip (the two grids are sized per shader engine: a CU-masked launch keeps the one-kernel form).  The paper's network: its branches AND its heads 256, 128, 2
+// (lrg_wave_branch_fits) -- any other head stack on the paper's branches keeps the one-kernel form, as lite 2 does.
 // Reads what steps 1 - 8 left in *A (async_two_kernels_fit).  Decides A->wave_wgs, wave_a_wgs, wave_waves, wave_split, wave_fill, wmask, h3, reg_tiles, rt_bb_every,
 // may raise *n_front, and returns the worker kernel's workgroups (0: one kernel).
 static int plan_two_kernels(const LrgAsyncBuffers *ab, const LrgWeights *weights, const LrgPackedBuffers *b, const LrgAsyncSwitches &sw, int n_slots, int wgs, int cus,

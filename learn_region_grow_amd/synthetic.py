@@ -170,15 +170,17 @@ def area5_shaped_room(target_equalized_points, seed, n_furniture=None, resolutio
 
 
 def make_synthetic_weights(seed=0, feature_size=13, lite=0, gain=2.0, bias_std=0.2, add_bias_shift=0.0,
-                           rmv_bias_shift=-3.0):
+                           rmv_bias_shift=-3.0, conv_channels=None, head_channels=None):
     """name -> float32 array with the checkpoint's variable names and TF shapes ([1,Cin,Cout]).
 
     W ~ U(-a,a), a = gain*sqrt(6/(fan_in+fan_out)) (the reference initialiser
     VarianceScaling(1.0,'fan_avg','uniform'), learn_region_grow_util.py:107, scaled towards the
     spread of trained weights); biases ~ N(0,bias_std); drawn in sorted-name order.  The last
-    layer's class-1 bias is shifted so that regions keep growing (add) and rarely shed (remove)."""
+    layer's class-1 bias is shifted so that regions keep growing (add) and rarely shed (remove).
+    conv_channels / head_channels: other widths than the `lite` tables' (the hidden head layers: the 2-wide last one follows)."""
     lite = 0 if lite is None else int(lite)
-    cc, c2 = CONV_CHANNELS[lite], CONV2_CHANNELS[lite]
+    cc = CONV_CHANNELS[lite] if conv_channels is None else list(conv_channels)
+    c2 = CONV2_CHANNELS[lite] if head_channels is None else list(head_channels)
     shapes = {}
     for pre in ('lrg_', 'lrg_neighbor_'):
         for i, c in enumerate(cc):

@@ -43,12 +43,14 @@ def weight_shapes(feature_size=13, lite=0):
     return shapes
 
 
-def forward(w, inlier, neighbor, lite=0, dtype=np.float32, return_acts=False):
+def forward(w, inlier, neighbor, lite=0, dtype=np.float32, return_acts=False, conv_channels=None, head_channels=None):
     """inlier [B,Ni,F], neighbor [B,Nn,F] -> add [B,Nn,2], rmv [B,Ni,2].
 
-    Computed exactly as the reference graph does (un-hoisted 1088-wide head)."""
+    Computed exactly as the reference graph does (un-hoisted 1088-wide head).  conv_channels / head_channels: the widths of a
+    network that is none of the `lite` tables' (hidden head layers only: the 2-wide last one follows); default: the tables."""
     lite = _lite(lite)
-    cc, c2 = CONV_CHANNELS[lite], CONV2_CHANNELS[lite]
+    cc = CONV_CHANNELS[lite] if conv_channels is None else list(conv_channels)
+    c2 = CONV2_CHANNELS[lite] if head_channels is None else list(head_channels)
     W = {k: np.asarray(v, dtype=dtype) for k, v in w.items()}
     acts = {}
 

@@ -33,7 +33,7 @@ def table(hip_lib):
         done = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
         assert done.returncode == 0, '%s\n%s' % (' '.join(cmd), done.stderr)
     done = subprocess.run([TOOL], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
-    # (non-zero: the sweep no longer holds what it must -- every refusal code, the known-defect rows, at most a fifth refusals)
+    # (non-zero: the sweep no longer holds what it must -- every refusal code, the paper-shape kernels on the paper's network only, at most a fifth refusals)
     assert done.returncode == 0, done.stderr
     return done.stdout.splitlines()
 
@@ -73,6 +73,30 @@ def test_queue_covers_the_rings_the_plan_addresses(table, hip_lib):
             assert 0 < ring_end <= words, '%d slots: the rings end at word %d of a queue of %d' % (n, ring_end, words)
             seen[n] = ring_end
     assert set(SLOTS) <= set(seen)
+
+
+def test_paper_shape_kernels_are_granted_to_the_paper_shape_only(table):
+    """lrg_async_gemv_unit2 (half-teams in the pooled-product units) is written for 1024 pooled features and lrg_team_head_tile_reg (the head tiles of a
+    register-tile launch) for the heads 256, 128, 2.  By label prefix: no lite-2 row (512 pooled features) has unit_pairs, forced rows included; no row of the
+    heads 128, 64, 2 or 256, 64, 2 on the paper's branches has register tiles or any other two-kernel launch (worker_wgs, wave_wgs) -- and the units those
+    networks keep stop at the one-kernel launch's 148 slots, not at the register tiles' 176.  The paper's own rows still have both."""
+    rows = list(granted(table))
+    lite2 = [(k, v) for k, v in rows if k.startswith('lite2/')]
+    heads = [(k, v) for k, v in rows if k.startswith('h128/') or k.startswith('h256x64/')]
+    assert dict(rows)['plan/n_head=2']['reg_tiles'] == 0      # (a head stack of two layers, 256 -> 2, at 68 slots)
+    assert len(lite2) >= 25 and len(heads) >= 50      # (the thirty slot counts of the sweep, less the few that are refused)
+    assert {'lite2/n84', 'lite2/n148', 'lite2/n68/sw.unit_pairs=1', 'lite2/n136/sw.unit_pairs=1'} <= {k for k, _ in lite2}
+    assert {'h128/n1', 'h128/n68/sw.unit_pairs=1', 'h128/n68/w1', 'h256x64/n1', 'h256x64/n176', 'h256x64/n68/w1'} <= {k for k, _ in heads}
+    for label, v in lite2:
+        assert v['unit_pairs'] == 0, label
+        assert v['reg_tiles'] == 0 and v['worker_wgs'] == 0, label
+    assert any(v['gemv_units'] == 4 for k, v in lite2 if k in ('lite2/n84', 'lite2/n148'))      # (the units themselves stay: four wavefronts per task)
+    for label, v in heads:
+        assert v['reg_tiles'] == 0 and v['worker_wgs'] == 0 and v['wave_wgs'] == 0, label
+        n = int(label.split('/')[1][1:])
+        assert v['gemv_units'] == 0 or n <= 148, label
+    paper = dict(rows)
+    assert paper['n47w0u0t0']['reg_tiles'] == 1 and paper['n128w0u0t0']['reg_tiles'] == 1 and paper['n128w0u0t0']['unit_pairs'] == 1
 
 
 def test_both_kernels_lds_fits_a_cu(table):

@@ -238,7 +238,8 @@ def test_fill_in_inside_the_launch_equals_the_fill_in_between_launches(net, monk
 def test_free_run_feature_size_and_lite_variants(cuda_device, F, lite):
     """The reference's feature-size variants (test_region_grow.py:72-77: the first F of the 13 columns) and lite = 2 through the free-running launches --
     rows gathered at a 64-byte stride in 16-byte pieces whatever F is (9 .. 16), the host's fill-in kernels where the in-launch one (13 features) does
-    not apply -- against the lock-step iterations."""
+    not apply -- against the lock-step iterations.  Four slots: lite 2 at the many-slot counts of its pooled-product units (84 and 148 in flight), and the
+    paper's convolutions under other heads, are in tests/test_gpu_free_run_shapes.py."""
     from learn_region_grow_amd.lrgnet import LrgNetHIP
     from learn_region_grow_amd.grow import RegionGrower
     w = synthetic.make_synthetic_weights(feature_size=F, lite=lite, **WEIGHT_KW)

@@ -192,3 +192,24 @@ def test_small_rooms_under_the_bernoulli_policy(net, net12, net_oracles, case):
     audit = sa.Audit(gr, rooms, oracle_runs, form, logits=True)
     assert gr.S == len(rooms) * (2 if case == 'restart_group' else 1)
     audit.run(_free_call(gr) if form == 'free' else gr.enqueue_iteration)
+
+
+def test_lite2_pooled_product_units_at_84_slots_under_the_bernoulli_policy(cuda_device):
+    """Lite 2 (convolutions 64, 64, 256: 512 pooled features, four pooled-product units) with 84 slots in flight, three of them on rooms: the first slot
+    count at which the launch plan used to hand the units' tasks to half-teams written for 1024 pooled features (csrc/lrg_async_plan.inl, plan_units; the
+    plans: tests/test_async_plan.py).  Every step's logits are those of a dense evaluation of the same lite-2 network, one instance at a time, bit for
+    bit -- from the first step on, without waiting for a draw to flip.  The regions and labels of whole runs at 84 and 148 slots:
+    tests/test_gpu_free_run_shapes.py."""
+    from learn_region_grow_amd.lrgnet import LrgNetHIP
+    nt = LrgNetHIP(1, 1, 512, 512, 13, 2, device=cuda_device).load_weights(synthetic.make_synthetic_weights(lite=2, **WEIGHT_KW))
+    rooms = _small_rooms('free')
+    runs = {}
+
+    def oracle(seed):
+        runs[seed] = [sa.oracle_run(r, seed, policy='net', net_fn=gpu_net_fn(nt)) for r in rooms]
+        return [w for w, _ in runs[seed]]
+    seed, _ = seed_without_near_tie(oracle, range(123, 131), SAME_LOGITS_MARGIN)
+    gr = _grower(nt, n_rooms=84, policy='net', seed=seed, free_run=True)
+    audit = sa.Audit(gr, rooms, runs[seed], 'free', logits=True)
+    assert gr.free_run and gr.S == 84
+    audit.run(_free_call(gr))      # (every step of the oracle's runs is met: Audit.run)

@@ -50,7 +50,7 @@ static unsigned crc32(const std::string &s) {
 }
 
 // ---- a case: the arguments of one lrg_grow_async call ----
-enum Net { PAPER, LITE2, HEADS128, WIDE1 };
+enum Net { PAPER, LITE2, HEADS128, WIDE1, HEADS256_64 };
 struct Setup {
     int n_slots, cus, max_points, max_steps, budget_us;
     LrgSlot *slots;
@@ -80,8 +80,8 @@ static Setup make(int n_slots, int cus, int net, int features, int n_inlier, int
     S.slots = at<LrgSlot>(R_SLOTS); S.rooms = at<LrgRoom>(R_ROOMS);
     S.prm.resolution = 0.1f; S.prm.feature_size = features; S.prm.n_inlier = n_inlier; S.prm.n_neighbor = n_neighbor;
     S.prm.cluster_threshold = 10; S.prm.restarts = 1; S.prm.group_size = 1; S.prm.max_region_steps = 0; S.prm.rng_seed = 1; S.prm.policy = 0; S.prm.scoring = 0;
-    static const int conv[4][5] = {{64, 64, 64, 128, 512}, {64, 64, 256, 0, 0}, {64, 64, 64, 128, 512}, {64, 128, 64, 128, 512}};
-    static const int head[4][3] = {{256, 128, 2}, {64, 64, 2}, {128, 64, 2}, {256, 128, 2}};
+    static const int conv[5][5] = {{64, 64, 64, 128, 512}, {64, 64, 256, 0, 0}, {64, 64, 64, 128, 512}, {64, 128, 64, 128, 512}, {64, 64, 64, 128, 512}};
+    static const int head[5][3] = {{256, 128, 2}, {64, 64, 2}, {128, 64, 2}, {256, 128, 2}, {256, 64, 2}};      // (the last: the paper's but for the second width)
     LrgWeights &w = S.w;
     w.feature_size = features; w.n_conv = net == LITE2 ? 3 : 5; w.n_head = 3;
     for (int i = 0; i < w.n_conv; ++i) {
@@ -197,7 +197,7 @@ static int rows = 0, refused = 0;
 static std::set<int> check_codes, plan_codes;
 static std::set<std::string> labels;
 static std::map<int, long long> ring_end;      // by slot count: the end of the last wave ring over the granted plans, in words of the queue
-static int defect_pairs = 0, defect_reg = 0, lds_over = 0;
+static int lite2_rows = 0, lite2_pairs = 0, heads_rows = 0, heads_reg = 0, lds_over = 0;
 
 static void run(const std::string &label, const Setup &S) {
     if (!labels.insert(label).second) { fprintf(stderr, "async_plan_table: label used twice: %s\n", label.c_str()); exit(2); }
@@ -219,8 +219,8 @@ static void run(const std::string &label, const Setup &S) {
         const long long end = LRG_AQ_WAVE_RING(A, 8);
         if (end > ring_end[S.n_slots]) ring_end[S.n_slots] = end;
         if (plan.lds > 160 * 1024 || plan.worker_lds > 160 * 1024) ++lds_over;
-        if (S.net == LITE2 && S.n_slots >= 84 && A.gemv_units && A.unit_pairs == 1) ++defect_pairs;
-        if (S.net == HEADS128 && A.reg_tiles == 1) ++defect_reg;
+        if (S.net == LITE2) { ++lite2_rows; if (A.unit_pairs) ++lite2_pairs; }
+        if (S.net == HEADS128 || S.net == HEADS256_64) { ++heads_rows; if (A.reg_tiles || plan.two_kernels) ++heads_reg; }
     }
     if (full) printf("%s", text.c_str());
 }
@@ -262,6 +262,8 @@ int main(int argc, char **argv) {
         snprintf(l, sizeof(l), "h128/n%d", n); run(l, make(n, 256, HEADS128, 13, 512, 512));
         snprintf(l, sizeof(l), "p13/32x64/n%d", n); run(l, make(n, 256, PAPER, 13, 32, 64));
     }
+    // (behind the sweep above, whose order the golden table keeps: the paper's network but for the second head width -- the same C, the same P)
+    for (int n : SLOTS) { snprintf(l, sizeof(l), "h256x64/n%d", n); run(l, make(n, 256, HEADS256_64, 13, 512, 512)); }
 
     // one argument at a time
     for (int n : {8, 68, 136, 272}) {
@@ -316,6 +318,15 @@ int main(int argc, char **argv) {
     vary("n136/sw.unit_pairs=0", paper(136), [](Setup &S) { S.sw.unit_pairs = 0; });
     vary("n68/sw.unit_pairs=1", paper(68), [](Setup &S) { S.sw.unit_pairs = 1; });
     vary("n272/sw.unit_pairs=1", paper(272), [](Setup &S) { S.sw.unit_pairs = 1; });
+    // (forced half-teams: granted to the paper's 1024 pooled features only, whatever the heads behind them)
+    vary("lite2/n68/sw.unit_pairs=1", make(68, 256, LITE2, 13, 512, 512), [](Setup &S) { S.sw.unit_pairs = 1; });
+    vary("lite2/n136/sw.unit_pairs=1", make(136, 256, LITE2, 13, 512, 512), [](Setup &S) { S.sw.unit_pairs = 1; });
+    vary("h128/n68/sw.unit_pairs=1", make(68, 256, HEADS128, 13, 512, 512), [](Setup &S) { S.sw.unit_pairs = 1; });
+    // (register tiles asked for by name, and wave-branch tasks: another head stack keeps the one-kernel launch)
+    for (int bw : {1, 4}) {
+        vary("h128/n68/w" + std::to_string(bw), make(68, 256, HEADS128, 13, 512, 512), [&](Setup &S) { S.ab.branch_waves = bw; });
+        vary("h256x64/n68/w" + std::to_string(bw), make(68, 256, HEADS256_64, 13, 512, 512), [&](Setup &S) { S.ab.branch_waves = bw; });
+    }
     for (int n : {200, 400}) {
         const std::string p = "n" + std::to_string(n) + "/";
         vary(p + "sw.gemv_batch=1/u-1", paper(n), [](Setup &S) { S.sw.gemv_batch = 1; S.ab.gemv_units = -1; });
@@ -382,9 +393,11 @@ int main(int argc, char **argv) {
         if (!check_codes.count(LRG_EINVAL + code)) { fprintf(stderr, "async_plan_table: no case of lrg_async_check returns LRG_EINVAL - %d\n", -code); bad = 1; }
     for (int code : {-6, -7, -8, -9})
         if (!plan_codes.count(LRG_EINVAL + code)) { fprintf(stderr, "async_plan_table: no case of lrg_async_plan returns LRG_EINVAL - %d\n", -code); bad = 1; }
-    // (the two defects ADVICE.md names, with today's values: the tables of the changes that mend them show which launches move)
-    if (!defect_pairs) { fprintf(stderr, "async_plan_table: no lite-2 row from 84 slots with units and unit_pairs 1\n"); bad = 1; }
-    if (!defect_reg) { fprintf(stderr, "async_plan_table: no row of the heads 128, 64, 2 with reg_tiles 1\n"); bad = 1; }
+    // (the two gates of kernels written for the paper's shape only: half-teams in the units need 1024 pooled features -- lrg_async_gemv_unit2 -- and a two-kernel
+    //  launch, with its register head tiles, the heads 256, 128, 2 -- lrg_team_head_tile_reg; no granted row of another network may show either)
+    if (!lite2_rows || !heads_rows) { fprintf(stderr, "async_plan_table: no granted row of lite 2 / of another head stack on the paper's branches\n"); bad = 1; }
+    if (lite2_pairs) { fprintf(stderr, "async_plan_table: %d lite-2 rows (512 pooled features) with unit_pairs 1\n", lite2_pairs); bad = 1; }
+    if (heads_reg) { fprintf(stderr, "async_plan_table: %d rows of the heads 128, 64, 2 / 256, 64, 2 with a two-kernel launch\n", heads_reg); bad = 1; }
     if (lds_over) { fprintf(stderr, "async_plan_table: %d granted plans ask for more than 160 KB of LDS\n", lds_over); bad = 1; }
     for (int n : SLOTS)
         if (!ring_end.count(n)) { fprintf(stderr, "async_plan_table: no granted plan at %d slots\n", n); bad = 1; }
