@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 21
+#define LRG_ABI_VERSION 22
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -1165,6 +1165,44 @@ int lrg_metrics_batch(const int32_t *labels, const int32_t *gt_row, const int32_
 /* test_region_grow.py:319-355, test_mcpnet.py:146-170: the per-room status words of the last lrg_metrics_batch on this workspace. */
 int lrg_metrics_batch_status(const void *workspace, const int32_t *room_start, const int32_t *gt_start, const int32_t *n_cluster, int n_rooms,
                              int32_t *host_status_per_room, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 22.  Training tuples for LrgNet (stage_data.py:104-240) on the device, under the counter stream (csrc/lrg_rng.h: key (rng_seed,
+ * LrgRoom.room_id), purposes STAGE_SEED 5 .. STAGE_NEIGHBOR 10; a build extension as in the grow loop -- the reference draws from one
+ * legacy stream).  Of LrgRoom the calls read points, voxels, obj_id, n and room_id and write visited.
+ *
+ * lrg_stage_teacher: one workgroup per entry of room_list [n_list] (indices into `rooms`), all in one launch; no workgroup waits for
+ * another.  It runs the loop of stage_data.py:104-231 for the room: the seed order is the Feistel permutation of the room's points; per
+ * object the mistake probabilities, per pass the candidates (inside the dilated box, neither current nor visited) and the current points,
+ * both in point-index order, the teacher's decisions, the stuck flag, the rule that a removal which would empty the mask is skipped
+ * (:213), the new box, completion, early termination, cluster_threshold and `visited`.  It emits no float rows.  Room r works in
+ * cur_mask [ws_off[r] ..) (n bytes), lists [2 ws_off[r] ..) (2 n words) and objects [4 ws_off[r] ..) (4 n words), and writes into its
+ * arena, arena [arena_off[r] .. + arena_cap[r]) words: list entries from the front (a point index, bit 31 = its remove / add flag),
+ * 8-word tuple headers from the back (tuple k at arena_cap - 8 (k + 1): inlier count, neighbour count, offsets of both lists in the
+ * room's arena, `complete` = (float)((double)inter / (double)union) as bits, the object's seed, the pass, 0).  A side of more than
+ * max_points entries is emitted as its Feistel subset, and the "continue growing" test of :209 then looks at the emitted flags (:182,
+ * :192).  Per stored object: objects [4 ws_off[r] + 4 j ..) = steps, seed, points of the final mask, its IoU as float bits.
+ * status [4 r ..) = LRG_STAGE_OK / LRG_STAGE_OVERFLOW (a tuple would overrun the arena: the room stopped there; run it again with a
+ * larger arena, the draws are pure functions) / LRG_STAGE_ITER_CAP (an object's loop reached max_iters passes), tuples, arena words
+ * used, objects stored.  visited and cur_mask of a listed room are cleared by the launch itself.
+ * Limits: rooms below 2^30 points, 1 <= max_points <= LRG_STAGE_MAX_POINTS.  Refused with LRG_EINVAL - 100 .. - 103.
+ *
+ * lrg_stage_tuples: one workgroup per row of table [n_tuples, 8] = room, inlier count, neighbour count, offsets of the two lists in
+ * `arena` (absolute), first output row of the inlier side, of the neighbour side, 0.  It takes numpy.median's float32 result of the
+ * channels 0, 1 and 6 .. F-1 over the emitted inlier rows (:234-235), subtracts it from both sides in float32 (:236-240) and writes
+ * points [rows, F] / remove [rows] and neighbor_points [rows, F] / add [rows].  Refused with LRG_EINVAL - 105 .. - 107. */
+#define LRG_STAGE_MAX_POINTS 1024
+#define LRG_STAGE_MAX_FEATURES 64
+#define LRG_STAGE_OK 0
+#define LRG_STAGE_OVERFLOW 1
+#define LRG_STAGE_ITER_CAP 2
+/* stage_data.py:104-231 */
+int lrg_stage_teacher(const LrgRoom *rooms, const int32_t *room_list, int n_list, const int64_t *ws_off, uint8_t *cur_mask, int32_t *lists,
+                      int32_t *arena, const int64_t *arena_off, const int32_t *arena_cap, int32_t *objects, int32_t *status, uint32_t rng_seed,
+                      int max_points, int cluster_threshold, int max_steps, int max_iters, void *stream);
+/* stage_data.py:233-240 */
+int lrg_stage_tuples(const LrgRoom *rooms, const int32_t *arena, const int32_t *table, int n_tuples, int F, float *points, int32_t *remove,
+                     float *neighbor_points, int32_t *add, void *stream);
 
 #ifdef __cplusplus
 }

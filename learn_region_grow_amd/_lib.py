@@ -12,9 +12,9 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
            'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip', 'lrg_pointnet_train.hip',
-           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip', 'lrg_mcpnet_train.hip']
+           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip', 'lrg_mcpnet_train.hip', 'lrg_stage.hip']
 
-LRG_ABI_VERSION = 21      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 22      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -133,6 +133,8 @@ LRG_VGRID_MAX_CELLS = 1 << 26          # dense voxel grid of a room (LrgRoom.vgr
 LRG_VGRID_TOTAL_CELLS = 1 << 31        # ... and 8 GB for the rooms of one grower
 LRG_DONE_RING = 1020
 LRG_STATS_WORDS = 4 + LRG_DONE_RING
+LRG_STAGE_MAX_POINTS = 1024
+LRG_STAGE_OK, LRG_STAGE_OVERFLOW, LRG_STAGE_ITER_CAP = range(3)      # lrg_stage_teacher: a room's status word
 LRG_FPFH_LISTS = 1                     # lrg_fpfh flags: the pair pass stores the neighbour lists for the gather pass
 
 
@@ -351,6 +353,8 @@ _SIGS = {
     'lrg_metrics_batch_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.c_int]),
     'lrg_metrics_batch': (ctypes.c_int, [_fp] * 5 + [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.c_int, ctypes.c_uint, _fp, ctypes.c_size_t] + [_fp] * 7),
     'lrg_metrics_batch_status': (ctypes.c_int, [_fp] + [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp]),
+    'lrg_stage_teacher': (ctypes.c_int, [_fp, _fp, ctypes.c_int] + [_fp] * 8 + [ctypes.c_uint32] + [ctypes.c_int] * 4 + [_fp]),
+    'lrg_stage_tuples': (ctypes.c_int, [_fp] * 3 + [ctypes.c_int] * 2 + [_fp] * 5),
 }
 
 EXPORTS = sorted(_SIGS)

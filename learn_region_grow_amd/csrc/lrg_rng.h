@@ -11,6 +11,13 @@
 #define LRG_PURPOSE_ADD 2u
 #define LRG_PURPOSE_RMV 3u
 #define LRG_PURPOSE_MCP_NEIGHBOR 4u      // MCPNet's 50 neighbour rows (lrg_mcpnet.hip), seed_point = the point's index in its room
+// the staging teacher (lrg_stage.hip): seed_point = the object's seed, step = the pass of its loop, slot = the point's index in its room
+#define LRG_PURPOSE_STAGE_SEED 5u        // the room's seed order (Feistel keys at (0, 0, 0))
+#define LRG_PURPOSE_STAGE_PROB 6u        // the object's mistake probabilities: slot 0 add, slot 1 remove
+#define LRG_PURPOSE_STAGE_ADD 7u
+#define LRG_PURPOSE_STAGE_RMV 8u
+#define LRG_PURPOSE_STAGE_INLIER 9u      // Feistel keys of an emitted side's subset
+#define LRG_PURPOSE_STAGE_NEIGHBOR 10u
 #define LRG_PURPOSE_PERMKEY 0x80u
 
 struct lrg_u32x4 { uint32_t x, y, z, w; };
