@@ -1806,9 +1806,8 @@ __device__ __forceinline__ void lrg_async_reg_tile_team(lrg_kargs_ptr kp, long l
 // ---- team 1 of a register-tile CU: ring 1 -- head tiles as REGISTER HEAD TILES (lrg_team_head_tile_reg), pooled blocks where there are no units (inlined into
 //      the worker kernel: ~240 VGPRs) ----
 #define LRG_RT_TEAM1_FLOATS (LRG_ASYNC_CTL_FLOATS + LRG_RH_FLOATS)
-__device__ __forceinline__ void lrg_async_reg_head_team(lrg_kargs_ptr kp, long long t_launch) {
+__device__ __forceinline__ void lrg_async_reg_head_team(lrg_kargs_ptr kp, long long t_launch, int sm_off) {      // sm_off: LDS offset (floats) of the team's control words
     const LrgAsyncArgs &A = LRG_ASYNC_KARGS().A;
-    const int sm_off = LRG_RT_WEIGHT_FLOATS + LRG_RT_TEAM0_FLOATS;
     float *sm = lrg_async_smem + sm_off + LRG_ASYNC_CTL_FLOATS;
     LrgLdsTeam team = lrg_async_team(A, sm, 0);
     const int tid = team.tid(), lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1925,18 +1924,24 @@ __global__ __launch_bounds__(LRG_WORKER_THREADS) void lrg_grow_async_worker_kern
     }
     if (K.A.reg_tiles) {
         // a register-tile CU: [the kernels of layers 0 - 2 and the biases of both branches][team 0: control words, layer-3 exchange][team 1: a tile team's region]
-        lrg_rt_load_kernels(K.A.prob[0], 0, tid, LRG_WORKER_THREADS);
-        lrg_rt_load_kernels(K.A.prob[1], LRG_RT_SIDE, tid, LRG_WORKER_THREADS);
-        const int sm_off = (tid >> 8) ? LRG_RT_WEIGHT_FLOATS + LRG_RT_TEAM0_FLOATS : LRG_RT_WEIGHT_FLOATS;
+        // Its role (lrg_rt_role, lrg_async_plan.h) says which ring each team serves.  A HEAD2 CU runs no branch tile: it loads no branch kernels, and its team 0 -- a
+        // second head team -- has its region where they would lie.  One call site per team function: the register allocation is the kernel's.
+        const int role = lrg_rt_role(w, K.A.rt_bb_every, K.A.rt_head_every);
+        const int t = __builtin_amdgcn_readfirstlane(tid >> 8), ring = lrg_rt_team_ring(role, t);
+        if (role != LRG_RT_HEAD2) {
+            lrg_rt_load_kernels(K.A.prob[0], 0, tid, LRG_WORKER_THREADS);
+            lrg_rt_load_kernels(K.A.prob[1], LRG_RT_SIDE, tid, LRG_WORKER_THREADS);
+        }
+        const int sm_off = t ? LRG_RT_WEIGHT_FLOATS + LRG_RT_TEAM0_FLOATS : role == LRG_RT_HEAD2 ? 0 : LRG_RT_WEIGHT_FLOATS;
         int *word = reinterpret_cast<int *>(lrg_async_smem + sm_off);
         if ((tid & 255) == 0) { word[4] = 0; word[5] = 0; }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        if (!(tid >> 8)) lrg_async_reg_tile_team(kp, t_launch, LRG_RT_WEIGHT_FLOATS);
-        else if (K.A.fill_list && w < K.A.fill_wgs) lrg_async_worker(kp, sm_off, t_launch, 1);      // (the fill-in ring on a few of them)
-        else if (K.A.rt_bb_every > 0 && w % K.A.rt_bb_every == K.A.rt_bb_every - 1) lrg_async_reg_tile_team(kp, t_launch, sm_off);      // (a CU with two branch teams)
+        if (t && K.A.fill_list && w < K.A.fill_wgs) lrg_async_worker(kp, sm_off, t_launch, 1);      // (the fill-in ring on a few of them)
+        else if (ring < 0) return;                                                                 // (BRANCH1: the branch team has the SIMDs to itself)
+        else if (ring == 0) lrg_async_reg_tile_team(kp, t_launch, sm_off);
         else if (K.A.reg_tiles == 2) lrg_async_worker(kp, sm_off, t_launch, 2);                    // (LRG_ASYNC_RT_TEAM_HEADS=1: the head tiles as team tiles)
-        else lrg_async_reg_head_team(kp, t_launch);
+        else lrg_async_reg_head_team(kp, t_launch, sm_off);
         return;
     }
     const int t = tid >> 8;

@@ -118,9 +118,12 @@ struct LrgAsyncArgs {
     int wmask;                   // entries of one wave ring - 1 (power of two)
     float *h3[2];                // [row_cap, 128] per side: layer 3's output rows, from the PREFIX to the POOL tasks
     int rt_bb_every;             // register tiles: every so-manyth worker CU runs branch tiles on BOTH its teams (0: none)
-    int unit_pairs;              // 1: the pooled-product units run their tasks on half-teams of two wavefronts (lrg_async_gemv_unit2)
+    int rt_head_every;           // register tiles, CUs by role (lrg_rt_role below): of every so many CUs of an XCD's share of the worker grid one runs head tiles on both
+                                 // teams, the others branch tiles on team 0 alone (0: none; never beside rt_bb_every)
+    int unit_pairs;             // 1: the pooled-product units run their tasks on half-teams of two wavefronts (lrg_async_gemv_unit2)
     int reg_tiles;               // 1: the worker kernel's workgroups are all alike -- team 0 runs the branch tiles of ring 0 as REGISTER TILES (lrg_team_branch_tile_reg: a team
                                  // of four wavefronts per tile, layers 0 - 2 per wavefront in registers, one barrier), team 1 the pooled blocks and head tiles of ring 1
+                                 // -- unless the CUs have roles (rt_bb_every, rt_head_every: lrg_rt_role below)
     int worker_base;             // blockIdx.x of the first worker workgroup in the kernel that runs the tile teams (n_front + gemv_units, or wave_wgs in the worker kernel)
     int total_wgs;               // workgroups of the launch in all (both kernels): what the start rendezvous waits for
     int max_steps;               // evaluations per slot in this launch
@@ -134,6 +137,28 @@ struct LrgAsyncArgs {
                                  // 8 + 2 t busy ticks of task type t, 9 + 2 t their number; 16 ticks teams waited for a task, 17 waits;
                                  // the prepared mask update: 7 ticks spent making records, 19 records tried, 18 front steps that used one
 };
+
+// ---- the roles of a register-tile CU (LrgAsyncArgs.reg_tiles) ----
+// Which ring's tickets the two teams of worker workgroup w take.  The matrix pipe is per SIMD and the two teams' wavefronts sit two to a SIMD: a head tile's MFMAs
+// come straight out of the branch tile beside it.  By role a branch tile has its SIMDs to itself and head tiles share theirs with head tiles.
+//   MIXED    team 0 branch tiles (ring 0), team 1 head tiles (ring 1)
+//   BRANCH2  both teams branch tiles                                       (rt_bb_every)
+//   BRANCH1  team 0 branch tiles, team 1's wavefronts leave at the start   (rt_head_every: the CUs that are not HEAD2)
+//   HEAD2    both teams head tiles, no branch kernels in LDS               (rt_head_every)
+// The worker grid goes round the 8 XCDs workgroup by workgroup, whichever XCD the round starts on: w / 8 counts the CUs of one XCD's share, so picking by it
+// gives every XCD the same mix (and every XCD's L2 the kernels of both roles).  The one definition: the worker kernel (lrg_async.inl) and the host's table
+// (tools/async_plan_table.hip --roles) both read it.
+enum LrgRtRole { LRG_RT_MIXED = 0, LRG_RT_BRANCH2 = 1, LRG_RT_BRANCH1 = 2, LRG_RT_HEAD2 = 3 };
+__host__ __device__ inline int lrg_rt_role(int w, int rt_bb_every, int rt_head_every) {
+    if (rt_head_every > 0) return (w >> 3) % rt_head_every == rt_head_every - 1 ? LRG_RT_HEAD2 : LRG_RT_BRANCH1;
+    if (rt_bb_every > 0 && w % rt_bb_every == rt_bb_every - 1) return LRG_RT_BRANCH2;
+    return LRG_RT_MIXED;
+}
+// the ring team t (0, 1) of a CU of that role serves; -1: the team leaves
+__host__ __device__ inline int lrg_rt_team_ring(int role, int t) {
+    if (t == 0) return role == LRG_RT_HEAD2 ? 1 : 0;
+    return role == LRG_RT_BRANCH2 ? 0 : role == LRG_RT_BRANCH1 ? -1 : 1;
+}
 
 // ---- the launch's arguments ----
 // ONE kernel parameter, so that every role below can be a function of its own (own register allocation: the tile code needs 112
@@ -155,7 +180,9 @@ struct LrgAsyncSwitches {
     double gemv_batch_us;        // LRG_ASYNC_GEMV_BATCH_US: how long a batch waits for more slots, in us; 1.5
     int tail_heads;              // LRG_ASYNC_TAIL_HEADS: 0 = a head tile of the slot's own per tail; 1: the heads of the tails on the shared tiles too
     int rt_bb_every;             // LRG_ASYNC_RT_BB_EVERY: every so-manyth register-tile CU runs branch tiles on both teams (0: none); unset: 4 from 120 slots, else 0
-    int wave_fronts;             // LRG_ASYNC_WAVE_FRONTS: > 0 front workgroups of a two-kernel launch; 0: as many as the shader engines they claim have room for
+    int rt_head_every;           // LRG_ASYNC_RT_HEAD_EVERY: register-tile CUs by role -- one CU in so many (per XCD) runs head tiles on both teams, the others branch tiles on one
+                                 // (0: none, every CU mixed); a non-zero value turns rt_bb_every off; unset: see plan_two_kernels
+    int wave_fronts;            // LRG_ASYNC_WAVE_FRONTS: > 0 front workgroups of a two-kernel launch; 0: as many as the shader engines they claim have room for
     int wave_extra_wgs;          // LRG_ASYNC_WAVE_EXTRA_WGS: (test hook) worker workgroups beyond what the shader engines hold; 0
     int wave_wgs;                // LRG_ASYNC_WAVE_WGS: > 0 wave-branch CUs; 0: 62 % (with units) | 55 % of the worker CUs
     int wave_a_wgs;              // LRG_ASYNC_WAVE_A_WGS: > 0 PREFIX CUs among them; 0: a fifth

@@ -75,6 +75,7 @@ LrgAsyncSwitches lrg_async_switches() {
     s.gemv_batch_us = lrg_env_real("LRG_ASYNC_GEMV_BATCH_US", 1.5);
     s.tail_heads = lrg_env_int("LRG_ASYNC_TAIL_HEADS", 1);
     s.rt_bb_every = lrg_env_int("LRG_ASYNC_RT_BB_EVERY", LRG_ENV_UNSET);
+    s.rt_head_every = lrg_env_int("LRG_ASYNC_RT_HEAD_EVERY", LRG_ENV_UNSET);
     s.wave_fronts = lrg_env_int("LRG_ASYNC_WAVE_FRONTS", 0);
     s.wave_extra_wgs = lrg_env_int("LRG_ASYNC_WAVE_EXTRA_WGS", 0);
     s.wave_wgs = lrg_env_int("LRG_ASYNC_WAVE_WGS", 0);
@@ -311,13 +312,27 @@ static int plan_pool_rows(const LrgAsyncBuffers *ab, int n_slots, int row_stride
 // whole chip (the two grids are sized per shader engine: a CU-masked launch keeps the one-kernel form).  The paper's network: its branches AND its heads 256, 128, 2
 // (lrg_wave_branch_fits) -- any other head stack on the paper's branches keeps the one-kernel form, as lite 2 does.
 // Reads what steps 1 - 8 left in *A (async_two_kernels_fit).  Decides A->wave_wgs, wave_a_wgs, wave_waves, wave_split, wave_fill, wmask, h3, reg_tiles, rt_bb_every,
-// may raise *n_front, and returns the worker kernel's workgroups (0: one kernel).
+// rt_head_every (as asked for: plan_roles grants it), may raise *n_front, and returns the worker kernel's workgroups (0: one kernel).
+//
+// Register-tile CUs by role (lrg_rt_role, lrg_async_plan.h; profiles/cu_roles.txt): of every 3 CUs of an XCD's share one runs head tiles on both teams, two run
+// branch tiles on one team -- 128 branch-only and 64 head-only CUs of 192.  A branch tile beside a head team that never pauses takes 50.4 k ticks, alone 32.0 k; a
+// head tile beside a head team 28.0 k, beside a branch team 36.2 k.  Plain benchmark, k instance-steps/s, every CU mixed | one in 3 (two runs each, no overlap up to
+// 76): 4 slots 101 | 102, 8: 198 | 206, 16: 364 | 376, 24: 509 | 534, 34: 628 | 664, 46: 808 | 854, 52: 883 | 930, 60: 971 | 1 009, 68: 1 049 | 1 080,
+// 72: 1 084 | 1 107, 76: 1 113 | 1 122, 80: 1 135 | 1 137, 84: 1 185 | 1 178, 92: 1 233 | 1 196, 100: 1 258 | 1 206, 136: 1 305 | 1 204, 160: 1 310 | 1 214 --
+// beyond ~80 slots the 128 branch teams are what a slot's tiles queue for.  One in 2 (96 branch teams) loses from 52 slots (68: 912), one in 4 (96 head teams)
+// at 68 (928).  Automatic from 4 to 72 slots, where it wins at every measured point by 2 % or more (4 slots: 1 %); elsewhere today's plan, rt_bb_every included.
+#ifndef LRG_RT_HEAD_EVERY_AUTO
+#define LRG_RT_HEAD_EVERY_AUTO(n_slots) ((n_slots) >= 4 && (n_slots) <= 72 ? 3 : 0)
+#endif
 static int plan_two_kernels(const LrgAsyncBuffers *ab, const LrgWeights *weights, const LrgPackedBuffers *b, const LrgAsyncSwitches &sw, int n_slots, int wgs, int cus,
                             LrgAsyncArgs *A, int *n_front_io) {
     A->wave_wgs = 0; A->wave_a_wgs = 0; A->wave_waves = 0; A->wave_split = 4; A->wave_fill = 0; A->wmask = (int)async_wave_ring_entries(n_slots) - 1; A->h3[0] = A->h3[1] = nullptr; A->reg_tiles = 0;
     // (every fourth register-tile CU with two branch teams from 120 slots: a slot's branch tiles queue for their teams there -- 68 slots -2.5 %, 100: +0.3 %, 136: +3.6 %, 160: +4.6 %)
     A->rt_bb_every = sw.rt_bb_every != LRG_ENV_UNSET ? sw.rt_bb_every : (n_slots >= 120 ? 4 : 0);
-    int worker_wgs = 0;                                      // workgroups of the worker kernel (wave-branch mode)
+    // (register-tile CUs by role, lrg_rt_role: what is asked for -- plan_roles below grants it.  LRG_ASYNC_RT_HEAD_EVERY forces; unset: LRG_RT_HEAD_EVERY_AUTO above,
+    //  unless LRG_ASYNC_RT_BB_EVERY asks for CUs with two branch teams by name -- the two never combine)
+    A->rt_head_every = sw.rt_head_every != LRG_ENV_UNSET ? sw.rt_head_every : (sw.rt_bb_every != LRG_ENV_UNSET && sw.rt_bb_every > 0) ? 0 : LRG_RT_HEAD_EVERY_AUTO(n_slots);
+    int worker_wgs = 0;                                     // workgroups of the worker kernel (wave-branch mode)
     int n_front = *n_front_io;
     int want = ab->branch_waves;
     if (want == 0 && n_slots >= LRG_REG_TILE_AUTO_MIN && n_slots <= LRG_REG_TILE_AUTO_MAX) want = 1;      // (register tiles where they win: include/lrg_hip.h)
@@ -403,6 +418,18 @@ static void plan_fill_teams(const LrgAsyncBuffers *ab, const LrgAsyncSwitches &s
     }
 }
 
+// (10b') Register-tile CUs by role (lrg_rt_role, lrg_async_plan.h): grants what plan_two_kernels left in A->rt_head_every, or takes it back.  One CU in N of an XCD's
+// share of the worker grid (w / 8) runs head tiles on both teams, the others branch tiles on team 0 alone -- N is kept within 2 .. worker_wgs / 8, so that the grid
+// has a CU of either role and neither ring is left without a team (a value below 2, or a grid of fewer than 16 workgroups: ignored).  Only where every CU is a
+// plain register-tile CU: not with team head tiles (reg_tiles == 2), whose team 0 region is not a head team's, and not with fill-in teams, which take team 1 of
+// the first CUs whatever their role.  Never beside two-branch-team CUs: a granted value makes rt_bb_every 0.  Decides A->rt_head_every, rt_bb_every.
+static void plan_roles(int worker_wgs, LrgAsyncArgs *A) {
+    int n = A->reg_tiles == 1 && !A->fill_wgs ? min(A->rt_head_every, worker_wgs / 8) : 0;
+    if (n < 2) n = 0;
+    A->rt_head_every = n;
+    if (n) A->rt_bb_every = 0;
+}
+
 // (10c) Which team serves which ring, the small teams and the tasks per branch tile.  Decides A->ring0_halves, head_ring, small_teams, small_alt, poll_sleep,
 // branch_parts -- and for a two-kernel launch overrides them with that form's (and takes back fill_extra).
 static void plan_rings_and_parts(const LrgAsyncBuffers *ab, const LrgAsyncSwitches &sw, int n_slots, int teams, LrgAsyncArgs *A) {
@@ -448,6 +475,9 @@ static void plan_lds(const LrgAsyncArgs &A, int teams, bool two_kernels, size_t 
     // (wave-branch mode, the worker kernel: a wave-branch CU's kernels + its fill-in team | two tile teams)
     *worker_lds = (max(max((size_t)(LRG_WB_FLOATS + LRG_ASYNC_FILL_TEAM_FLOATS), (size_t)2 * LRG_ASYNC_TEAM_FLOATS),
                        (size_t)(LRG_RT_WEIGHT_FLOATS + LRG_RT_TEAM0_FLOATS + max((int)LRG_ASYNC_TEAM_FLOATS, (int)LRG_RT_TEAM1_FLOATS))) * sizeof(float) + 15) & ~(size_t)15;
+    // (a HEAD2 CU, lrg_rt_role: its second head team's region lies over the branch kernels and team 0's exchange buffer, which it does not use -- worker_lds does not grow)
+    static_assert(LRG_ASYNC_TEAM_FLOATS <= LRG_RT_WEIGHT_FLOATS + LRG_RT_TEAM0_FLOATS && LRG_RT_TEAM1_FLOATS <= LRG_RT_WEIGHT_FLOATS + LRG_RT_TEAM0_FLOATS,
+                  "a head team's region in the place of the branch kernels and team 0's region");
     static_assert((LRG_WB_FLOATS + LRG_ASYNC_FILL_TEAM_FLOATS) * sizeof(float) <= 160 * 1024, "a wave-branch CU: the kernels of its (side, quarter) and a fill-in team");
 }
 
@@ -479,6 +509,7 @@ int lrg_async_plan(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
     A.n_slots = n_slots; A.n_front = n_front; A.teams = two_kernels ? 2 : teams;
     A.worker_base = n_front + A.gemv_units; A.total_wgs = two_kernels ? n_front + A.gemv_units + worker_wgs : wgs;
     plan_fill_teams(ab, sw, wgs, n_front, worker_wgs, teams, &A, &a);
+    plan_roles(worker_wgs, &A);
     plan_rings_and_parts(ab, sw, n_slots, teams, &A);
     plan_ticks(ab, max_steps, budget_us, &A);
     plan_lds(A, teams, two_kernels, &plan->lds, &plan->worker_lds);

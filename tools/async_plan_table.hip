@@ -5,6 +5,7 @@
 // and, behind them, one 'Q' line per slot count: where the rings the plans address end in the queue, and the words lrg_grow_async_queue_bytes gives it.
 // --full prints the canonical text itself behind every line.  tests/test_async_plan.py compares the output with tests/golden/async_plan_table.txt, so that
 // a change to a decision of the plan shows as the launches it moves.
+// --roles prints another table instead: the register-tile CUs by role over the same sweep (roles_rows below; tests/test_async_roles.py).
 //
 // No kernel and no HIP call: the plan is a function of its arguments, the CU count and the switches.  Every address is made up (a region number in the bits
 // from 40 up, an offset below) and none is dereferenced; the text names pointers by region and offset, never by value, and never prints a struct's raw bytes.
@@ -19,6 +20,8 @@
 #include <map>
 #include <set>
 #include <string>
+#include <vector>
+#include <algorithm>
 #include "../learn_region_grow_amd/csrc/lrg_async_plan.h"
 
 // ---- made-up addresses ----
@@ -199,8 +202,63 @@ static std::set<std::string> labels;
 static std::map<int, long long> ring_end;      // by slot count: the end of the last wave ring over the granted plans, in words of the queue
 static int lite2_rows = 0, lite2_pairs = 0, heads_rows = 0, heads_reg = 0, lds_over = 0;
 
+// ---- --roles: the register-tile CUs by role (lrg_rt_role, csrc/lrg_async_plan.h) ----
+// For every case of the sweep, the plan with the switch rt_head_every unset, 0, 2, 3, 4 and 64.  A granted register-tile row prints one line per value:
+//     label|value|rt_head_every rt_bb_every|CUs MIXED BRANCH2 BRANCH1 HEAD2|teams on ring 0, on ring 1, on the fill-in ring|the fewest ring-0 / ring-1 teams on 8 consecutive workgroups
+// every other granted row one line, label|-|the six plans' rt_head_every (all 0: no roles without register tiles).  The teams are counted with the kernel's
+// own functions, lrg_rt_role and lrg_rt_team_ring, over the worker grid.  Exit code 1: a granted row with a ring that no team serves, with rt_head_every beside
+// rt_bb_every, or with roles and no register tiles.  tests/test_async_roles.py compares the output with tests/golden/async_roles_table.txt.
+static bool roles = false;
+static int roles_bad = 0;
+static void roles_rows(const std::string &label, const Setup &S0) {
+    static const char *const names[6] = {"unset", "0", "2", "3", "4", "64"};
+    const int values[6] = {default_switches.rt_head_every, 0, 2, 3, 4, 64};
+    static LrgAsyncPlan plan;
+    std::string plain = label + "|-|";
+    bool reg = false;
+    for (int i = 0; i < 6; ++i) {
+        Setup S = S0;
+        S.sw.rt_head_every = values[i];
+        memset(static_cast<void *>(&plan), 0xA5, sizeof(plan));
+        if (lrg_async_check(S.slots, S.rooms, S.n_slots, S.max_points, &S.prm, &S.w, &S.b, &S.ab, S.max_steps, S.budget_us) ||
+            lrg_async_plan(S.slots, S.rooms, S.n_slots, S.max_points, &S.prm, &S.w, &S.b, &S.ab, S.max_steps, S.budget_us, S.cus, S.sw, &plan))
+            return;                                  // (a refusal: no row)
+        const LrgAsyncArgs &A = plan.K.A;
+        if (A.rt_head_every && A.rt_bb_every) { fprintf(stderr, "async_plan_table: %s/%s: rt_head_every %d beside rt_bb_every %d\n", label.c_str(), names[i], A.rt_head_every, A.rt_bb_every); roles_bad = 1; }
+        if (!A.reg_tiles) {
+            if (A.rt_head_every) { fprintf(stderr, "async_plan_table: %s/%s: roles without register tiles\n", label.c_str(), names[i]); roles_bad = 1; }
+            plain += (i ? " " : "") + std::to_string(A.rt_head_every);
+            continue;
+        }
+        reg = true;
+        const int W = plan.worker_wgs - A.wave_wgs;  // (the register-tile CUs: the worker grid)
+        int cus[4] = {0, 0, 0, 0}, teams[3] = {0, 0, 0}, least[2] = {1 << 30, 1 << 30};
+        std::vector<int> on0(W + 1, 0), on1(W + 1, 0);      // prefix sums of the teams per workgroup on ring 0 / ring 1
+        for (int w = 0; w < W; ++w) {
+            const int role = lrg_rt_role(w, A.rt_bb_every, A.rt_head_every);
+            ++cus[role];
+            int r0 = 0, r1 = 0;
+            for (int t = 0; t < 2; ++t) {
+                const int ring = (t && A.fill_list && w < A.fill_wgs) ? 2 : lrg_rt_team_ring(role, t);      // (the kernel's order: a fill-in team first)
+                if (ring >= 0) ++teams[ring];
+                r0 += ring == 0; r1 += ring == 1;
+            }
+            on0[w + 1] = on0[w] + r0; on1[w + 1] = on1[w] + r1;
+        }
+        for (int w = 0; w + 8 <= W; ++w) {
+            least[0] = std::min(least[0], on0[w + 8] - on0[w]);
+            least[1] = std::min(least[1], on1[w + 8] - on1[w]);
+        }
+        if (!teams[0] || !teams[1]) { fprintf(stderr, "async_plan_table: %s/%s: %d teams on ring 0, %d on ring 1\n", label.c_str(), names[i], teams[0], teams[1]); roles_bad = 1; }
+        printf("%s|%s|%d %d|%d %d %d %d|%d %d %d|%d %d\n", label.c_str(), names[i], A.rt_head_every, A.rt_bb_every, cus[LRG_RT_MIXED], cus[LRG_RT_BRANCH2], cus[LRG_RT_BRANCH1],
+               cus[LRG_RT_HEAD2], teams[0], teams[1], teams[2], least[0], least[1]);
+    }
+    if (!reg) printf("%s\n", plain.c_str());
+}
+
 static void run(const std::string &label, const Setup &S) {
     if (!labels.insert(label).second) { fprintf(stderr, "async_plan_table: label used twice: %s\n", label.c_str()); exit(2); }
+    if (roles) { roles_rows(label, S); return; }
     static LrgAsyncPlan plan;
     memset(static_cast<void *>(&plan), 0xA5, sizeof(plan));      // (a field that the plan leaves unset shows as that pattern, not as what the last case left)
     int rc = lrg_async_check(S.slots, S.rooms, S.n_slots, S.max_points, &S.prm, &S.w, &S.b, &S.ab, S.max_steps, S.budget_us);
@@ -232,11 +290,13 @@ static const int SLOTS[] = {1, 16, 17, 24, 25, 46, 47, 83, 84, 96, 97, 119, 120,
 int main(int argc, char **argv) {
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--full")) full = true;
-        else { fprintf(stderr, "usage: async_plan_table [--full]\n"); return 2; }
+        else if (!strcmp(argv[i], "--roles")) roles = true;
+        else { fprintf(stderr, "usage: async_plan_table [--full | --roles]\n"); return 2; }
     }
     clearenv();                                  // (the switches' defaults, not this shell's)
     default_switches = lrg_async_switches();
-    printf("%s\n", COLUMNS);
+    printf("%s\n", roles ? "# label|rt_head_every asked|rt_head_every rt_bb_every|CUs MIXED BRANCH2 BRANCH1 HEAD2|teams ring0 ring1 fill|fewest ring0 ring1 teams on 8 consecutive workgroups"
+                         : COLUMNS);
     char l[128];
 
     // the paper's network on the whole chip: every slot count x the forms of the launch x units x teams
@@ -384,6 +444,7 @@ int main(int argc, char **argv) {
     vary("plan/conv1=128", make(68, 256, WIDE1, 13, 512, 512), [](Setup &) {});
     vary("plan/add_w0+8", B, [](Setup &S) { S.w.add_w[0] = at<float>(R_ADD_W, 8); });
 
+    if (roles) return roles_bad;
     for (const auto &q : ring_end) printf("Q %d %lld %zu\n", q.first, q.second, lrg_grow_async_queue_bytes(q.first) / sizeof(int32_t));
 
     // what the sweep must hold

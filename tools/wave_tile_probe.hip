@@ -3,6 +3,7 @@
 // Checks conv[1] and the pooled maxima bit for bit against a host evaluation in the MFMA formulation's summation order (per output a chain of FMAs over
 // k = 8g + 0, 4, 1, 5, 2, 6, 3, 7, then bias, then ReLU: lrg_fused_tile.inl), and times a task with 1 .. 16 wavefronts per CU on 1 / 64 / 200 CUs.
 // `wave_tile_probe pairs`: the register branch tile on the teams of a 512-thread workgroup, as the free-running worker kernel runs it (pairs_kernel below).
+// `wave_tile_probe roles`: head and branch teams of such a workgroup by the role of their CU -- who shares the SIMDs with whom (roles_kernel below).
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -154,6 +155,7 @@ struct PArgs {
     long long *cycles;                   // [workgroups][2]
     int tile0, tile_mod, tiles_per_team, tiles_per_slot, nparts, iters, head_beside;      // tile = tile0 + (its number in the launch) % tile_mod
     LrgFusedProb head;
+    int kind[2], background;             // roles_kernel: what team 0 / 1 runs (0: absent, 1: branch tiles, 2: head tiles); the team that runs until the other is through (-1: none)
 };
 __global__ __launch_bounds__(512) void pairs_kernel(PArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, nteams = (int)blockDim.x >> 8;
@@ -222,6 +224,100 @@ __global__ __launch_bounds__(512) void pairs_kernel(PArgs a) {
     }
 }
 
+// `wave_tile_probe roles`: the teams of a register-tile CU by role (csrc/lrg_async_plan.h, lrg_rt_role; tests/test_gpu_cu_roles.py) -- a head team alone, beside a
+// second head team, beside a branch team; a branch team with team 1 absent.  The LDS is the worker's, and a CU whose team 0 runs head tiles (HEAD2) holds no branch
+// kernels: team 0's head region lies in their place, team 1's where it always is.  A team runs iters x tiles_per_team tiles and is timed, or (`background`) runs
+// until the other team is through.  Head tile h = 64 t + (its number) % 64 is slot h's: the pooled product (layer 0's bias) is a row per slot.
+__global__ __launch_bounds__(512) void roles_kernel(PArgs a) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int t = __builtin_amdgcn_readfirstlane(tid >> 8), wn = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);
+    const bool head2 = a.kind[0] == 2;
+    if (a.kind[0] == 1 || a.kind[1] == 1) {
+        const int sizes[3] = {1024, 4096, 4096}, offs[3] = {LRG_RT_W0, LRG_RT_W1, LRG_RT_W2};
+        const int bs[5] = {64, 64, 64, 128, 512}, bo[5] = {LRG_RT_B0, LRG_RT_B1, LRG_RT_B2, LRG_RT_B3, LRG_RT_B4};
+        for (int side = 0; side < 2; ++side) {
+            for (int l = 0; l < 3; ++l)
+                for (int i = tid; i < sizes[l] / 4; i += blockDim.x) reinterpret_cast<float4 *>(lrg_async_smem + side * LRG_RT_SIDE + offs[l])[i] = reinterpret_cast<const float4 *>(a.w[side][l])[i];
+            for (int l = 0; l < 5; ++l)
+                for (int i = tid; i < bs[l]; i += blockDim.x) lrg_async_smem[side * LRG_RT_SIDE + bo[l] + i] = a.b[side][l][i];
+        }
+    }
+    const int region0 = head2 ? 0 : LRG_RT_WEIGHT_FLOATS, region1 = LRG_RT_WEIGHT_FLOATS + P_TEAM0;
+    const int region = t ? region1 : region0, xch = region + P_CTL;
+    int *word = reinterpret_cast<int *>(lrg_async_smem + region);      // [0] a background team's 'go on', [4] the team's counter, [6] 'done'
+    const int kind = a.kind[t];
+    if ((tid & 255) == 0) { word[0] = 1; word[4] = 0; word[6] = 0; }
+    if (kind == 1 && (tid & 255) < 2) reinterpret_cast<int *>(lrg_async_smem + xch + LRG_RT_PAIR_CNT)[tid & 255] = 0;
+    __syncthreads();
+    if (!kind) return;
+    LrgLdsTeam team;
+    team.cnt = &word[4]; team.target = 0; team.base = t * 256; team.gave_up = nullptr;
+    LrgLdsPair pair;
+    pair.cnt = reinterpret_cast<int *>(lrg_async_smem + xch + LRG_RT_PAIR_CNT) + (wn >> 1); pair.target = 0; pair.gave_up = nullptr;
+    const bool background = a.background == t;
+    volatile int *done = reinterpret_cast<volatile int *>(lrg_async_smem + (t ? region0 : region1)) + 6;
+    struct { __device__ void operator()() const {} } nowait;
+    const int n = (background ? 16 : 1) * a.iters * a.tiles_per_team;      // (bounded)
+    const long long t0 = (long long)__builtin_readcyclecounter();
+    for (int it = 0; it < n; ++it) {
+        if (background) {
+            if ((tid & 255) == 0) word[0] = !*done;
+            team.sync();
+            const int go = word[0];
+            if (!go) break;
+        }
+        if (kind == 2) {
+            const int h = t * a.tiles_per_team + it % a.tiles_per_team;
+            lrg_team_head_tile_reg(a.head, (long)h * 32, h, xch, team, nowait, wn, lane);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            team.sync();                                      // (as the task does before its arrival)
+        } else {
+            const int tile = a.tile0 + (((int)blockIdx.x * 2 + t) * a.tiles_per_team + it % a.tiles_per_team) % a.tile_mod;
+            const int slot = tile / a.tiles_per_slot, side = slot & 1;
+            lrg_team_branch_tile_reg<1>(a.x, a.center, a.conv1, a.pool + (long)slot * 512, a.w[side][3], a.w[side][4], (long)tile * 32, slot, side * LRG_RT_SIDE, xch, team, pair, wn, lane, 0);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            team.sync();
+            team.sync();                                      // (the next task's first meeting, as in pairs_kernel)
+        }
+    }
+    const long long t1 = (long long)__builtin_readcyclecounter();
+    if ((tid & 255) == 0 && !background) {
+        a.cycles[blockIdx.x * 2 + t] = t1 - t0;
+        word[6] = 1;
+    }
+}
+
+// the register head tile's host chain: the MFMA chain per layer (layer 0's bias is the slot's pooled product, then a zero layer bias), then lrg_fused_tile's last
+// layer (eight partial chains over k = 4q + 32m + i, a butterfly over q)
+static void head_ref(const std::vector<float> &cin, int rows, int rows_per_slot, const std::vector<float> &hw0, const std::vector<float> &hbv, const std::vector<float> &hw1,
+                     const std::vector<float> &hbias1, const std::vector<float> &fw, const std::vector<float> &fb, std::vector<float> &lref) {
+    std::vector<float> g0(256), g1h(128);
+    lref.assign((size_t)rows * 2, 0.f);
+    for (int n = 0; n < rows; ++n) {
+        for (int c = 0; c < 256; ++c) {
+            float acc = 0.f;
+            for (int g = 0; g < 8; ++g) for (int s2 = 0; s2 < 4; ++s2) for (int hh = 0; hh < 2; ++hh) { const int k = 8 * g + 4 * hh + s2; acc = fmaf(hw0[(size_t)k * 256 + c], cin[(size_t)n * 64 + k], acc); }
+            g0[c] = fmaxf((acc + hbv[(size_t)(n / rows_per_slot) * 256 + c]) + 0.f, 0.f);
+        }
+        for (int c = 0; c < 128; ++c) {
+            float acc = 0.f;
+            for (int g = 0; g < 32; ++g) for (int s2 = 0; s2 < 4; ++s2) for (int hh = 0; hh < 2; ++hh) { const int k = 8 * g + 4 * hh + s2; acc = fmaf(hw1[(size_t)k * 128 + c], g0[k], acc); }
+            g1h[c] = fmaxf(acc + hbias1[c], 0.f);
+        }
+        float part[8][2];
+        for (int q = 0; q < 8; ++q) {
+            float s0 = 0.f, s1 = 0.f;
+            for (int k = 4 * q; k < 128; k += 32)
+                for (int i = 0; i < 4; ++i) { s0 = fmaf(g1h[k + i], fw[2 * (k + i)], s0); s1 = fmaf(g1h[k + i], fw[2 * (k + i) + 1], s1); }
+            part[q][0] = s0; part[q][1] = s1;
+        }
+        for (int o = 0; o < 2; ++o) {
+            const float t01 = part[0][o] + part[1][o], t23 = part[2][o] + part[3][o], t45 = part[4][o] + part[5][o], t67 = part[6][o] + part[7][o];
+            lref[(size_t)n * 2 + o] = ((t01 + t23) + (t45 + t67)) + fb[o];
+        }
+    }
+}
+
 // one layer in the MFMA formulation's order; pre (nullable): the value before the ReLU
 static void layer_ref2(const float *in, int rows, int K, const std::vector<float> &w, const std::vector<float> &b, int N, std::vector<float> &out, std::vector<float> *pre) {
     const int ng = (K + 7) / 8;
@@ -247,7 +343,7 @@ static size_t differ(const std::vector<float> &g, const std::vector<float> &r, s
     return bad;
 }
 
-static int pairs_main() {
+static int pairs_main(bool roles) {
     const int n_tiles = 130, rows = n_tiles * 32, F = 13;      // tiles 0, 1: the single tiles and the two of one slot; 2 .. 129: the two teams' 64 each
     const int Ks[5] = {F, 64, 64, 64, 128}, Ns[5] = {64, 64, 64, 128, 512};
     srand(4711);
@@ -321,6 +417,59 @@ static int pairs_main() {
         CK(hipMemcpy(gp.data(), pool, gp.size() * 4, hipMemcpyDeviceToHost));
     };
     size_t bad = 0;
+    if (roles) {
+        // ---- `roles`: the teams of a register-tile CU by role (roles_kernel).  128 head tiles of a slot each beside the 128 branch tiles 2 .. 129 ----
+        const int HT = 128, hrows = HT * 32;
+        host(2, 130, 1, false);
+        std::vector<float> hx((size_t)hrows * 64), hw0((size_t)64 * 256), hw1((size_t)256 * 128), hbv((size_t)HT * 256), hb1(128), fw(256), fb(2), pk0, pk1, lref;
+        for (auto &v : hx) v = fmaxf(rnd(), 0.f) * 2.f;      // (conv[1] rows: behind a ReLU)
+        for (auto &v : hw0) v = rnd() * 0.2f;
+        for (auto &v : hw1) v = rnd() * 0.1f;
+        for (auto &v : hbv) v = rnd() * 0.5f;
+        for (auto *v : {&hb1, &fb}) for (auto &e : *v) e = rnd() * 0.1f;
+        for (auto &v : fw) v = rnd() * 0.2f;
+        pack(hw0, 64, 256, pk0); pack(hw1, 256, 128, pk1);
+        head_ref(hx, hrows, 32, hw0, hbv, hw1, hb1, fw, fb, lref);
+        LrgFusedProb &H = a.head;
+        H.x = up(hx); H.L[0].w = up(pk0); H.L[0].bias = up(hbv); H.L[1].w = up(pk1); H.L[1].bias = up(hb1); H.fw = up(fw); H.fb = up(fb);
+        float *lout; CK(hipMalloc(&lout, (size_t)hrows * 2 * 4)); H.fout = lout;
+        CK(hipFuncSetAttribute(reinterpret_cast<const void *>(roles_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        std::vector<float> lg((size_t)hrows * 2);
+        a.h3 = nullptr; a.tile0 = 2; a.tiles_per_team = 64; a.tiles_per_slot = 1; a.nparts = 1;
+        struct Case { const char *name; int kind[2], timed; } cases[4] = {
+            {"(a) a head tile alone", {2, 0}, 0}, {"(b) a head tile beside a head team", {2, 2}, 0},
+            {"(c) a head tile beside a branch team", {1, 2}, 1}, {"(d) a branch tile, team 1 absent", {1, 0}, 0}};
+        // values: every team runs its 64 tiles once, both teams to the end
+        for (const Case &c : cases) {
+            a.kind[0] = c.kind[0]; a.kind[1] = c.kind[1]; a.background = -1; a.iters = 1;
+            CK(hipMemset(conv1, 0xFF, (size_t)rows * 64 * 4)); CK(hipMemset(pool, 0, (size_t)n_tiles * 512 * 4)); CK(hipMemset(lout, 0xFF, (size_t)hrows * 2 * 4));
+            hipLaunchKernelGGL(roles_kernel, dim3(1), dim3(512), P_LDS_FLOATS * 4, 0, a);
+            CK(hipDeviceSynchronize());
+            CK(hipMemcpy(g1.data(), conv1, g1.size() * 4, hipMemcpyDeviceToHost));
+            CK(hipMemcpy(gp.data(), pool, gp.size() * 4, hipMemcpyDeviceToHost));
+            CK(hipMemcpy(lg.data(), lout, lg.size() * 4, hipMemcpyDeviceToHost));
+            size_t bl = 0, nl = 0, b1 = 0, bp = 0, nb = 0;
+            for (int t = 0; t < 2; ++t) {
+                if (c.kind[t] == 2) { bl += differ(lg, lref, (size_t)t * 64 * 64, 64 * 64); nl += 64 * 64; }      // (team t's head tiles 64 t .. 64 t + 63: 32 rows x 2 logits each)
+                if (c.kind[t] == 1) { b1 += differ(g1, r1, (size_t)(2 + 64 * t) * 32 * 64, (size_t)64 * 32 * 64); bp += differ(gp, rp, (size_t)(2 + 64 * t) * 512, 64 * 512); nb += 64; }
+            }
+            printf("roles %s, 64 tiles per team: logits %zu of %zu differ from the host chain; conv[1] %zu of %zu; pooled %zu of %zu\n", c.name, bl, nl, b1, nb * 32 * 64, bp, nb * 512);
+            bad += bl + b1 + bp;
+        }
+        // ticks per tile of the timed team (64 tiles x 8), the other team -- where there is one -- running its tiles without pause until the timed one is through
+        for (const Case &c : cases)
+            for (int grid : {1, 200}) {
+                a.kind[0] = c.kind[0]; a.kind[1] = c.kind[1]; a.background = (c.kind[0] && c.kind[1]) ? 1 - c.timed : -1; a.iters = 8;
+                hipLaunchKernelGGL(roles_kernel, dim3(grid), dim3(512), P_LDS_FLOATS * 4, 0, a);
+                CK(hipDeviceSynchronize());
+                std::vector<long long> cy((size_t)grid * 2);
+                CK(hipMemcpy(cy.data(), cyc, cy.size() * 8, hipMemcpyDeviceToHost));
+                double sum = 0;
+                for (int g = 0; g < grid; ++g) sum += (double)cy[g * 2 + c.timed] / (a.iters * a.tiles_per_team);
+                printf("ROLES %s, grid %3d: %8.0f counter ticks per tile\n", c.name, grid, sum / grid);
+            }
+        return bad ? 1 : 0;
+    }
     // ---- single tiles: tile 0 on side 0, tile 1 on side 1 (a slot each), one workgroup (one team) per tile ----
     host(0, 2, 1, true);
     printf("single tile inputs: %d of %d (point, layer) of layers 0 - 2 have a negative pre-activation in one block and a positive one in the other; "
@@ -380,7 +529,8 @@ static int pairs_main() {
 }
 
 int main(int argc, char **argv) {
-    if (argc > 1 && !strcmp(argv[1], "pairs")) return pairs_main();
+    if (argc > 1 && !strcmp(argv[1], "pairs")) return pairs_main(false);
+    if (argc > 1 && !strcmp(argv[1], "roles")) return pairs_main(true);
     const int n_slots = 6, rows_per_slot = 96, rows = n_slots * rows_per_slot, n_tiles = rows / 32, F = 13;
     const int Ks[5] = {F, 64, 64, 64, 128}, Ns[5] = {64, 64, 64, 128, 512};
     srand(12345);
@@ -504,32 +654,10 @@ int main(int argc, char **argv) {
         for (auto &v : fb) v = rnd() * 0.1f;
         for (auto &v : hbv) v = rnd() * 0.5f;
         pack(hw0, 64, 256, pk0); pack(hw1, 256, 128, pk1);
-        // host: the MFMA chain per layer, then lrg_fused_tile's last layer (eight partial chains over k = 4q + 32m + i, butterfly over q)
-        std::vector<float> g0((size_t)rows * 256), g1h((size_t)rows * 128), lref((size_t)rows * 2);
+        // host: head_ref above
+        std::vector<float> lref;
         const std::vector<float> &cin = h[1];
-        for (int n = 0; n < rows; ++n) {
-            for (int c = 0; c < 256; ++c) {
-                float acc = 0.f;
-                for (int g = 0; g < 8; ++g) for (int s2 = 0; s2 < 4; ++s2) for (int hh = 0; hh < 2; ++hh) { const int k = 8 * g + 4 * hh + s2; acc = fmaf(hw0[(size_t)k * 256 + c], cin[(size_t)n * 64 + k], acc); }
-                g0[(size_t)n * 256 + c] = fmaxf((acc + hbv[(size_t)(n / rows_per_slot) * 256 + c]) + 0.f, 0.f);
-            }
-            for (int c = 0; c < 128; ++c) {
-                float acc = 0.f;
-                for (int g = 0; g < 32; ++g) for (int s2 = 0; s2 < 4; ++s2) for (int hh = 0; hh < 2; ++hh) { const int k = 8 * g + 4 * hh + s2; acc = fmaf(hw1[(size_t)k * 128 + c], g0[(size_t)n * 256 + k], acc); }
-                g1h[(size_t)n * 128 + c] = fmaxf(acc + hbias1[c], 0.f);
-            }
-            float part[8][2];
-            for (int q = 0; q < 8; ++q) {
-                float s0 = 0.f, s1 = 0.f;
-                for (int k = 4 * q; k < 128; k += 32)
-                    for (int i = 0; i < 4; ++i) { s0 = fmaf(g1h[(size_t)n * 128 + k + i], fw[2 * (k + i)], s0); s1 = fmaf(g1h[(size_t)n * 128 + k + i], fw[2 * (k + i) + 1], s1); }
-                part[q][0] = s0; part[q][1] = s1;
-            }
-            for (int o = 0; o < 2; ++o) {
-                const float t01 = part[0][o] + part[1][o], t23 = part[2][o] + part[3][o], t45 = part[4][o] + part[5][o], t67 = part[6][o] + part[7][o];
-                lref[(size_t)n * 2 + o] = ((t01 + t23) + (t45 + t67)) + fb[o];
-            }
-        }
+        head_ref(cin, rows, rows_per_slot, hw0, hbv, hw1, hbias1, fw, fb, lref);
         auto up = [&](const std::vector<float> &v) { float *dd; CK(hipMalloc(&dd, v.size() * 4)); CK(hipMemcpy(dd, v.data(), v.size() * 4, hipMemcpyHostToDevice)); return dd; };
         LrgFusedProb &H = a.head;
         memset(&H, 0, sizeof(H));
