@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 22
+#define LRG_ABI_VERSION 23
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -1203,6 +1203,49 @@ int lrg_stage_teacher(const LrgRoom *rooms, const int32_t *room_list, int n_list
 /* stage_data.py:233-240 */
 int lrg_stage_tuples(const LrgRoom *rooms, const int32_t *arena, const int32_t *table, int n_tuples, int F, float *points, int32_t *remove,
                      float *neighbor_points, int32_t *add, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 23.  SemanticKITTI scans fused into scenes (stage_semantic_kitti.py), one sample (a stack of `interval` scans) per call,
+ * one thread per point in every launch.  All arithmetic is float64 in plain chains of unfused products and sums, the IEEE division and rint.
+ * A table is a linear-probe hash of packed voxel keys: keys [slots] and vals [slots] from the caller, slots a power of two of at least
+ * max(64, 2 n) (lrg_kitti_table_slots (n); 0 for an n the calls refuse); every call fills its table itself.  A slot holds the smallest index
+ * that inserted its key (CAS on the key, atomicMin on the value).  status [1] is cleared by every call and collects LRG_KITTI_ST_* bits: a
+ * coordinate that is not finite, a voxel outside the 21-bit key window (less one cell either side, for the neighbour probes), a scan index out
+ * of range, a full table.  With a bit set the outputs are not to be used.  Every result is a minimum, an integer sum or a minimum-index root,
+ * so a call writes the same bytes every time.  Limits: n <= LRG_KITTI_MAX_POINTS.
+ *
+ * lrg_kitti_project: points [n, ld] float32 (x y z first) of n_scans scans back to back in (scan, index) order, scan_of [n] ascending,
+ * labels [n] (object << 16 | class), pose [n_scans, 12] = the first three rows of Tr^-1 pose Tr of every scan, tr [16] and p2 [12] the
+ * calibration's rows, images = the scans' RGB images in one buffer, scan s at img_off [s] with img_h [s] rows of img_w [s] pixels.
+ * Writes xyz [n, 3] = ((r0 x + r1 y) + r2 z) + t; valid [n]: h = P2 (Tr [x y z 1]) in the same four-term chains, u = rint (h0 / h2),
+ * v = rint (h1 / h2), valid when h2 > 0, 0 <= u < W and 0 <= v < H, compared as doubles; rgb [n, 3]: image [v, u] of a valid point; an
+ * invalid point takes the colour of the smallest valid index of its voxel, rint (xyz / voxel_resolution), when that index belongs to a scan
+ * not later than its own, else 0 0 0; keep [n] = colour not 0 0 0 and class < 250.  Refused with LRG_EINVAL - 110 .. - 112.
+ *
+ * lrg_kitti_first_in_voxel: rep [i] = the smallest index whose voxel rint (xyz / resolution) is that of point i.  Refused with
+ * LRG_EINVAL - 113 .. - 115.
+ *
+ * lrg_kitti_components: for equalised points (one per voxel), every point with obj == 0 probes its 26 neighbour voxels and is joined to each
+ * point found there whose cls equals its own (lrg_union.h; it `emits` an edge then).  Writes root [n] (the minimum index of the point's
+ * component), and at every root size [root] (points of the component) and first_src [root] (its smallest emitting member; INT_MAX without
+ * one); emits [n].  Refused with LRG_EINVAL - 116 .. - 118. */
+#define LRG_KITTI_MAX_POINTS (1 << 28)
+#define LRG_KITTI_ST_NONFINITE 1
+#define LRG_KITTI_ST_WINDOW 2
+#define LRG_KITTI_ST_SCAN 4
+#define LRG_KITTI_ST_TABLE 8
+int lrg_kitti_table_slots(int n);
+/* stage_semantic_kitti.py:94-135 */
+int lrg_kitti_project(const float *points, int ld, const int32_t *scan_of, const uint32_t *labels, int n, int n_scans, const double *pose,
+                      const double *tr, const double *p2, const uint8_t *images, const int64_t *img_off, const int32_t *img_h,
+                      const int32_t *img_w, double voxel_resolution, uint64_t *keys, int32_t *vals, int slots, double *xyz, uint8_t *rgb,
+                      uint8_t *valid, uint8_t *keep, int32_t *status, void *stream);
+/* stage_semantic_kitti.py:23-31, :144-154 */
+int lrg_kitti_first_in_voxel(const double *xyz, int n, double resolution, uint64_t *keys, int32_t *vals, int slots, int32_t *rep,
+                             int32_t *status, void *stream);
+/* stage_semantic_kitti.py:167-183 */
+int lrg_kitti_components(const double *xyz, const int32_t *obj, const int32_t *cls, int n, double resolution, uint64_t *keys, int32_t *vals,
+                         int slots, int32_t *root, int32_t *size, int32_t *first_src, uint8_t *emits, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

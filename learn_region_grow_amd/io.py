@@ -5,9 +5,13 @@
 ``savePLY``     learn_region_grow_util.py:57-73   ASCII PLY, "%f %f %f %d %d %d" per vertex
 ``savePCD``     learn_region_grow_util.py:33-55   ASCII PCD v0.7 with packed rgb
 ``label_colors`` test_region_grow.py:368-371      the colour table of the result clouds
+``read_png``    stage_semantic_kitti.py:103       what imageio.imread gives for the camera images, from zlib and NumPy alone
 
 HDF5 goes through ``h5lite`` (h5py is not installed here); weights through ``checkpoint``.
 """
+import struct
+import zlib
+
 import numpy as np
 
 from . import h5lite
@@ -58,3 +62,72 @@ def label_colors(n_labels):
     obj_color = np.random.RandomState(0).randint(0, 255, (n_labels, 3))
     obj_color[0] = [100, 100, 100]
     return obj_color
+
+
+def _png_unfilter(raw, height, stride, bpp):
+    """The scanlines of an inflated PNG stream without their filters (PNG 1.2, section 6): [height, stride] uint8."""
+    if len(raw) != height * (stride + 1):
+        raise ValueError('PNG: %d bytes of image data, %d expected' % (len(raw), height * (stride + 1)))
+    rows = np.frombuffer(raw, dtype=np.uint8).reshape(height, stride + 1)
+    out = np.zeros((height + 1, stride), dtype=np.uint8)                  # row 0: the zeros above the first scanline
+    for r in range(height):
+        kind, line, up = int(rows[r, 0]), rows[r, 1:], out[r]
+        cur = out[r + 1]
+        if kind == 0:
+            cur[:] = line
+        elif kind == 1:                                                    # Sub: a running sum per byte lane of the pixel
+            for lane in range(bpp):
+                cur[lane::bpp] = np.cumsum(line[lane::bpp], dtype=np.uint64).astype(np.uint8)
+        elif kind == 2:                                                    # Up
+            cur[:] = line + up
+        elif kind in (3, 4):                                               # Average, Paeth: each byte needs the one bpp to its left
+            l, u, o = line.tolist(), up.tolist(), [0] * stride
+            for i in range(stride):
+                a = o[i - bpp] if i >= bpp else 0
+                if kind == 3:
+                    pred = (a + u[i]) >> 1
+                else:
+                    c = u[i - bpp] if i >= bpp else 0
+                    pa, pb, pc = abs(u[i] - c), abs(a - c), abs(a + u[i] - 2 * c)
+                    pred = a if pa <= pb and pa <= pc else (u[i] if pb <= pc else c)
+                o[i] = (l[i] + pred) & 255
+            cur[:] = o
+        else:
+            raise ValueError('PNG: unknown filter type %d in row %d' % (kind, r))
+    return out[1:]
+
+
+def read_png(filename):
+    """An 8-bit, non-interlaced grey, RGB or RGBA PNG as uint8 [H, W, 3] (grey repeated, alpha dropped).  Any other PNG is an error."""
+    with open(filename, 'rb') as f:
+        data = f.read()
+    if data[:8] != b'\x89PNG\r\n\x1a\n':
+        raise ValueError('%s is not a PNG file' % filename)
+    pos, header, idat, ended = 8, None, [], False
+    while pos + 8 <= len(data) and not ended:
+        length, tag = struct.unpack('>I4s', data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + length]
+        if len(body) != length or pos + 12 + length > len(data):
+            raise ValueError('%s: truncated %s chunk' % (filename, tag.decode('latin-1')))
+        if struct.unpack('>I', data[pos + 8 + length:pos + 12 + length])[0] != (zlib.crc32(tag + body) & 0xFFFFFFFF):
+            raise ValueError('%s: bad CRC in %s chunk' % (filename, tag.decode('latin-1')))
+        if tag == b'IHDR':
+            header = struct.unpack('>IIBBBBB', body)
+        elif tag == b'IDAT':
+            idat.append(body)
+        elif tag == b'IEND':
+            ended = True
+        pos += 12 + length
+    if header is None or not idat or not ended:
+        raise ValueError('%s: IHDR, IDAT or IEND missing' % filename)
+    width, height, depth, colour, compression, filtering, interlace = header
+    if depth != 8 or colour not in (0, 2, 6) or compression != 0 or filtering != 0 or interlace != 0 or width < 1 or height < 1:
+        raise ValueError('%s: only 8-bit non-interlaced grey / RGB / RGBA PNGs are read (bit depth %d, colour type %d, interlace %d)' %
+                         (filename, depth, colour, interlace))
+    bpp = {0: 1, 2: 3, 6: 4}[colour]
+    try:
+        raw = zlib.decompress(b''.join(idat))
+    except zlib.error as e:
+        raise ValueError('%s: %s' % (filename, e))
+    px = _png_unfilter(raw, height, width * bpp, bpp).reshape(height, width, bpp)
+    return np.ascontiguousarray(np.repeat(px, 3, axis=2) if bpp == 1 else px[:, :, :3])
