@@ -2,10 +2,16 @@
 // cases, on the host: no kernel, no HIP call.  One line per case,
 //     name|ml|beam_width|search_width|updated,...|size,...|score,...|best,...|kept,...
 // which tests/test_beam_select.py checks against Python's sorted() (the reference's own selection, test_beam_search.py:282).
+// With a file name as its argument the cases come from that file instead, one per line: name|ml|beam_width|search_width|updated,...|size,...|score,...
+// (the scores only under ml; "-inf" is read as such) -- tests/test_beam_rooms_host.py hands it the 64-slot patterns of the GPU tests.
 // A host sanitizer build of this program (-Xarch_host -fsanitize=address,undefined) is where the function's index arithmetic is checked.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <sstream>
+#include <string>
 #include <vector>
 #include "../learn_region_grow_amd/csrc/lrg_beam_select.h"
 
@@ -37,7 +43,39 @@ static void run(const Case &c) {
     std::printf("\n");
 }
 
-int main() {
+static std::vector<std::string> split(const std::string &s, char sep) {
+    std::vector<std::string> out;
+    std::string item;
+    std::istringstream in(s);
+    while (std::getline(in, item, sep)) out.push_back(item);
+    if (!s.empty() && s.back() == sep) out.push_back("");
+    return out;
+}
+
+static int run_file(const char *path) {
+    std::ifstream in(path);
+    if (!in) { std::fprintf(stderr, "cannot read %s\n", path); return 2; }
+    std::string line;
+    while (std::getline(in, line)) {
+        if (line.empty()) continue;
+        const std::vector<std::string> f = split(line, '|');
+        if (f.size() != 7) { std::fprintf(stderr, "bad line: %s\n", line.c_str()); return 2; }
+        Case c{f[0].c_str(), std::atoi(f[1].c_str()), std::atoi(f[2].c_str()), std::atoi(f[3].c_str()), {}, {}, {}};
+        for (const std::string &v : split(f[4], ',')) c.updated.push_back(std::atoi(v.c_str()));
+        for (const std::string &v : split(f[5], ',')) c.size.push_back(std::atoi(v.c_str()));
+        if (c.ml) for (const std::string &v : split(f[6], ',')) c.score.push_back(std::strtod(v.c_str(), nullptr));
+        if (c.bw < 1 || c.bw > LRG_BEAM_MAXQ || c.sw < 1 || c.bw * c.sw > 64 || c.updated.size() > 64 || c.size.size() != c.updated.size() ||
+            (c.ml && c.score.size() != c.updated.size())) {
+            std::fprintf(stderr, "bad case: %s\n", line.c_str());
+            return 2;
+        }
+        run(c);
+    }
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1) return run_file(argv[1]);
     const double inf = INFINITY;
     std::vector<Case> cases = {
         // --scoring np: ties in size keep child order (a stable sort); an unchanged child (0) and a parent without neighbours (-1) never enter
