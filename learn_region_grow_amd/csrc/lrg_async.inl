@@ -175,49 +175,7 @@ __device__ __forceinline__ void lrg_async_gemv(const LrgGemvArgs &g, int slot, i
 }
 
 
-// ---- pooled-product units: the heads' pooled kernels stay in LDS ----
-// As a task of the tile teams the pooled product of a slot is four trips of 512 KB from L2 (7.7 us each, 12.5 us from the last branch
-// tile to the last block with the queueing, profiles/r03_free8_perf.log) in the middle of the slot's chain of latencies.  The
-// kernels are the same for every slot: 2 x [P = 1024, C = 256] floats = 2 MB = sixteen CUs' LDS at 32 columns each.  A unit
-// (workgroup) loads its [P, 32] slice once per launch; its four teams of four wavefronts take the slots whose branch tiles have
-// all arrived from ONE ring that every unit reads (entry i: (generation of i) << 20 | slot, written once by the last branch tile
-// to arrive; a unit's teams take the entries in turn -- a ticket counter in the unit's LDS, nothing to reserve in memory); a task =
-// the slot's 4 KB pooled row from L2, 128 FMAs per lane from LDS, 32 sums out, one more arrival on the slot's pooled-product counter,
-// which the slot's head tiles poll (LrgWaitPooled).  Summation order: that of lrg_head_gemv_kernel (eight K ranges, MFMA k order
-// inside, the partial sums in order, the bias last) -- bit for bit what the tile teams' blocks give.
-// (Tried: mailboxes instead of the ring -- a 64-bit word per slot, arrivals | target << 32, every branch tile adds itself, one team per
-// unit watches all slots -- so that the units start ~2 us earlier, before the last tile knows it was the last: 808 k -> 795 k
-// instance-steps/s at 68 slots, the second atomic per tile and the watchers' loads cost more than the earlier start gains.)
-#define LRG_GEMV_UNIT_COLS 32
-#define LRG_GEMV_UNIT_TEAMS 4
-#define LRG_GEMV_UNIT_TEAM_FLOATS(P) ((P) + 8 * LRG_GEMV_UNIT_COLS + 16)      // pooled row, partial sums, task words + barrier counter
-#define LRG_GEMV_UNIT_FLOATS(P) ((P) * LRG_GEMV_UNIT_COLS + LRG_GEMV_UNIT_TEAMS * LRG_GEMV_UNIT_TEAM_FLOATS(P))      // + n_slots claim words behind
-#define LRG_GEMV_UNIT_MAX_SLOTS 2048
-__device__ __forceinline__ int lrg_gemv_ring_tag(int i, int gmask) { return (((unsigned)i / (unsigned)(gmask + 1)) % 2047u) + 1; }
-
-// ---- the launch's arguments ----
-// ONE kernel parameter, LrgAsyncKArgs (lrg_async_plan.h, where the reasons are)
-// (inside a non-kernel function __builtin_amdgcn_kernarg_segment_ptr() folds to null: the kernel takes the pointer and hands it on,
-//  typed as constant address space, so that the roles' loads of the arguments stay scalar loads)
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef const __attribute__((address_space(4))) void *lrg_kargs_ptr;
-#else
-typedef const void *lrg_kargs_ptr;
-#endif
-#define LRG_ASYNC_KARGS() (*(const LrgAsyncKArgs *)kp)
-// Arguments of a non-kernel function arrive in vector registers; what is wave-uniform goes back to scalar registers first, so that
-// the loads of the launch's arguments are scalar loads and the addresses derived from them scalar arithmetic.
-__device__ __forceinline__ lrg_kargs_ptr lrg_uniform(lrg_kargs_ptr p) {
-    const unsigned long long v = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (lrg_kargs_ptr)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ int lrg_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-// the launch's dynamic LDS: roles get OFFSETS into it (a float * parameter would be a generic pointer, and every LDS access of a
-// tile a flat instruction)
-extern __shared__ __attribute__((aligned(16))) float lrg_async_smem[];
-#include "lrg_wave_tile.inl"
-#define LRG_ASYNC_ROLE __device__ __noinline__
+#include "lrg_async_units.inl"
 // The tile tasks are inlined into the worker's loop (round 4).  As functions of their own (round 3) every call saved and restored the callee-saved registers the
 // tile code uses -- 54 / 72 dwords per lane and task through scratch memory: ~0.6 MB of writes and as many reads per evaluation, which is what the write counter of
 // profiles/r03_pmc_free_run.json (13.5 GB per launch) was made of, and 1.3 % of the rate.  One function = one register allocation for branch and head tiles and the
@@ -617,274 +575,6 @@ LRG_ASYNC_ROLE int lrg_async_task_gemv_batch(lrg_kargs_ptr kp_, int code_, int s
         }
     team.sync();
     return team.target;
-}
-
-// ---- a pooled-product unit (see LRG_GEMV_UNIT_COLS above): `unit` = 0 .. gemv_units - 1, all sixteen wavefronts arrive here ----
-LRG_ASYNC_ROLE void lrg_async_gemv_unit(lrg_kargs_ptr kp_, int unit_, long long t_launch) {
-    const lrg_kargs_ptr kp = lrg_uniform(kp_);
-    const int unit = lrg_uniform(unit_);
-    const LrgAsyncArgs &A = LRG_ASYNC_KARGS().A;
-    const LrgGemvArgs &g = A.gemv;
-    const int P = g.P, kq = P >> 3;
-    const int upz = g.C / LRG_GEMV_UNIT_COLS;                 // units per head
-    const int z = unit / upz, col0 = (unit - z * upz) * LRG_GEMV_UNIT_COLS;
-    float *wl = lrg_async_smem;                                // [P][32] this unit's columns of head z's pooled kernel
-    {   // the slice, once per launch: 16-byte loads, eight per row
-        const float *w = g.w[z] + col0;
-        for (int i = threadIdx.x; i < P * (LRG_GEMV_UNIT_COLS / 4); i += LRG_FRONT_THREADS) {
-            const int row = i >> 3, q = i & 7;
-            *reinterpret_cast<float4 *>(wl + row * LRG_GEMV_UNIT_COLS + 4 * q) = *reinterpret_cast<const float4 *>(w + (long)row * g.ldw + 4 * q);
-        }
-    }
-    const int t = lrg_uniform((int)threadIdx.x >> 8);
-    float *sm = lrg_async_smem + P * LRG_GEMV_UNIT_COLS + t * LRG_GEMV_UNIT_TEAM_FLOATS(P);
-    float *pl = sm, *part = sm + P;
-    int *word = reinterpret_cast<int *>(part + 8 * LRG_GEMV_UNIT_COLS);      // [0], [1] the task of even / odd rounds, [4] barrier counter
-    int *ctl = reinterpret_cast<int *>(lrg_async_smem + LRG_GEMV_UNIT_FLOATS(P));          // [0] the unit's next ring entry
-    if ((threadIdx.x & 255) == 0) { word[0] = 0; word[1] = 0; word[4] = 0; }
-    if (threadIdx.x < 4) ctl[threadIdx.x] = 0;
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                              // the slice is in place; from here on the teams go their own ways
-    LrgLdsTeam team;
-    team.cnt = &word[4];
-    team.target = 0;
-    team.base = (int)(threadIdx.x & ~255u);
-    team.gave_up = &A.queue[LRG_AQ_ABORT];
-    const int tid = team.tid(), lane = tid & 63, wave = tid >> 6;
-    const int c = lane & 31, r = 2 * wave + (lane >> 5);      // this lane's column and K range
-    const float bias = g.bias[z] ? g.bias[z][col0 + (tid & 31)] : 0.f;
-    const int32_t *ring = A.queue + LRG_AQ_RING + 2 * (A.qmask + 1);
-    for (int round = 0;; round ^= 1) {
-        long long t_task = 0;
-        if (wave == 0) {
-            // the unit's next ring entry, taken by whichever team is free; the other wavefronts wait at the barrier below
-            int slot = -2;
-            int i = 0;
-            if (lane == 0) i = __hip_atomic_fetch_add(&ctl[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            i = __shfl(i, 0);
-            const int32_t *e = ring + (i & A.gmask);
-            const int tag = lrg_gemv_ring_tag(i, A.gmask);
-            for (unsigned spin = 0; slot == -2; ++spin) {
-                const int code = lrg_ld_coh(e);
-                if ((code >> 20) == tag) { slot = code & 0xFFFFF; break; }      // (slot | tile counts: unpacked below)
-                if ((spin & 7) == 7) {
-                    if (lrg_ld_coh(&A.queue[LRG_AQ_FRONTS_DONE]) >= A.n_front || lrg_ld_coh(&A.queue[LRG_AQ_ABORT])) slot = -1;
-                    else if ((spin & 1023) == 1023 && wall_clock64() - t_launch > A.abort_ticks) {
-                        lrg_st_coh(&A.queue[LRG_AQ_ABORT], 4);
-                        slot = -1;
-                    }
-                }
-                if (slot == -2) __builtin_amdgcn_s_sleep(2);
-            }
-            if (lane == 0) word[round] = slot;
-        }
-        team.sync();
-        const int entry = word[round];                        // (the other word is written next round: no second barrier)
-        if (entry < 0) return;
-        const int slot = entry & 0xFFF;                       // (units serve at most LRG_GEMV_UNIT_MAX_SLOTS = 2048 slots)
-        if (LRG_DBG(A)) t_task = wall_clock64();
-        if (A.pool_rows) {
-            // the slot's pooled feature (:122-125) = the maximum over its branch tiles' rows of column maxima, taken here on the way into LDS:
-            // every lane owns 16 bytes of the feature and has one load per tile of that side in flight (the values are >= 0: their
-            // order is that of their bit patterns, as in the atomicMax formulation)
-            const int nt_in = ((entry >> 16) & 15) + 1, nt_nb = ((entry >> 12) & 15) + 1;
-            const int half4 = P >> 3;                          // 16-byte pieces per side
-            const float *rows = A.pool_rows + (long)slot * A.pool_rows_stride;
-            for (int j = tid; j < (P >> 2); j += FTHREADS) {
-                const int side = j >= half4 ? 1 : 0, c4 = j - side * half4, nt = side ? nt_nb : nt_in;
-                const float *src = rows + (long)side * 16 * (P >> 1);
-                int4 m = make_int4(0, 0, 0, 0);
-                for (int t0 = 0; t0 < nt; t0 += 8) {          // (eight loads in flight: a side has 3.5 tiles on average, 16 at most)
-                    float4 v[8];
-#pragma unroll
-                    for (int t = 0; t < 8; ++t)
-                        if (t0 + t < nt) v[t] = lrg_ld_coh4(src, (unsigned)((t0 + t) * (P >> 1) + 4 * c4) * 4u);
-#pragma unroll
-                    for (int t = 0; t < 8; ++t)
-                        if (t0 + t < nt) {
-                            m.x = max(m.x, __float_as_int(v[t].x)); m.y = max(m.y, __float_as_int(v[t].y));
-                            m.z = max(m.z, __float_as_int(v[t].z)); m.w = max(m.w, __float_as_int(v[t].w));
-                        }
-                }
-                *reinterpret_cast<int4 *>(pl + 4 * j) = m;
-            }
-        } else {   // the slot's pooled row: one 16-byte load per lane
-#ifndef LRG_EXP_NO_UNIT_LOAD      // (experiment switch, --policy gt only)
-            const float *src = g.pooled + (long)slot * P;
-            for (int j = tid; j < (P >> 2); j += FTHREADS)
-                *reinterpret_cast<float4 *>(pl + 4 * j) = lrg_ld_coh4(src, (unsigned)j * 16u);
-#endif
-        }
-        team.sync();
-        {
-            const float *w = wl + (r * kq) * LRG_GEMV_UNIT_COLS + c;
-            const float *p = pl + r * kq;
-            float acc = 0.f;
-            for (int kb = 0; kb < kq; kb += 16) {
-                float wv[16];
-                float4 pv[4];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) wv[u] = w[(kb + u) * LRG_GEMV_UNIT_COLS];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) pv[u] = *reinterpret_cast<const float4 *>(p + kb + 4 * u);
-                const float pk[16] = {pv[0].x, pv[0].y, pv[0].z, pv[0].w, pv[1].x, pv[1].y, pv[1].z, pv[1].w,
-                                      pv[2].x, pv[2].y, pv[2].z, pv[2].w, pv[3].x, pv[3].y, pv[3].z, pv[3].w};
-#pragma unroll
-                for (int uu = 0; uu < 16; ++uu) {
-                    const int u = (uu & 8) | ((uu & 1) << 2) | ((uu >> 1) & 3);      // k = 8g + 0, 4, 1, 5, 2, 6, 3, 7 (lrg_async_gemv)
-                    acc = fmaf(pk[u], wv[u], acc);
-                }
-            }
-            part[r * LRG_GEMV_UNIT_COLS + c] = acc;
-        }
-        team.sync();
-        // the sums and the arrival by the LAST wavefront: the first is back at the mailboxes while these stores drain
-        if (wave == 3) {
-            {   // (32 sums, stored as eight 16-byte pieces)
-                float sum = part[lane & (LRG_GEMV_UNIT_COLS - 1)];
-#pragma unroll
-                for (int q = 1; q < 8; ++q) sum += part[q * LRG_GEMV_UNIT_COLS + (lane & (LRG_GEMV_UNIT_COLS - 1))];
-                sum += bias;
-                const float v0 = __shfl(sum, 4 * (lane & 7)), v1 = __shfl(sum, 4 * (lane & 7) + 1), v2 = __shfl(sum, 4 * (lane & 7) + 2), v3 = __shfl(sum, 4 * (lane & 7) + 3);
-                if (lane < LRG_GEMV_UNIT_COLS / 4) lrg_st_coh4(g.hb[z] + (long)slot * g.C + col0, (unsigned)lane * 16u, make_float4(v0, v1, v2, v3));
-            }
-            lrg_drain_stores();
-            if (lane == 0) {
-                int32_t *sy = A.sync + (long)slot * LRG_ASYNC_SYNC_WORDS;
-                if (LRG_DBG(A)) {
-                    const int done = __hip_atomic_fetch_add(&sy[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-                    const long long now = wall_clock64();
-                    lrg_dbg_add(A, 8 + 2 * LRG_TASK_GEMV, now - t_task); lrg_dbg_add(A, 9 + 2 * LRG_TASK_GEMV, 1);
-                    if (done == lrg_ld_coh(&sy[5])) lrg_dbg_add(A, 3, (int)((unsigned)now - (unsigned)lrg_ld_coh(&sy[8])));
-                } else {
-                    __hip_atomic_fetch_add(&sy[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-    }
-}
-
-// ---- a pooled-product unit of HALF-TEAMS (round 6): eight tasks in flight per unit instead of four ----
-// With the register tiles a step is ~69 us and sixteen units x four teams x 3.3 us a task are 81 % busy at 0.99 M evaluations a second: a slot's pooled product
-// queues for the slowest of its sixteen units (15 us from the last branch tile to the last sum, profiles/r06_bench_debug_68_reg_tiles.log).  A task's 3.3 us are
-// latencies (the ring entry, the slot's pooled row, two barriers, the store, the arrival), not arithmetic, and a fifth team has no place: four staged rows are all the
-// LDS holds beside the unit's 128 KB slice.  Here a task is run by TWO wavefronts: the row comes in ONE trip (16 bytes of either half per thread) and is staged half
-// at a time (2 KB); a lane owns a column and TWO of the eight K ranges (256 FMAs).  Eight half-teams = sixteen wavefronts: twice the tasks in flight on the same LDS.
-// (First form: no staging, the row's values read chunk by chunk with write-through-coherent loads one chunk ahead -- sixteen dependent trips to the memory side per
-//  task: 15 us a task, 530 k instance-steps/s.)  The sums are those of lrg_async_gemv_unit bit for bit (per K range a chain
-// over k = 8g + 0, 4, 1, 5, 2, 6, 3, 7; the eight partial sums in order; the bias last).
-#define LRG_GEMV_UNIT2_TEAM_FLOATS(P) ((P) / 2 + 8 * LRG_GEMV_UNIT_COLS + 32)      // half a pooled row, partial sums, task words + barrier counter
-#define LRG_GEMV_UNIT2_FLOATS(P) ((P) * LRG_GEMV_UNIT_COLS + 8 * LRG_GEMV_UNIT2_TEAM_FLOATS(P) + 4)
-// (LrgLdsPair, the two wavefronts' meeting: lrg_fused_tile.inl, beside LrgLdsTeam -- the register branch tiles' wave pairs use it too)
-
-LRG_ASYNC_ROLE void lrg_async_gemv_unit2(lrg_kargs_ptr kp_, int unit_, long long t_launch) {
-    const lrg_kargs_ptr kp = lrg_uniform(kp_);
-    const int unit = lrg_uniform(unit_);
-    const LrgAsyncArgs &A = LRG_ASYNC_KARGS().A;
-    const LrgGemvArgs &g = A.gemv;
-    const int P = g.P, kq = P >> 3;
-    const int upz = g.C / LRG_GEMV_UNIT_COLS;
-    const int z = unit / upz, col0 = (unit - z * upz) * LRG_GEMV_UNIT_COLS;
-    float *wl = lrg_async_smem;                                // [P][32] this unit's columns of head z's pooled kernel
-    {
-        const float *w = g.w[z] + col0;
-        for (int i = threadIdx.x; i < P * (LRG_GEMV_UNIT_COLS / 4); i += LRG_FRONT_THREADS) {
-            const int row = i >> 3, q = i & 7;
-            *reinterpret_cast<float4 *>(wl + row * LRG_GEMV_UNIT_COLS + 4 * q) = *reinterpret_cast<const float4 *>(w + (long)row * g.ldw + 4 * q);
-        }
-    }
-    const int ht = lrg_uniform((int)threadIdx.x >> 7);
-    float *prow_lds = lrg_async_smem + P * LRG_GEMV_UNIT_COLS + ht * LRG_GEMV_UNIT2_TEAM_FLOATS(P);      // [P / 2] half of the slot's pooled row
-    float *part = prow_lds + P / 2;                                                                 // [8][32] partial sums
-    int *word = reinterpret_cast<int *>(part + 8 * LRG_GEMV_UNIT_COLS);                            // [0], [1] the task of even / odd rounds, [4] barrier counter
-    int *ctl = reinterpret_cast<int *>(lrg_async_smem + P * LRG_GEMV_UNIT_COLS + 8 * LRG_GEMV_UNIT2_TEAM_FLOATS(P));      // [0] the unit's next ring entry
-    if ((threadIdx.x & 127) == 0) { word[0] = 0; word[1] = 0; word[4] = 0; }
-    if (threadIdx.x < 4) ctl[threadIdx.x] = 0;
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    LrgLdsPair pair;
-    pair.cnt = &word[4]; pair.target = 0; pair.gave_up = &A.queue[LRG_AQ_ABORT];
-    const int tid = (int)threadIdx.x & 127, lane = tid & 63, wave = tid >> 6;
-    const int c = lane & 31, h = lane >> 5;
-    const float bias = g.bias[z] ? g.bias[z][col0 + c] : 0.f;
-    const int32_t *ring = A.queue + LRG_AQ_RING + 2 * (A.qmask + 1);
-    for (int round = 0;; round ^= 1) {
-        long long t_task = 0;
-        if (wave == 0) {
-            int slot = -2;
-            int i = 0;
-            if (lane == 0) i = __hip_atomic_fetch_add(&ctl[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            i = __shfl(i, 0);
-            const int32_t *e = ring + (i & A.gmask);
-            const int tag = lrg_gemv_ring_tag(i, A.gmask);
-            for (unsigned spin = 0; slot == -2; ++spin) {
-                const int code = lrg_ld_coh(e);
-                if ((code >> 20) == tag) { slot = code & 0xFFFFF; break; }
-                if ((spin & 7) == 7) {
-                    if (lrg_ld_coh(&A.queue[LRG_AQ_FRONTS_DONE]) >= A.n_front || lrg_ld_coh(&A.queue[LRG_AQ_ABORT])) slot = -1;
-                    else if ((spin & 1023) == 1023 && wall_clock64() - t_launch > A.abort_ticks) { lrg_st_coh(&A.queue[LRG_AQ_ABORT], 4); slot = -1; }
-                }
-                if (slot == -2) __builtin_amdgcn_s_sleep(2);
-            }
-            if (lane == 0) word[round] = slot;
-        }
-        pair.sync();
-        const int entry = word[round];
-        if (entry < 0) return;
-        const int slot = entry & 0xFFF;
-        if (LRG_DBG(A)) t_task = wall_clock64();
-        // the slot's pooled row: ONE trip -- every thread of the pair takes 16 bytes of either half (four K ranges each) -- and half a row at a time in LDS: eight
-        // staged HALF rows are what fits beside the slice.  Ranges 2 wave + h (first half) and 4 + 2 wave + h (second): each a chain of kq FMAs.
-        const float4 ph0 = lrg_ld_coh4(g.pooled + (long)slot * P, (unsigned)tid * 16u), ph1 = lrg_ld_coh4(g.pooled + (long)slot * P, (unsigned)(128 + tid) * 16u);
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            if (pass) pair.sync();                                   // (everybody is done with the first half)
-            *reinterpret_cast<float4 *>(prow_lds + 4 * tid) = pass ? ph1 : ph0;
-            pair.sync();
-            const int rl = 2 * wave + h, r = 4 * pass + rl;
-            const float *w = wl + (r * kq) * LRG_GEMV_UNIT_COLS + c;
-            const float *p = prow_lds + rl * kq;
-            float acc = 0.f;
-            for (int kb = 0; kb < kq; kb += 16) {
-                float wv[16];
-                float4 pv[4];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) wv[u] = w[(kb + u) * LRG_GEMV_UNIT_COLS];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) pv[u] = *reinterpret_cast<const float4 *>(p + kb + 4 * u);
-                const float pk[16] = {pv[0].x, pv[0].y, pv[0].z, pv[0].w, pv[1].x, pv[1].y, pv[1].z, pv[1].w,
-                                      pv[2].x, pv[2].y, pv[2].z, pv[2].w, pv[3].x, pv[3].y, pv[3].z, pv[3].w};
-#pragma unroll
-                for (int uu = 0; uu < 16; ++uu) {
-                    const int u = (uu & 8) | ((uu & 1) << 2) | ((uu >> 1) & 3);      // k = 8g + 0, 4, 1, 5, 2, 6, 3, 7 (lrg_async_gemv)
-                    acc = fmaf(pk[u], wv[u], acc);
-                }
-            }
-            part[r * LRG_GEMV_UNIT_COLS + c] = acc;
-        }
-        pair.sync();
-        // the sums and the arrival by the second wavefront: the first is back at the ring while these stores drain
-        if (wave == 1) {
-            float sum = part[lane & (LRG_GEMV_UNIT_COLS - 1)];
-#pragma unroll
-            for (int q = 1; q < 8; ++q) sum += part[q * LRG_GEMV_UNIT_COLS + (lane & (LRG_GEMV_UNIT_COLS - 1))];
-            sum += bias;
-            const float v0 = __shfl(sum, 4 * (lane & 7)), v1 = __shfl(sum, 4 * (lane & 7) + 1), v2 = __shfl(sum, 4 * (lane & 7) + 2), v3 = __shfl(sum, 4 * (lane & 7) + 3);
-            if (lane < LRG_GEMV_UNIT_COLS / 4) lrg_st_coh4(g.hb[z] + (long)slot * g.C + col0, (unsigned)lane * 16u, make_float4(v0, v1, v2, v3));
-            lrg_drain_stores();
-            if (lane == 0) {
-                int32_t *sy = A.sync + (long)slot * LRG_ASYNC_SYNC_WORDS;
-                if (LRG_DBG(A)) {
-                    const int done = __hip_atomic_fetch_add(&sy[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-                    const long long now = wall_clock64();
-                    lrg_dbg_add(A, 8 + 2 * LRG_TASK_GEMV, now - t_task); lrg_dbg_add(A, 9 + 2 * LRG_TASK_GEMV, 1);
-                    if (done == lrg_ld_coh(&sy[5])) lrg_dbg_add(A, 3, (int)((unsigned)now - (unsigned)lrg_ld_coh(&sy[8])));
-                } else {
-                    __hip_atomic_fetch_add(&sy[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-    }
 }
 
 // a head tile that was started beside the pooled-product units waits here for its slot's product (lrg_fused_tile, WAIT::late)
@@ -1728,7 +1418,8 @@ __global__ __launch_bounds__(LRG_FRONT_THREADS) void lrg_grow_async_kernel(LrgAs
     if (tid == 0) __hip_atomic_fetch_add(&K.A.queue[LRG_AQ_ARRIVED], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (nobody waits for the result)
     if ((int)blockIdx.x >= K.A.n_front && (int)blockIdx.x < K.A.n_front + K.A.gemv_units) {
         // (half-teams: eight tasks in flight per unit; not with per-tile pool rows, whose maximum is taken while the row is staged)
-        if (K.A.unit_pairs && !K.A.pool_rows) lrg_async_gemv_unit2(kp, (int)blockIdx.x - K.A.n_front, t_launch);
+        if (K.A.unit_regs) lrg_async_gemv_unit3(kp, (int)blockIdx.x - K.A.n_front, t_launch);      // (the slice in registers: before the half-teams)
+        else if (K.A.unit_pairs && !K.A.pool_rows) lrg_async_gemv_unit2(kp, (int)blockIdx.x - K.A.n_front, t_launch);
         else lrg_async_gemv_unit(kp, (int)blockIdx.x - K.A.n_front, t_launch);
         return;
     }

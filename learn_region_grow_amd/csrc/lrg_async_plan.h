@@ -121,6 +121,7 @@ struct LrgAsyncArgs {
     int rt_head_every;           // register tiles, CUs by role (lrg_rt_role below): of every so many CUs of an XCD's share of the worker grid one runs head tiles on both
                                  // teams, the others branch tiles on team 0 alone (0: none; never beside rt_bb_every)
     int unit_pairs;             // 1: the pooled-product units run their tasks on half-teams of two wavefronts (lrg_async_gemv_unit2)
+    int unit_regs;               // 1: the pooled-product units keep their slice in registers and stream the rows through an LDS FIFO (lrg_async_gemv_unit3); before unit_pairs
     int reg_tiles;               // 1: the worker kernel's workgroups are all alike -- team 0 runs the branch tiles of ring 0 as REGISTER TILES (lrg_team_branch_tile_reg: a team
                                  // of four wavefronts per tile, layers 0 - 2 per wavefront in registers, one barrier), team 1 the pooled blocks and head tiles of ring 1
                                  // -- unless the CUs have roles (rt_bb_every, rt_head_every: lrg_rt_role below)
@@ -176,6 +177,7 @@ struct LrgAsyncKArgs {
 // The shape of a launch that the Python host chooses -- front workgroups, teams, units, parts, CUs, fill-in workgroups, branch_waves -- is set in LrgAsyncBuffers.
 struct LrgAsyncSwitches {
     int unit_pairs;              // LRG_ASYNC_UNIT_PAIRS: 0 / non-zero forces the units' half-teams off / on; unset: on from 84 slots (never on unless the pooled feature has 1024 columns)
+    int unit_regs;               // LRG_ASYNC_UNIT_REGS: 0 / non-zero forces the units' register form off / on; unset: see plan_units (never on unless the heads are the paper's: 1024 pooled features, 256 columns)
     int gemv_batch;              // LRG_ASYNC_GEMV_BATCH: > 0 batched pooled products where they fit (a launch without units); -1: off
     double gemv_batch_us;        // LRG_ASYNC_GEMV_BATCH_US: how long a batch waits for more slots, in us; 1.5
     int tail_heads;              // LRG_ASYNC_TAIL_HEADS: 0 = a head tile of the slot's own per tail; 1: the heads of the tails on the shared tiles too
@@ -213,3 +215,8 @@ int lrg_async_check(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points,
 int lrg_async_plan(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, const LrgGrowParams *params, const LrgWeights *weights,
                    const LrgPackedBuffers *b, const LrgAsyncBuffers *ab, int max_steps, int budget_us, int cus, const LrgAsyncSwitches &sw,
                    LrgAsyncPlan *plan);
+// The shape of the process's last lrg_grow_async launch, for tests and tools (not part of include/lrg_hip.h): up to LRG_ASYNC_LAST_PLAN_WORDS words --
+// [0] 1 once a launch was planned, [1] two_kernels, [2] front_wgs, [3] worker_wgs, [4] n_front, [5] gemv_units, [6] unit_pairs, [7] unit_regs, [8] reg_tiles,
+// [9] teams, [10] per-tile pool rows in use, [11] n_slots.  Returns the words written.
+#define LRG_ASYNC_LAST_PLAN_WORDS 12
+extern "C" int lrg_async_last_plan(int32_t *out, int n);

@@ -71,6 +71,7 @@ size_t lrg_grow_async_pool_rows_bytes(const LrgWeights *weights, int n_slots) {
 LrgAsyncSwitches lrg_async_switches() {
     LrgAsyncSwitches s;
     s.unit_pairs = lrg_env_int("LRG_ASYNC_UNIT_PAIRS", LRG_ENV_UNSET);
+    s.unit_regs = lrg_env_int("LRG_ASYNC_UNIT_REGS", LRG_ENV_UNSET);
     s.gemv_batch = lrg_env_int("LRG_ASYNC_GEMV_BATCH", -1);
     s.gemv_batch_us = lrg_env_real("LRG_ASYNC_GEMV_BATCH_US", 1.5);
     s.tail_heads = lrg_env_int("LRG_ASYNC_TAIL_HEADS", 1);
@@ -232,6 +233,12 @@ static void plan_units(const LrgAsyncBuffers *ab, const LrgWeights *weights, con
     // P / 2 = 512 -- lite 2 (P = 512) keeps the four-wavefront units, which are general in P
     const bool pairs_fit = g.P == 1024;
     A->unit_pairs = !pairs_fit ? 0 : sw.unit_pairs != LRG_ENV_UNSET ? (sw.unit_pairs ? 1 : 0) : (units && n_slots >= 84 ? 1 : 0);
+    // (the slice in registers, lrg_async_gemv_unit3: the kernel prefers it over the half-teams, whose field keeps its value.  For the paper's heads only -- 64 weights
+    //  a lane are a [1024, 32] slice on eight wavefronts -- and where its FIFO fits the units' LDS, which it does not enlarge; LRG_ASYNC_UNIT_REGS=0 / 1 forces.
+    //  The figures behind the default: profiles/unit_registers.txt)
+    const bool regs_fit = units && g.P == LRG_GEMV_UNIT3_P && g.C == 256 &&
+                          (size_t)LRG_GEMV_UNIT3_FLOATS * sizeof(float) <= (size_t)max((int)LRG_GEMV_UNIT_FLOATS(g.P), (int)LRG_GEMV_UNIT2_FLOATS(g.P)) * sizeof(float) + 16;
+    A->unit_regs = !regs_fit ? 0 : sw.unit_regs != LRG_ENV_UNSET ? (sw.unit_regs ? 1 : 0) : 1;
     // without the units: the pooled products in batches (lrg_async.inl, LRG_GEMV_BATCH) where slots become ready faster than a batch's patience --
     // LRG_ASYNC_GEMV_BATCH=0 / =1: off / on whatever the slot count; LRG_ASYNC_GEMV_BATCH_US: the patience
     const int batch_us10 = (int)(10.0 * sw.gemv_batch_us);
@@ -579,6 +586,9 @@ static int async_launch(const LrgAsyncPlan &plan, int cus, hipStream_t st) {
     return 0;
 }
 
+// what the process's last lrg_grow_async planned (lrg_async_last_plan, lrg_async_plan.h; for tests and tools: callers that launch from several threads see any one of them)
+static int32_t async_last_plan[LRG_ASYNC_LAST_PLAN_WORDS] = {};
+
 int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, const LrgGrowParams *params, const LrgWeights *weights,
                    const LrgPackedBuffers *b, const LrgAsyncBuffers *ab, int max_steps, int budget_us, void *stream) {
     int rc = lrg_async_check(slots, rooms, n_slots, max_points, params, weights, b, ab, max_steps, budget_us);
@@ -588,5 +598,17 @@ int lrg_grow_async(LrgSlot *slots, LrgRoom *rooms, int n_slots, int max_points, 
     LrgAsyncPlan plan;
     if ((rc = lrg_async_plan(slots, rooms, n_slots, max_points, params, weights, b, ab, max_steps, budget_us, prop.multiProcessorCount, lrg_async_switches(), &plan)))
         return rc;
+    {
+        const LrgAsyncArgs &A = plan.K.A;
+        const int32_t v[LRG_ASYNC_LAST_PLAN_WORDS] = {1, plan.two_kernels ? 1 : 0, plan.front_wgs, plan.worker_wgs, A.n_front, A.gemv_units, A.unit_pairs, A.unit_regs, A.reg_tiles, A.teams,
+                                                      A.pool_rows ? 1 : 0, A.n_slots};
+        for (int i = 0; i < LRG_ASYNC_LAST_PLAN_WORDS; ++i) async_last_plan[i] = v[i];
+    }
     return async_launch(plan, prop.multiProcessorCount, (hipStream_t)stream);
+}
+
+int lrg_async_last_plan(int32_t *out, int n) {
+    if (!out || n < 0) return LRG_EINVAL;
+    for (int i = 0; i < n && i < LRG_ASYNC_LAST_PLAN_WORDS; ++i) out[i] = async_last_plan[i];
+    return min(n, LRG_ASYNC_LAST_PLAN_WORDS);
 }

@@ -6,6 +6,7 @@
 // --full prints the canonical text itself behind every line.  tests/test_async_plan.py compares the output with tests/golden/async_plan_table.txt, so that
 // a change to a decision of the plan shows as the launches it moves.
 // --roles prints another table instead: the register-tile CUs by role over the same sweep (roles_rows below; tests/test_async_roles.py).
+// --unit-regs prints a third: the form of the pooled-product units over the same sweep (unit_regs_rows below; tests/test_async_unit_regs.py).
 //
 // No kernel and no HIP call: the plan is a function of its arguments, the CU count and the switches.  Every address is made up (a region number in the bits
 // from 40 up, an offset below) and none is dereferenced; the text names pointers by region and offset, never by value, and never prints a struct's raw bytes.
@@ -256,9 +257,43 @@ static void roles_rows(const std::string &label, const Setup &S0) {
     if (!reg) printf("%s\n", plain.c_str());
 }
 
+// ---- --unit-regs: the form of the pooled-product units (LrgAsyncArgs.unit_regs, the switch LRG_ASYNC_UNIT_REGS) ----
+// For every granted case of the sweep one line, the plan with the switch unset, 0 and 1:
+//     label|gemv_units unit_pairs|unit_regs with the switch unset, 0, 1|lds with the switch unset, 0, 1
+// Exit code 1: the register form without units, or for other heads than the paper's (1024 pooled features, 256 columns), or forced off and still on, or a plan
+// whose units, half-teams or LDS move with the switch.
+static bool unit_regs = false;
+static int unit_regs_bad = 0;
+static void unit_regs_rows(const std::string &label, const Setup &S0) {
+    static LrgAsyncPlan plan[3];
+    const int values[3] = {default_switches.unit_regs, 0, 1};
+    if (lrg_async_check(S0.slots, S0.rooms, S0.n_slots, S0.max_points, &S0.prm, &S0.w, &S0.b, &S0.ab, S0.max_steps, S0.budget_us)) return;
+    for (int i = 0; i < 3; ++i) {
+        Setup S = S0;
+        S.sw.unit_regs = values[i];
+        memset(static_cast<void *>(&plan[i]), 0xA5, sizeof(plan[i]));
+        if (lrg_async_plan(S.slots, S.rooms, S.n_slots, S.max_points, &S.prm, &S.w, &S.b, &S.ab, S.max_steps, S.budget_us, S.cus, S.sw, &plan[i])) return;
+    }
+    const LrgAsyncArgs &A = plan[0].K.A;
+    bool bad = false;
+    for (int i = 0; i < 3; ++i) {
+        const LrgAsyncArgs &B = plan[i].K.A;
+        const bool papers_heads = B.gemv.P == 1024 && B.gemv.C == 256;
+        if (B.unit_regs != 0 && B.unit_regs != 1) bad = true;
+        if (B.unit_regs && (!B.gemv_units || !papers_heads)) bad = true;
+        if (B.gemv_units != A.gemv_units || B.unit_pairs != A.unit_pairs || plan[i].lds != plan[0].lds || plan[i].front_wgs != plan[0].front_wgs) bad = true;
+    }
+    if (plan[1].K.A.unit_regs) bad = true;
+    if (plan[2].K.A.unit_regs != ((A.gemv_units && A.gemv.P == 1024 && A.gemv.C == 256) ? 1 : 0)) bad = true;
+    if (bad) { fprintf(stderr, "async_plan_table: %s: the units' register form where it must not be, or a plan that moves with its switch\n", label.c_str()); unit_regs_bad = 1; }
+    printf("%s|%d %d|%d %d %d|%lld %lld %lld\n", label.c_str(), A.gemv_units, A.unit_pairs, A.unit_regs, plan[1].K.A.unit_regs, plan[2].K.A.unit_regs,
+           (long long)plan[0].lds, (long long)plan[1].lds, (long long)plan[2].lds);
+}
+
 static void run(const std::string &label, const Setup &S) {
     if (!labels.insert(label).second) { fprintf(stderr, "async_plan_table: label used twice: %s\n", label.c_str()); exit(2); }
     if (roles) { roles_rows(label, S); return; }
+    if (unit_regs) { unit_regs_rows(label, S); return; }
     static LrgAsyncPlan plan;
     memset(static_cast<void *>(&plan), 0xA5, sizeof(plan));      // (a field that the plan leaves unset shows as that pattern, not as what the last case left)
     int rc = lrg_async_check(S.slots, S.rooms, S.n_slots, S.max_points, &S.prm, &S.w, &S.b, &S.ab, S.max_steps, S.budget_us);
@@ -291,10 +326,13 @@ int main(int argc, char **argv) {
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--full")) full = true;
         else if (!strcmp(argv[i], "--roles")) roles = true;
-        else { fprintf(stderr, "usage: async_plan_table [--full | --roles]\n"); return 2; }
+        else if (!strcmp(argv[i], "--unit-regs")) unit_regs = true;
+        else { fprintf(stderr, "usage: async_plan_table [--full | --roles | --unit-regs]\n"); return 2; }
     }
     clearenv();                                  // (the switches' defaults, not this shell's)
     default_switches = lrg_async_switches();
+    if (unit_regs) printf("# label|gemv_units unit_pairs|unit_regs with LRG_ASYNC_UNIT_REGS unset, 0, 1|lds with it unset, 0, 1\n");
+    else
     printf("%s\n", roles ? "# label|rt_head_every asked|rt_head_every rt_bb_every|CUs MIXED BRANCH2 BRANCH1 HEAD2|teams ring0 ring1 fill|fewest ring0 ring1 teams on 8 consecutive workgroups"
                          : COLUMNS);
     char l[128];
@@ -445,6 +483,7 @@ int main(int argc, char **argv) {
     vary("plan/add_w0+8", B, [](Setup &S) { S.w.add_w[0] = at<float>(R_ADD_W, 8); });
 
     if (roles) return roles_bad;
+    if (unit_regs) return unit_regs_bad;
     for (const auto &q : ring_end) printf("Q %d %lld %zu\n", q.first, q.second, lrg_grow_async_queue_bytes(q.first) / sizeof(int32_t));
 
     // what the sweep must hold

@@ -4,7 +4,9 @@
 // k = 8g + 0, 4, 1, 5, 2, 6, 3, 7, then bias, then ReLU: lrg_fused_tile.inl), and times a task with 1 .. 16 wavefronts per CU on 1 / 64 / 200 CUs.
 // `wave_tile_probe pairs`: the register branch tile on the teams of a 512-thread workgroup, as the free-running worker kernel runs it (pairs_kernel below).
 // `wave_tile_probe roles`: head and branch teams of such a workgroup by the role of their CU -- who shares the SIMDs with whom (roles_kernel below).
+// `wave_tile_probe units`: the three forms of the pooled-product units (csrc/lrg_async_units.inl), each alone on hand-made rows and ring entries (units_kernel below).
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +14,16 @@
 #include <vector>
 extern __shared__ __attribute__((aligned(16))) float lrg_async_smem[];
 #include "lrg_wave_tile.inl"
+// (mode `units`: the pooled-product units as lrg_async.inl includes them -- the few words it defines before that, said again here)
+#include "lrg_async_plan.h"
+#define LRG_FRONT_THREADS 1024
+#define LRG_ASYNC_SYNC_WORDS 16
+#define LRG_TASK_GEMV 2
+#define LRG_ASYNC_DEBUG 0
+#define LRG_DBG(A) (LRG_ASYNC_DEBUG && (A).dbg)
+__device__ __forceinline__ void lrg_dbg_add(const LrgAsyncArgs &A, int i, long long v) { if (LRG_DBG(A)) atomicAdd(&A.dbg[i], (unsigned long long)v); }
+__device__ __forceinline__ void lrg_drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+#include "lrg_async_units.inl"
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
 
@@ -528,8 +540,166 @@ static int pairs_main(bool roles) {
     return bad ? 1 : 0;
 }
 
+// ---- mode `units`: sixteen pooled-product units of one form and a driver workgroup in the front workgroups' place ----
+// Thread i of the driver owns slot i: it writes the slot's ring entry as the last branch tile would (a ticket from LRG_AQ_GTAIL, the tagged entry), waits for the
+// sixteen arrivals on the slot's sync[1] and writes the next, `rounds` times; then the driver counts itself among the fronts that are done and the units leave.
+// One active slot: a task at a time, the ticks from the entry's store to the sixteenth arrival seen are the stage's latency.  96 active slots: the ring is kept
+// full and the tasks per second are the units' capacity.  Every wait is bounded by abort_ticks (one second), as in a launch.
+struct UArgs { int form, n_active, rounds; unsigned long long *out; };      // out: [0] ticks from the first entry to the last arrival, [1] ticks entry -> arrival, summed
+__global__ __launch_bounds__(LRG_FRONT_THREADS) void units_kernel(LrgAsyncKArgs K, UArgs u) {
+    const long long t_launch = wall_clock64();
+#if defined(__HIP_DEVICE_COMPILE__)
+    lrg_kargs_ptr kp = (lrg_kargs_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+#else
+    lrg_kargs_ptr kp = nullptr;
+#endif
+    if (blockIdx.x >= 1) {
+        const int unit = (int)blockIdx.x - 1;
+        if (u.form == 3) lrg_async_gemv_unit3(kp, unit, t_launch);
+        else if (u.form == 2) lrg_async_gemv_unit2(kp, unit, t_launch);
+        else lrg_async_gemv_unit(kp, unit, t_launch);
+        return;
+    }
+    const LrgAsyncArgs &A = K.A;
+    const int slot = threadIdx.x;
+    int32_t *sy = A.sync + (long)slot * LRG_ASYNC_SYNC_WORDS;
+    int issued = 0, done = 0;
+    long long t_issue = 0, lat = 0;
+    if (slot < u.n_active)
+        for (unsigned spin = 1; done < u.rounds; ++spin) {
+            if (issued == done) {
+                const int nt_in = 1 + (slot & 15), nt_nb = 16 - (slot & 15);
+                const int i = __hip_atomic_fetch_add(&A.queue[LRG_AQ_GTAIL], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                t_issue = wall_clock64();
+                lrg_st_coh(&A.queue[LRG_AQ_RING + 2 * (A.qmask + 1) + (i & A.gmask)], (lrg_gemv_ring_tag(i, A.gmask) << 20) | ((nt_in - 1) << 16) | ((nt_nb - 1) << 12) | slot);
+                ++issued;
+            } else if (lrg_ld_coh(&sy[1]) >= A.gemv_units * issued) {
+                lat += wall_clock64() - t_issue;
+                ++done;
+            } else {
+                if ((spin & 255u) == 0 && (lrg_ld_coh(&A.queue[LRG_AQ_ABORT]) || wall_clock64() - t_launch > A.abort_ticks)) { lrg_st_coh(&A.queue[LRG_AQ_ABORT], 9); break; }
+                __builtin_amdgcn_s_sleep(1);
+            }
+        }
+    if (slot < u.n_active) atomicAdd(&u.out[1], (unsigned long long)lat);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u.out[0] = (unsigned long long)(wall_clock64() - t_launch);
+        __hip_atomic_fetch_add(&A.queue[LRG_AQ_FRONTS_DONE], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+static int units_main() {
+    const int P = 1024, C = 256, S = 96, TILES = 16, ROUNDS = 8;
+    srand(2024);
+    auto rnd = []() { return (float)rand() / RAND_MAX * 2.f - 1.f; };
+    std::vector<float> w[2], bias[2], pooled((size_t)S * P), prow((size_t)S * 2 * TILES * (P / 2)), pooled_max((size_t)S * P, 0.f);
+    for (int z = 0; z < 2; ++z) {
+        w[z].resize((size_t)P * C); bias[z].resize(C);
+        for (auto &v : w[z]) v = rnd() * 0.05f;
+        for (auto &v : bias[z]) v = rnd() * 0.1f;
+    }
+    for (auto &v : pooled) { v = rnd() * 3.f; if (v < 0.f) v = 0.f; }      // (pooled features are maxima of ReLU outputs: about half of them zero here)
+    // per-tile pool rows: slot s has 1 + s % 16 inlier tiles and 16 - s % 16 neighbour tiles (1 and 16 of either among them); the rows of tiles it does not have hold
+    // a huge value that no maximum may pick up
+    for (int s = 0; s < S; ++s)
+        for (int side = 0; side < 2; ++side) {
+            const int nt = side ? 16 - (s & 15) : 1 + (s & 15);
+            for (int t = 0; t < TILES; ++t)
+                for (int c = 0; c < P / 2; ++c) {
+                    float v = rnd() * 3.f;
+                    if (v < 0.f) v = 0.f;
+                    if (t >= nt) v = 3e38f;
+                    prow[(((size_t)s * 2 + side) * TILES + t) * (P / 2) + c] = v;
+                    if (t < nt) pooled_max[(size_t)s * P + side * (P / 2) + c] = fmaxf(pooled_max[(size_t)s * P + side * (P / 2) + c], v);
+                }
+        }
+    // the host chain: eight K ranges of 128, in a range one chain of fmaf over k = 8g + 0, 4, 1, 5, 2, 6, 3, 7 for g ascending, the eight partial sums in order, the bias
+    auto host = [&](const std::vector<float> &rows, std::vector<float> &out) {
+        out.assign((size_t)2 * S * C, 0.f);
+        static const int perm[8] = {0, 4, 1, 5, 2, 6, 3, 7};
+        for (int z = 0; z < 2; ++z)
+            for (int s = 0; s < S; ++s)
+                for (int c = 0; c < C; ++c) {
+                    float part[8];
+                    for (int r = 0; r < 8; ++r) {
+                        float acc = 0.f;
+                        for (int g = 0; g < 16; ++g)
+                            for (int j = 0; j < 8; ++j) { const int k = r * 128 + 8 * g + perm[j]; acc = fmaf(rows[(size_t)s * P + k], w[z][(size_t)k * C + c], acc); }
+                        part[r] = acc;
+                    }
+                    float sum = part[0];
+                    for (int r = 1; r < 8; ++r) sum += part[r];
+                    out[((size_t)z * S + s) * C + c] = sum + bias[z][c];
+                }
+    };
+    std::vector<float> ref_row, ref_max;
+    host(pooled, ref_row); host(pooled_max, ref_max);
+    auto up = [&](const std::vector<float> &v) { float *dd; CK(hipMalloc(&dd, v.size() * 4)); CK(hipMemcpy(dd, v.data(), v.size() * 4, hipMemcpyHostToDevice)); return dd; };
+    static LrgAsyncKArgs K;
+    memset(static_cast<void *>(&K), 0, sizeof(K));
+    LrgAsyncArgs &A = K.A;
+    float *hb, *d_prow = up(prow);
+    CK(hipMalloc(&hb, (size_t)2 * S * C * 4));
+    A.gemv.pooled = up(pooled);
+    for (int z = 0; z < 2; ++z) { A.gemv.w[z] = up(w[z]); A.gemv.bias[z] = up(bias[z]); A.gemv.hb[z] = hb + (size_t)z * S * C; }
+    A.gemv.ldw = C; A.gemv.B = S; A.gemv.P = P; A.gemv.C = C;
+    A.qmask = 63; A.gmask = 255;                 // (a units' ring of 256 entries: 96 slots x 8 rounds go round it three times)
+    const size_t queue_words = LRG_AQ_RING + 2 * (A.qmask + 1) + (A.gmask + 1) + 64;
+    CK(hipMalloc(&A.queue, queue_words * 4)); CK(hipMalloc(&A.sync, (size_t)S * LRG_ASYNC_SYNC_WORDS * 4));
+    A.n_slots = S; A.n_front = 1; A.gemv_units = 2 * C / LRG_GEMV_UNIT_COLS; A.pool_rows_stride = 2 * TILES * (P / 2);
+    A.abort_ticks = 100000000LL;                 // one second
+    unsigned long long *out;
+    CK(hipMalloc(&out, 16));
+    const size_t lds = (size_t)std::max((int)LRG_GEMV_UNIT_FLOATS(P), (int)LRG_GEMV_UNIT2_FLOATS(P)) * 4 + 16;      // (what lrg_async_plan gives the units)
+    static_assert(LRG_GEMV_UNIT3_FLOATS <= LRG_GEMV_UNIT_FLOATS(1024), "the register form's FIFO within the units' LDS");
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(units_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    std::vector<float> got((size_t)2 * S * C);
+    std::vector<int32_t> sy((size_t)S * LRG_ASYNC_SYNC_WORDS), q(queue_words);
+    unsigned long long res[2];
+    // one launch: returns the abort word (0: every wait ended by itself)
+    auto launch = [&](int form, bool pool_rows, int n_active, int rounds) {
+        CK(hipMemset(A.queue, 0, queue_words * 4)); CK(hipMemset(A.sync, 0, sy.size() * 4)); CK(hipMemset(out, 0, 16)); CK(hipMemset(hb, 0xFF, got.size() * 4));
+        A.pool_rows = pool_rows ? d_prow : nullptr;
+        UArgs u; u.form = form; u.n_active = n_active; u.rounds = rounds; u.out = out;
+        hipLaunchKernelGGL(units_kernel, dim3(1 + A.gemv_units), dim3(LRG_FRONT_THREADS), lds, 0, K, u);
+        CK(hipDeviceSynchronize());
+        CK(hipMemcpy(got.data(), hb, got.size() * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(sy.data(), A.sync, sy.size() * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(q.data(), A.queue, q.size() * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(res, out, 16, hipMemcpyDeviceToHost));
+        return q[LRG_AQ_ABORT];
+    };
+    static const char *const names[4] = {"", "four teams", "half-teams", "registers"};
+    size_t bad_all = 0;
+    for (int form = 1; form <= 3; ++form) {
+        for (int pr = 0; pr < 2; ++pr) {
+            if (pr && form == 2) continue;       // (the half-teams do not take per-tile pool rows: the kernel gives those launches the four-team form)
+            const int aborted = launch(form, pr, S, ROUNDS);
+            const std::vector<float> &ref = pr ? ref_max : ref_row;
+            const size_t bad = differ(got, ref, 0, got.size());
+            int complete = 0;
+            for (int s = 0; s < S; ++s) complete += sy[(size_t)s * LRG_ASYNC_SYNC_WORDS + 1] == A.gemv_units * ROUNDS;
+            printf("units form %d (%s), %s: sums %zu of %zu differ from the host chain; slots with all arrivals %d of %d; abort word %d\n", form, names[form],
+                   pr ? "per-tile pool rows" : "pooled rows", bad, got.size(), complete, S, aborted);
+            for (size_t i = 0, shown = 0; i < got.size() && shown < 6; ++i)
+                if (memcmp(&got[i], &ref[i], 4)) { printf("  head %zu slot %zu column %zu: gpu %.9g ref %.9g\n", i / ((size_t)S * C), i / C % S, i % C, got[i], ref[i]); ++shown; }
+            bad_all += bad + (size_t)(S - complete) + (aborted ? 1 : 0);
+            if (aborted) return 1;               // (a wait ran into its bound: nothing more is started)
+        }
+        int aborted = launch(form, false, 1, 2000);
+        printf("UNITS form %d (%s) latency: %8.0f ticks of 10 ns from the entry written to the sixteenth arrival seen, one task at a time (abort word %d)\n", form, names[form],
+               (double)res[1] / 2000.0, aborted);
+        if (aborted) return 1;
+        aborted = launch(form, false, S, 200);
+        printf("UNITS form %d (%s) capacity: %8.0f k tasks/s per unit with %d slots' entries kept in the ring (%d tasks in %llu ticks; abort word %d)\n", form, names[form],
+               (double)S * 200 / ((double)res[0] * 1e-8) * 1e-3, S, S * 200, res[0], aborted);
+        if (aborted) return 1;
+    }
+    return bad_all ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "pairs")) return pairs_main(false);
+    if (argc > 1 && !strcmp(argv[1], "units")) return units_main();
     if (argc > 1 && !strcmp(argv[1], "roles")) return pairs_main(true);
     const int n_slots = 6, rows_per_slot = 96, rows = n_slots * rows_per_slot, n_tiles = rows / 32, F = 13;
     const int Ks[5] = {F, 64, 64, 64, 128}, Ns[5] = {64, 64, 64, 128, 512};
