@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
            'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip', 'lrg_pointnet_train.hip',
-           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip', 'lrg_mcpnet_train.hip', 'lrg_stage.hip', 'lrg_kitti.hip']
+           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip', 'lrg_mcpnet_train.hip', 'lrg_stage.hip', 'lrg_kitti.hip', 'lrg_scan.hip']
 
 LRG_ABI_VERSION = 23      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000

@@ -37,46 +37,41 @@
 #include "lrg_room_hash.h"
 
 #define BL_THREADS 256
-#define BL_SCAN_ITEMS 8                       // per thread: 2048 elements per block
 
 enum { BL_NORMAL = 0, BL_CURVATURE = 1, BL_COLOR = 2, BL_FEATURE = 3, BL_SMOOTHNESS = 4, BL_EMBEDDING = 5, BL_LABELS = 6, BL_FPFH = 7, BL_MASK = 8 };   // 5: lrg_baseline_segment_embedding only, 6: lrg_baseline_segment_labels only, 7: lrg_baseline_segment_fpfh only, 8: lrg_baseline_segment_mask only
 // status bits (lrg_baseline_status)
 enum { BL_ST_WINDOW = 1, BL_ST_DUPLICATE = 2, BL_ST_RANK = 4, BL_ST_STACK = 8 };
 
 struct LrgBaselineLayout {
-    size_t keys, vals;                 // hash: 4 n + 64 rooms slots
+    size_t keys, vals;                 // the rooms' hash segments (lrg_room_hash.h)
     size_t rooms, room_of, parent, size, minkey, ckey, visited, flag, scan, bsum, stack, scal;
     size_t total;
     long hslots, stack_cap;
-    int nb;
 };
 
 static int bl_layout(int N, int R, int mcs, LrgBaselineLayout *L) {
     if (N < 0 || R < 0 || N > (1 << 26) || R > (1 << 20)) return LRG_EINVAL - 70;
     if (mcs < 1 || mcs > LRG_BASELINE_MAX_MIN_CLUSTER) return LRG_EINVAL - 71;
-    L->hslots = 4L * N + 64L * R;
+    L->hslots = lrg_room_hash_slots(N, R);
     // a replayed component of c <= mcs points pushes at most 26 c times (only a point's first pop finds unvisited
     // neighbours): 1 + 26 c entries each, at most 27 n over all components
     L->stack_cap = 27L * N;
-    const long per_block = BL_THREADS * BL_SCAN_ITEMS;
-    L->nb = (int)((N + 1 + per_block - 1) / per_block);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = lrg_align_up(o + bytes, 256); return at; };
-    L->keys = take((size_t)L->hslots * 8);
-    L->vals = take((size_t)L->hslots * 4);
-    L->rooms = take((size_t)(R + 1) * 4);
-    L->room_of = take((size_t)N * 4);
-    L->parent = take((size_t)N * 4);
-    L->size = take((size_t)N * 4);
-    L->minkey = take((size_t)N * 8);
-    L->ckey = take((size_t)N * 4);
-    L->visited = take((size_t)N * 4);
-    L->flag = take((size_t)(N + 1) * 4);
-    L->scan = take((size_t)(N + 1) * 4);
-    L->bsum = take((size_t)(L->nb + 1) * 4);
-    L->stack = take((size_t)L->stack_cap * 4);
-    L->scal = take(64 * 4);
-    L->total = o;
+    LrgArena ws;
+    L->keys = ws.take((size_t)L->hslots * 8);
+    L->vals = ws.take((size_t)L->hslots * 4);
+    L->rooms = ws.take((size_t)(R + 1) * 4);
+    L->room_of = ws.take((size_t)N * 4);
+    L->parent = ws.take((size_t)N * 4);
+    L->size = ws.take((size_t)N * 4);
+    L->minkey = ws.take((size_t)N * 8);
+    L->ckey = ws.take((size_t)N * 4);
+    L->visited = ws.take((size_t)N * 4);
+    L->flag = ws.take((size_t)(N + 1) * 4);
+    L->scan = ws.take((size_t)(N + 1) * 4);
+    L->bsum = ws.take((size_t)(lrg_scan_blocks(N + 1) + 1) * 4);
+    L->stack = ws.take((size_t)L->stack_cap * 4);
+    L->scal = ws.take(64 * 4);
+    L->total = ws.total;
     return 0;
 }
 
@@ -96,14 +91,6 @@ struct BlArgs {
     int32_t *labels, *n_clusters;
     const double *nslack, *cslack; int32_t *cflags, *n_flagged;       // lrg_baseline_certify only (NULL otherwise)
 };
-
-// Bounds of room r (room_start was checked on the host: this only keeps a bad word from turning into an address)
-__device__ __forceinline__ bool bl_room(const BlArgs &a, int r, int *s, int *e) { return lrg_room_bounds(a.room_start, a.n, r, s, e); }
-
-// the room's hash segment: capacity the smallest power of two >= max(64, 2 n_room) (< 4 n_room + 64), at 4 start + 64 r
-__device__ __forceinline__ void bl_segment(const BlArgs &a, int r, int s, int e, uint64_t **keys, int32_t **vals, int *mask) {
-    lrg_room_segment(a.keys, a.vals, r, s, e, keys, vals, mask);
-}
 
 // normals[k].dot(normals[i]) as OpenBLAS's ddot computes it for n = 3: fma(a2, b2, fma(a1, b1, a0 * b0))
 __device__ __forceinline__ double bl_normal_dot(const double *nrm, int i, int k) {
@@ -206,11 +193,11 @@ __global__ __launch_bounds__(BL_THREADS) void bl_insert_kernel(BlArgs a) {
     if (i >= a.n) return;
     const int r = a.room_of[i];
     int s, e;
-    if (!bl_room(a, r, &s, &e)) return;
+    if (!lrg_room_bounds(a.room_start, a.n, r, &s, &e)) return;
     const uint64_t key = bl_key(a, i, 0, 0, 0);
     if (key == LRG_HASH_EMPTY) { atomicOr(&a.scal[0], BL_ST_WINDOW); a.room_of[i] = -1; return; }
     uint64_t *keys; int32_t *vals; int mask;
-    bl_segment(a, r, s, e, &keys, &vals, &mask);
+    lrg_room_segment(a.keys, a.vals, r, s, e, &keys, &vals, &mask);
     if (!lrg_room_insert(keys, vals, mask, key, i)) atomicOr(&a.scal[0], BL_ST_DUPLICATE);      // the room is not equalised
 }
 
@@ -220,9 +207,9 @@ __global__ __launch_bounds__(BL_THREADS) void bl_union_kernel(BlArgs a) {
     const int r = a.room_of[i];
     if (r < 0) return;
     int s, e;
-    if (!bl_room(a, r, &s, &e)) return;
+    if (!lrg_room_bounds(a.room_start, a.n, r, &s, &e)) return;
     uint64_t *keys; int32_t *vals; int mask;
-    bl_segment(a, r, s, e, &keys, &vals, &mask);
+    lrg_room_segment(a.keys, a.vals, r, s, e, &keys, &vals, &mask);
     const float *p = a.pts + (long)i * a.ld;
     const int vx = lrg_voxel_of(p[0], a.res), vy = lrg_voxel_of(p[1], a.res), vz = lrg_voxel_of(p[2], a.res);
     int o = 0;                                     // the offset's number, the centre left out
@@ -280,9 +267,9 @@ __global__ __launch_bounds__(BL_THREADS) void bl_certify_kernel(BlArgs a) {
     const int r = a.room_of[i];
     if (r < 0) return;
     int s, e;
-    if (!bl_room(a, r, &s, &e)) return;
+    if (!lrg_room_bounds(a.room_start, a.n, r, &s, &e)) return;
     uint64_t *keys; int32_t *vals; int mask;
-    bl_segment(a, r, s, e, &keys, &vals, &mask);
+    lrg_room_segment(a.keys, a.vals, r, s, e, &keys, &vals, &mask);
     const float *p = a.pts + (long)i * a.ld;
     const int vx = lrg_voxel_of(p[0], a.res), vy = lrg_voxel_of(p[1], a.res), vz = lrg_voxel_of(p[2], a.res);
     for (int dx = -1; dx <= 1; ++dx)
@@ -344,7 +331,7 @@ __global__ __launch_bounds__(BL_THREADS) void bl_count_kernel(BlArgs a) {
 // visited marked at pop time.  Returns the pop count len(C), or -1 when the stack would overflow its reservation.
 __device__ int bl_replay(const BlArgs &a, int s, int e, int r, int seed, int32_t *stk, int cap) {
     uint64_t *keys; int32_t *vals; int mask;
-    bl_segment(a, r, s, e, &keys, &vals, &mask);
+    lrg_room_segment(a.keys, a.vals, r, s, e, &keys, &vals, &mask);
     int top = 0, pops = 0;
     stk[top++] = seed;
     while (top > 0) {
@@ -391,63 +378,11 @@ __global__ __launch_bounds__(BL_THREADS) void bl_keep_kernel(BlArgs a) {
     if (keep) a.flag[s + key] = 1;
 }
 
-// ---- exclusive scan of flag[0 .. n] (n + 1 entries) into scan ----
-__device__ __forceinline__ int bl_block_exscan(int v, int *sh, int *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int inc = lrg_wave_incl_scan_i32(v);
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int k = 0; k < BL_THREADS / 64; ++k) {
-        if (k < w) base += sh[k];
-        tot += sh[k];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(BL_THREADS) void bl_scan_sums_kernel(const int32_t *x, long n, int32_t *bsum) {
-    __shared__ int sh[BL_THREADS / 64];
-    const long base = ((long)blockIdx.x * BL_THREADS + threadIdx.x) * BL_SCAN_ITEMS;
-    int s = 0;
-    for (int k = 0; k < BL_SCAN_ITEMS; ++k) s += base + k < n ? x[base + k] : 0;
-    int tot;
-    bl_block_exscan(s, sh, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(BL_THREADS) void bl_scan_top_kernel(int32_t *bsum, int nb) {
-    __shared__ int sh[BL_THREADS / 64];
-    int carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += BL_THREADS) {
-        const int i = b0 + threadIdx.x;
-        const int v = i < nb ? bsum[i] : 0;
-        int tot;
-        const int ex = bl_block_exscan(v, sh, &tot);
-        if (i < nb) bsum[i] = carry + ex;
-        carry += tot;
-    }
-}
-
-__global__ __launch_bounds__(BL_THREADS) void bl_scan_apply_kernel(const int32_t *x, long n, const int32_t *bsum, int32_t *out) {
-    __shared__ int sh[BL_THREADS / 64];
-    const long base = ((long)blockIdx.x * BL_THREADS + threadIdx.x) * BL_SCAN_ITEMS;
-    int v[BL_SCAN_ITEMS], s = 0;
-    for (int k = 0; k < BL_SCAN_ITEMS; ++k) { v[k] = base + k < n ? x[base + k] : 0; s += v[k]; }
-    int tot;
-    int run = bsum[blockIdx.x] + bl_block_exscan(s, sh, &tot);
-    for (int k = 0; k < BL_SCAN_ITEMS; ++k) {
-        if (base + k < n) out[base + k] = run;
-        run += v[k];
-    }
-}
-
 __global__ __launch_bounds__(BL_THREADS) void bl_label_kernel(BlArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < a.n_rooms) {
         int s, e;
-        a.n_clusters[i] = bl_room(a, i, &s, &e) ? a.scan[e] - a.scan[s] : 0;
+        a.n_clusters[i] = lrg_room_bounds(a.room_start, a.n, i, &s, &e) ? a.scan[e] - a.scan[s] : 0;
     }
     if (i >= a.n) return;
     const int r = a.room_of[i];
@@ -547,10 +482,7 @@ static int bl_segment_impl(const float *pts, int ld, const int32_t *room_start, 
         hipLaunchKernelGGL(bl_count_kernel, dim3(gn), dim3(BL_THREADS), 0, st, a);
         hipLaunchKernelGGL(bl_keep_kernel, dim3(gn), dim3(BL_THREADS), 0, st, a);
     }
-    const long nf = (long)n_points + 1;
-    hipLaunchKernelGGL(bl_scan_sums_kernel, dim3(L.nb), dim3(BL_THREADS), 0, st, a.flag, nf, a.bsum);
-    hipLaunchKernelGGL(bl_scan_top_kernel, dim3(1), dim3(BL_THREADS), 0, st, a.bsum, L.nb);
-    hipLaunchKernelGGL(bl_scan_apply_kernel, dim3(L.nb), dim3(BL_THREADS), 0, st, a.flag, nf, a.bsum, a.scan);
+    if ((rc = lrg_exscan_i32(a.flag, (long)n_points + 1, a.bsum, a.scan, st))) return rc;      // flag[0 .. n] (n + 1 entries) into scan
     hipLaunchKernelGGL(bl_label_kernel, dim3(gn), dim3(BL_THREADS), 0, st, a);
     LRG_LAUNCH_CHECK();
     return 0;

@@ -21,6 +21,18 @@
 
 static inline size_t lrg_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Carves a workspace into regions: take() returns the next region's offset, every region starts on a multiple of 256 bytes
+struct LrgArena {
+    size_t total = 0;
+    size_t take(size_t bytes) { const size_t at = total; total = lrg_align_up(total + bytes, 256); return at; }
+};
+
+// Exclusive scan of x[0 .. n) into out (lrg_scan.hip; three launches, blocks of LRG_SCAN_BLOCK elements).  bsum: lrg_scan_blocks(n) + 1
+// words of scratch, the last of which receives the total.  n == 0 launches nothing.  Exported for tests, not part of include/lrg_hip.h.
+#define LRG_SCAN_BLOCK 2048
+static inline long lrg_scan_blocks(long n) { return (n + LRG_SCAN_BLOCK - 1) / LRG_SCAN_BLOCK; }
+extern "C" int lrg_exscan_i32(const int32_t *x, long n, int32_t *bsum, int32_t *out, void *stream);
+
 // Switches from the environment (A/B runs and test hooks): the variable's value as atoi / atof reads it, `dflt` while it is not set.
 // LRG_ENV_UNSET as `dflt`: a switch whose default is decided by the caller.
 #define LRG_ENV_UNSET INT_MIN
@@ -34,6 +46,15 @@ static inline int lrg_current_device() {
     int d = 0;
     if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= LRG_MAX_DEVICES) d = 0;
     return d;
+}
+
+// the last r in [lo, hi] with start[r] <= i (start ascending: the room of point i, the chunk of term i, ...)
+__device__ __forceinline__ int lrg_last_start(const int32_t *start, int lo, int hi, int i) {
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (start[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
 }
 
 __device__ __forceinline__ int lrg_lane() { return threadIdx.x & 63; }

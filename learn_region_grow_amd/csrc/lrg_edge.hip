@@ -69,33 +69,32 @@ struct LrgEdgeLayout {
 static int ed_layout(int N, int R, int mcs, int cap, LrgEdgeLayout *L) {
     if (N < 0 || R < 0 || N > (1 << 26) || R > (1 << 20)) return LRG_EINVAL - 90;
     if (cap < 1 || cap > ED_MAX_SEARCH_CAP) return LRG_EINVAL - 91;
-    L->hslots = 4L * N + 64L * R;
+    L->hslots = lrg_room_hash_slots(N, R);
     L->waves = (N + 3) / 4 < ED_MAX_SEARCH_WAVES ? ((N + 3) / 4 + 3) / 4 * 4 : ED_MAX_SEARCH_WAVES;
     if (L->waves < 4) L->waves = 4;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = lrg_align_up(o + bytes, 256); return at; };
-    L->scal = take(64 * 4);
-    L->rooms = take((size_t)(R + 1) * 4);
-    L->keys = take((size_t)L->hslots * 8);
-    L->vals = take((size_t)L->hslots * 4);
-    L->room_of = take((size_t)N * 4);
-    L->nbr = take((size_t)N * 26 * 4);
-    L->nmin = take((size_t)N * 6 * 4);
-    L->nmax = take((size_t)N * 6 * 4);
-    L->elist = take((size_t)N * ED_SLOTS * 4);
-    L->logits_end = o;
-    L->pmax = take((size_t)N * 8);
-    L->keepw = take((size_t)N * 4);
-    L->clab = take((size_t)N * 4);
-    L->parent = take((size_t)N * 4);
-    L->live = take((size_t)N * 4);
-    L->nxt = take((size_t)N * 4);
-    L->todo = take((size_t)N * 4);
-    L->slab = take((size_t)L->waves * 3 * (size_t)cap * 4);
+    LrgArena ws;
+    L->scal = ws.take(64 * 4);
+    L->rooms = ws.take((size_t)(R + 1) * 4);
+    L->keys = ws.take((size_t)L->hslots * 8);
+    L->vals = ws.take((size_t)L->hslots * 4);
+    L->room_of = ws.take((size_t)N * 4);
+    L->nbr = ws.take((size_t)N * 26 * 4);
+    L->nmin = ws.take((size_t)N * 6 * 4);
+    L->nmax = ws.take((size_t)N * 6 * 4);
+    L->elist = ws.take((size_t)N * ED_SLOTS * 4);
+    L->logits_end = ws.total;
+    L->pmax = ws.take((size_t)N * 8);
+    L->keepw = ws.take((size_t)N * 4);
+    L->clab = ws.take((size_t)N * 4);
+    L->parent = ws.take((size_t)N * 4);
+    L->live = ws.take((size_t)N * 4);
+    L->nxt = ws.take((size_t)N * 4);
+    L->todo = ws.take((size_t)N * 4);
+    L->slab = ws.take((size_t)L->waves * 3 * (size_t)cap * 4);
     L->base_bytes = lrg_baseline_workspace_bytes(N, R, mcs);
     if (!L->base_bytes) return LRG_EINVAL - 92;
-    L->base = take(L->base_bytes);
-    L->total = o;
+    L->base = ws.take(L->base_bytes);
+    L->total = ws.total;
     return 0;
 }
 
@@ -113,8 +112,6 @@ struct EdArgs {
     int cap;
 };
 
-__device__ __forceinline__ bool ed_room(const EdArgs &a, int r, int *s, int *e) { return lrg_room_bounds(a.room_start, a.n, r, s, e); }
-
 __global__ __launch_bounds__(ED_THREADS) void ed_init_kernel(EdArgs a) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < a.hslots) { a.keys[t] = LRG_HASH_EMPTY; a.vals[t] = -1; }
@@ -127,7 +124,7 @@ __global__ __launch_bounds__(ED_THREADS) void ed_insert_kernel(EdArgs a) {
     if (i >= a.n) return;
     const int r = a.room_of[i];
     int s, e;
-    if (!ed_room(a, r, &s, &e)) { a.room_of[i] = -1; return; }
+    if (!lrg_room_bounds(a.room_start, a.n, r, &s, &e)) { a.room_of[i] = -1; return; }
     const float *p = a.pts + (long)i * a.ld;
     const uint64_t key = lrg_pack_voxel(lrg_voxel_of(p[0], a.res), lrg_voxel_of(p[1], a.res), lrg_voxel_of(p[2], a.res));
     if (key == LRG_HASH_EMPTY) { atomicOr(&a.scal[ED_STATUS], ED_ST_WINDOW); a.room_of[i] = -1; return; }
@@ -149,7 +146,7 @@ __global__ __launch_bounds__(ED_THREADS) void ed_neighbour_kernel(EdArgs a) {
         const float *p = a.pts + (long)i * a.ld;
         float mn[6], mx[6];
         for (int c = 0; c < 6; ++c) mn[c] = mx[c] = p[c];
-        const bool ok = r >= 0 && ed_room(a, r, &s, &e);
+        const bool ok = r >= 0 && lrg_room_bounds(a.room_start, a.n, r, &s, &e);
         uint64_t *keys = nullptr; int32_t *vals = nullptr; int mask = 0;
         if (ok) lrg_room_segment(a.keys, a.vals, r, s, e, &keys, &vals, &mask);
         const int vx = lrg_voxel_of(p[0], a.res), vy = lrg_voxel_of(p[1], a.res), vz = lrg_voxel_of(p[2], a.res);

@@ -3,7 +3,7 @@
 //
 // A batch of rooms goes through a fixed sequence of launches, one point per lane in each:
 //   init     hash slots empty, status cleared, the room of every point (binary search in room_start)
-//   insert   voxel key -> the room's own linear-probe segment, as bl_insert_kernel of lrg_baselines.hip (same capacity rule)
+//   insert   voxel key -> the room's own linear-probe segment (lrg_room_hash.h); a key met twice is an error
 //   pairs    125 window lookups; every j with d2 <= r2 counts in k; every pair j != i goes through computePairFeatures and
 //            increments three of the lane's 33 counters.  The counters live in LDS, one row of 33 words per lane: lane l's word b
 //            is on bank (l + b) % 32, so the 32 lanes of a half-wave never meet on a bank whatever their b, and a row has one
@@ -14,6 +14,7 @@
 // Nothing is accumulated by float atomics and the order of every sum is the window's, so the output is a function of the room
 // alone: not of the batch, the launch or the run.
 #include "lrg_common.h"
+#include "lrg_room_hash.h"
 
 #define FP_THREADS 256
 #define FP_BINS 33
@@ -29,17 +30,16 @@ struct LrgFpfhLayout {
 static int fp_layout(int N, int R, int flags, LrgFpfhLayout *L) {
     if (N < 0 || R < 0 || N > (1 << 26) || R > (1 << 20)) return LRG_EINVAL - 90;
     if (flags & ~LRG_FPFH_LISTS) return LRG_EINVAL - 90;
-    L->hslots = 4L * N + 64L * R;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = lrg_align_up(o + bytes, 256); return at; };
-    L->keys = take((size_t)L->hslots * 8);
-    L->vals = take((size_t)L->hslots * 4);
-    L->rooms = take((size_t)(R + 1) * 4);
-    L->room_of = take((size_t)N * 4);
-    L->bytes = take((size_t)N * FP_BYTES);
-    L->lists = take((flags & LRG_FPFH_LISTS) ? (size_t)N * FP_LIST_CAP * 4 : 0);
-    L->scal = take(64 * 4);
-    L->total = o;
+    L->hslots = lrg_room_hash_slots(N, R);
+    LrgArena ws;
+    L->keys = ws.take((size_t)L->hslots * 8);
+    L->vals = ws.take((size_t)L->hslots * 4);
+    L->rooms = ws.take((size_t)(R + 1) * 4);
+    L->room_of = ws.take((size_t)N * 4);
+    L->bytes = ws.take((size_t)N * FP_BYTES);
+    L->lists = ws.take((flags & LRG_FPFH_LISTS) ? (size_t)N * FP_LIST_CAP * 4 : 0);
+    L->scal = ws.take(64 * 4);
+    L->total = ws.total;
     return 0;
 }
 
@@ -53,33 +53,11 @@ struct FpArgs {
     int32_t *counts, *k; float *fpfh;
 };
 
-__device__ __forceinline__ bool fp_room(const FpArgs &a, int r, int *s, int *e) {
-    const int s0 = a.room_start[r], e0 = a.room_start[r + 1];
-    if (s0 < 0 || e0 < s0 || e0 > a.n) return false;
-    *s = s0; *e = e0;
-    return true;
-}
-
-// the room's hash segment: capacity the smallest power of two >= max(64, 2 n_room) (< 4 n_room + 64), at 4 start + 64 r
-__device__ __forceinline__ void fp_segment(const FpArgs &a, int r, int s, int e, uint64_t **keys, int32_t **vals, int *mask) {
-    int cap = 64;
-    while (cap < 2 * (e - s)) cap <<= 1;
-    const long off = 4L * s + 64L * r;
-    *keys = a.keys + off; *vals = a.vals + off; *mask = cap - 1;
-}
-
 __global__ __launch_bounds__(FP_THREADS) void fp_init_kernel(FpArgs a) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < a.hslots) { a.keys[t] = LRG_HASH_EMPTY; a.vals[t] = -1; }
     if (t < 64) a.scal[t] = 0;
-    if (t >= a.n) return;
-    const int i = (int)t;
-    int lo = 0, hi = a.n_rooms - 1;                // the last r with room_start[r] <= i
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.room_start[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    a.room_of[i] = lo;
+    if (t < a.n) a.room_of[t] = lrg_room_of(a.room_start, a.n_rooms, (int)t);
 }
 
 __global__ __launch_bounds__(FP_THREADS) void fp_insert_kernel(FpArgs a) {
@@ -87,20 +65,13 @@ __global__ __launch_bounds__(FP_THREADS) void fp_insert_kernel(FpArgs a) {
     if (i >= a.n) return;
     const int r = a.room_of[i];
     int s, e;
-    if (!fp_room(a, r, &s, &e)) { a.room_of[i] = -1; return; }
+    if (!lrg_room_bounds(a.room_start, a.n, r, &s, &e)) { a.room_of[i] = -1; return; }
     const float *p = a.pts + (long)i * a.ld;
     const uint64_t key = lrg_pack_voxel(lrg_voxel_of(p[0], a.res), lrg_voxel_of(p[1], a.res), lrg_voxel_of(p[2], a.res));
     if (key == LRG_HASH_EMPTY) { atomicOr(&a.scal[0], FP_ST_WINDOW); a.room_of[i] = -1; return; }
     uint64_t *keys; int32_t *vals; int mask;
-    fp_segment(a, r, s, e, &keys, &vals, &mask);
-    unsigned h = (unsigned)lrg_fmix64(key) & (unsigned)mask;
-    for (int probe = 0; probe <= mask; ++probe) {
-        const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&keys[h]), (unsigned long long)LRG_HASH_EMPTY,
-                                                  (unsigned long long)key);
-        if (prev == LRG_HASH_EMPTY) { vals[h] = i; return; }
-        if (prev == key) { atomicOr(&a.scal[0], FP_ST_DUPLICATE); return; }      // the room is not equalised
-        h = (h + 1) & (unsigned)mask;
-    }
+    lrg_room_segment(a.keys, a.vals, r, s, e, &keys, &vals, &mask);
+    if (!lrg_room_insert(keys, vals, mask, key, i)) atomicOr(&a.scal[0], FP_ST_DUPLICATE);      // the room is not equalised
 }
 
 // floor(11 x) clamped to [0, 10]; a NaN goes to bin 0 (fmaxf returns its other argument), so the result is always a valid index
@@ -160,9 +131,9 @@ __global__ __launch_bounds__(FP_THREADS) void fp_pairs_kernel(FpArgs a) {
     int k = 0, m = 0;
     const int r = a.room_of[i];
     int s, e;
-    if (r >= 0 && fp_room(a, r, &s, &e)) {
+    if (r >= 0 && lrg_room_bounds(a.room_start, a.n, r, &s, &e)) {
         uint64_t *keys; int32_t *vals; int mask;
-        fp_segment(a, r, s, e, &keys, &vals, &mask);
+        lrg_room_segment(a.keys, a.vals, r, s, e, &keys, &vals, &mask);
         const float *p = a.pts + (long)i * a.ld;
         const int vx = lrg_voxel_of(p[0], a.res), vy = lrg_voxel_of(p[1], a.res), vz = lrg_voxel_of(p[2], a.res);
         for (int ox = -2; ox <= 2; ++ox)
@@ -218,7 +189,7 @@ __global__ __launch_bounds__(FP_THREADS) void fp_gather_kernel(FpArgs a) {
     for (int b = 0; b < FP_BINS; ++b) acc[b] = 0.0;
     const int r = a.room_of[i];
     int s, e;
-    if (r >= 0 && fp_room(a, r, &s, &e)) {
+    if (r >= 0 && lrg_room_bounds(a.room_start, a.n, r, &s, &e)) {
         const int m = a.k[i] - 1;                                          // the pairs pass counted i itself
         if (a.lists && m <= FP_LIST_CAP) {
             for (int q = 0; q < m; ++q) {
@@ -229,7 +200,7 @@ __global__ __launch_bounds__(FP_THREADS) void fp_gather_kernel(FpArgs a) {
             }
         } else if (m > 0) {
             uint64_t *keys; int32_t *vals; int mask;
-            fp_segment(a, r, s, e, &keys, &vals, &mask);
+            lrg_room_segment(a.keys, a.vals, r, s, e, &keys, &vals, &mask);
             const float *p = a.pts + (long)i * a.ld;
             const int vx = lrg_voxel_of(p[0], a.res), vy = lrg_voxel_of(p[1], a.res), vz = lrg_voxel_of(p[2], a.res);
             for (int ox = -2; ox <= 2; ++ox)

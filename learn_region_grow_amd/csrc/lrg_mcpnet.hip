@@ -22,9 +22,9 @@
 //   head     concat(z, r, g, b, pooled) -> 200 (relu) -> 10 in fp32 FMA chains, then x * (1 / sqrt(max(sum x^2, 1e-12)))
 #include "lrg_common.h"
 #include "lrg_rng.h"
+#include "lrg_room_hash.h"
 
 #define MCP_THREADS 256
-#define MCP_SCAN_ITEMS 8
 #include "lrg_mcp_layout.h"
 #define MCP_PTS 16                   // points per wavefront: 800 rows = 25 tiles of 32
 
@@ -34,28 +34,24 @@ enum { MCP_ST_WINDOW = 1, MCP_ST_POSITION = 2 };
 struct LrgMcpLayout {
     size_t keys, cnt, off, fill, members, cell, room_of, rooms, rids, bsum, scal, total;
     long hslots;
-    int nb;
 };
 
 static int mcp_layout(int N, int R, LrgMcpLayout *L) {
     if (N < 0 || R < 1 || N > (1 << 26) || R > (1 << 20)) return LRG_EINVAL - 80;
-    L->hslots = 4L * N + 64L * R;
-    const long per_block = MCP_THREADS * MCP_SCAN_ITEMS;
-    L->nb = (int)((L->hslots + 1 + per_block - 1) / per_block);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = lrg_align_up(o + bytes, 256); return at; };
-    L->keys = take((size_t)L->hslots * 8);
-    L->cnt = take((size_t)(L->hslots + 1) * 4);
-    L->off = take((size_t)(L->hslots + 1) * 4);
-    L->fill = take((size_t)L->hslots * 4);
-    L->members = take((size_t)N * 4 + 4);
-    L->cell = take((size_t)N * 4 + 4);
-    L->room_of = take((size_t)N * 4 + 4);
-    L->rooms = take((size_t)(R + 1) * 4);
-    L->rids = take((size_t)R * 4);
-    L->bsum = take((size_t)(L->nb + 1) * 4);
-    L->scal = take(64 * 4);
-    L->total = o;
+    L->hslots = lrg_room_hash_slots(N, R);
+    LrgArena ws;
+    L->keys = ws.take((size_t)L->hslots * 8);
+    L->cnt = ws.take((size_t)(L->hslots + 1) * 4);
+    L->off = ws.take((size_t)(L->hslots + 1) * 4);
+    L->fill = ws.take((size_t)L->hslots * 4);
+    L->members = ws.take((size_t)N * 4 + 4);
+    L->cell = ws.take((size_t)N * 4 + 4);
+    L->room_of = ws.take((size_t)N * 4 + 4);
+    L->rooms = ws.take((size_t)(R + 1) * 4);
+    L->rids = ws.take((size_t)R * 4);
+    L->bsum = ws.take((size_t)(lrg_scan_blocks(L->hslots + 1) + 1) * 4);
+    L->scal = ws.take(64 * 4);
+    L->total = ws.total;
     return 0;
 }
 
@@ -67,34 +63,6 @@ struct McpArgs {
     int32_t *counts;
     const int32_t *positions; uint32_t seed; int32_t *nbr;
 };
-
-__device__ __forceinline__ bool mcp_room(const McpArgs &a, int r, int *s, int *e) {
-    const int s0 = a.room_start[r], e0 = a.room_start[r + 1];
-    if (s0 < 0 || e0 < s0 || e0 > a.n) return false;
-    *s = s0; *e = e0;
-    return true;
-}
-
-// the room's hash segment: capacity the smallest power of two >= max(64, 2 n_room) (< 4 n_room + 64), at 4 start + 64 r
-__device__ __forceinline__ void mcp_segment(const McpArgs &a, int r, int s, int e, long *base, int *mask) {
-    int cap = 64;
-    while (cap < 2 * (e - s)) cap <<= 1;
-    *base = 4L * s + 64L * r;
-    *mask = cap - 1;
-}
-
-// slot of `key` in the segment at `base`, -1 when absent
-__device__ __forceinline__ int mcp_find(const McpArgs &a, long base, int mask, uint64_t key) {
-    if (key == LRG_HASH_EMPTY) return -1;
-    unsigned h = (unsigned)lrg_fmix64(key) & (unsigned)mask;
-    for (int probe = 0; probe <= mask; ++probe) {
-        const uint64_t k = a.keys[base + h];
-        if (k == key) return (int)(base + h);
-        if (k == LRG_HASH_EMPTY) return -1;
-        h = (h + 1) & (unsigned)mask;
-    }
-    return -1;
-}
 
 // coarse cell of point i: round(x / 0.3) per axis, float32 division by float32(0.3), half to even (test_mcpnet.py:86, :98)
 __device__ __forceinline__ void mcp_cell_of(const McpArgs &a, int i, int *cx, int *cy, int *cz) {
@@ -108,14 +76,8 @@ __global__ __launch_bounds__(MCP_THREADS) void mcp_init_kernel(McpArgs a) {
     if (t == a.hslots) a.cnt[t] = 0;
     if (t < 64) a.scal[t] = 0;
     if (t >= a.n) return;
-    const int i = (int)t;
-    int lo = 0, hi = a.n_rooms - 1;                // the last r with room_start[r] <= i
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.room_start[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    a.room_of[i] = lo;
-    a.cell[i] = -1;
+    a.room_of[t] = lrg_room_of(a.room_start, a.n_rooms, (int)t);
+    a.cell[t] = -1;
 }
 
 __global__ __launch_bounds__(MCP_THREADS) void mcp_insert_kernel(McpArgs a) {
@@ -123,76 +85,17 @@ __global__ __launch_bounds__(MCP_THREADS) void mcp_insert_kernel(McpArgs a) {
     if (i >= a.n) return;
     const int r = a.room_of[i];
     int s, e;
-    if (!mcp_room(a, r, &s, &e)) return;
+    if (!lrg_room_bounds(a.room_start, a.n, r, &s, &e)) return;
     int cx, cy, cz;
     mcp_cell_of(a, i, &cx, &cy, &cz);
     const uint64_t key = lrg_pack_voxel(cx, cy, cz);
     if (key == LRG_HASH_EMPTY) { atomicOr(&a.scal[0], MCP_ST_WINDOW); return; }
     long base; int mask;
-    mcp_segment(a, r, s, e, &base, &mask);
-    unsigned h = (unsigned)lrg_fmix64(key) & (unsigned)mask;
-    for (int probe = 0; probe <= mask; ++probe) {
-        const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&a.keys[base + h]),
-                                                  (unsigned long long)LRG_HASH_EMPTY, (unsigned long long)key);
-        if (prev == LRG_HASH_EMPTY || prev == key) {
-            a.cell[i] = (int)(base + h);
-            atomicAdd(&a.cnt[base + h], 1);
-            return;
-        }
-        h = (h + 1) & (unsigned)mask;
-    }
-}
-
-// ---- exclusive scan of cnt[0 .. hslots] into off ----
-__device__ __forceinline__ int mcp_block_exscan(int v, int *sh, int *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int inc = lrg_wave_incl_scan_i32(v);
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int k = 0; k < MCP_THREADS / 64; ++k) {
-        if (k < w) base += sh[k];
-        tot += sh[k];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(MCP_THREADS) void mcp_scan_sums_kernel(const int32_t *x, long n, int32_t *bsum) {
-    __shared__ int sh[MCP_THREADS / 64];
-    const long base = ((long)blockIdx.x * MCP_THREADS + threadIdx.x) * MCP_SCAN_ITEMS;
-    int s = 0;
-    for (int k = 0; k < MCP_SCAN_ITEMS; ++k) s += base + k < n ? x[base + k] : 0;
-    int tot;
-    mcp_block_exscan(s, sh, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(MCP_THREADS) void mcp_scan_top_kernel(int32_t *bsum, int nb) {
-    __shared__ int sh[MCP_THREADS / 64];
-    int carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += MCP_THREADS) {
-        const int i = b0 + threadIdx.x;
-        const int v = i < nb ? bsum[i] : 0;
-        int tot;
-        const int ex = mcp_block_exscan(v, sh, &tot);
-        if (i < nb) bsum[i] = carry + ex;
-        carry += tot;
-    }
-}
-
-__global__ __launch_bounds__(MCP_THREADS) void mcp_scan_apply_kernel(const int32_t *x, long n, const int32_t *bsum, int32_t *out) {
-    __shared__ int sh[MCP_THREADS / 64];
-    const long base = ((long)blockIdx.x * MCP_THREADS + threadIdx.x) * MCP_SCAN_ITEMS;
-    int v[MCP_SCAN_ITEMS], s = 0;
-    for (int k = 0; k < MCP_SCAN_ITEMS; ++k) { v[k] = base + k < n ? x[base + k] : 0; s += v[k]; }
-    int tot;
-    int run = bsum[blockIdx.x] + mcp_block_exscan(s, sh, &tot);
-    for (int k = 0; k < MCP_SCAN_ITEMS; ++k) {
-        if (base + k < n) out[base + k] = run;
-        run += v[k];
-    }
+    lrg_room_segment(r, s, e, &base, &mask);
+    const int h = lrg_room_claim(a.keys + base, mask, key);
+    if (h < 0) return;
+    a.cell[i] = (int)(base + h);
+    atomicAdd(&a.cnt[base + h], 1);
 }
 
 __global__ __launch_bounds__(MCP_THREADS) void mcp_fill_kernel(McpArgs a) {
@@ -223,9 +126,9 @@ __global__ __launch_bounds__(MCP_THREADS) void mcp_sort_kernel(McpArgs a) {
 __device__ __forceinline__ int mcp_cells(const McpArgs &a, int i, int (&start)[27], int (&count)[27]) {
     const int r = a.room_of[i];
     int s, e;
-    if (a.cell[i] < 0 || !mcp_room(a, r, &s, &e)) return -1;
+    if (a.cell[i] < 0 || !lrg_room_bounds(a.room_start, a.n, r, &s, &e)) return -1;
     long base; int mask;
-    mcp_segment(a, r, s, e, &base, &mask);
+    lrg_room_segment(r, s, e, &base, &mask);
     int cx, cy, cz;
     mcp_cell_of(a, i, &cx, &cy, &cz);
     int total = 0, o = 0;
@@ -235,9 +138,9 @@ __device__ __forceinline__ int mcp_cells(const McpArgs &a, int i, int (&start)[2
         for (int dy = -1; dy <= 1; ++dy)
 #pragma unroll
             for (int dz = -1; dz <= 1; ++dz, ++o) {
-                const int h = mcp_find(a, base, mask, lrg_pack_voxel(cx + dx, cy + dy, cz + dz));
-                start[o] = h >= 0 ? a.off[h] : 0;
-                count[o] = h >= 0 ? a.cnt[h] : 0;
+                const int h = lrg_room_find(a.keys + base, mask, lrg_pack_voxel(cx + dx, cy + dy, cz + dz));
+                start[o] = h >= 0 ? a.off[base + h] : 0;
+                count[o] = h >= 0 ? a.cnt[base + h] : 0;
                 total += count[o];
             }
     return total;
@@ -497,13 +400,10 @@ int lrg_mcp_candidates(const float *pts, int ld, const int32_t *room_start, int 
     const int gi = (int)((init_n + MCP_THREADS - 1) / MCP_THREADS);
     const int gn = (int)(((long)a.n + MCP_THREADS - 1) / MCP_THREADS);
     const int gh = (int)((L.hslots + MCP_THREADS - 1) / MCP_THREADS);
-    const long ns = L.hslots + 1;
     hipLaunchKernelGGL(mcp_init_kernel, dim3(gi), dim3(MCP_THREADS), 0, st, a);
     if (a.n > 0) hipLaunchKernelGGL(mcp_insert_kernel, dim3(gn), dim3(MCP_THREADS), 0, st, a);
-    hipLaunchKernelGGL(mcp_scan_sums_kernel, dim3(L.nb), dim3(MCP_THREADS), 0, st, a.cnt, ns, reinterpret_cast<int32_t *>(static_cast<char *>(ws) + L.bsum));
-    hipLaunchKernelGGL(mcp_scan_top_kernel, dim3(1), dim3(MCP_THREADS), 0, st, reinterpret_cast<int32_t *>(static_cast<char *>(ws) + L.bsum), L.nb);
-    hipLaunchKernelGGL(mcp_scan_apply_kernel, dim3(L.nb), dim3(MCP_THREADS), 0, st, a.cnt, ns,
-                       reinterpret_cast<int32_t *>(static_cast<char *>(ws) + L.bsum), a.off);
+    // cnt[0 .. hslots] into off: the start of each cell's member list
+    if ((rc = lrg_exscan_i32(a.cnt, L.hslots + 1, reinterpret_cast<int32_t *>(static_cast<char *>(ws) + L.bsum), a.off, st))) return rc;
     if (a.n > 0) {
         hipLaunchKernelGGL(mcp_fill_kernel, dim3(gn), dim3(MCP_THREADS), 0, st, a);
         hipLaunchKernelGGL(mcp_sort_kernel, dim3(gh), dim3(MCP_THREADS), 0, st, a);

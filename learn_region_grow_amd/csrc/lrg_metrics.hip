@@ -61,33 +61,23 @@ static int mt_layout(const int32_t *room_start, const int32_t *gt_start, const i
         if (nr > max_n) max_n = (int)nr;
     }
     L->n = n; L->g = g; L->cols = cols; L->cells = cells; L->chunks = chunks; L->max_n = max_n;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = lrg_align_up(o + bytes, 256); return at; };
-    L->room_start = take((size_t)(n_rooms + 1) * 4);
-    L->gt_start = take((size_t)(n_rooms + 1) * 4);
-    L->ncl = take((size_t)n_rooms * 4);
-    L->col_start = take((size_t)(n_rooms + 1) * 4);
-    L->cell_start = take((size_t)(n_rooms + 1) * 4);
-    L->chunk_base = take((size_t)(n_rooms + 1) * 4);
-    L->status = take((size_t)n_rooms * 4);
-    L->cont = take((size_t)cells * 4);
-    L->cchunk = take((size_t)cells * 4);
-    L->a = take((size_t)g * 4);
-    L->b = take((size_t)cols * 4);
-    L->map = take((size_t)cols * 4);
-    L->T = take((size_t)(max_n + 1) * 8);
-    L->partial = take((size_t)chunks * 8);
-    L->total = o;
+    LrgArena ws;
+    L->room_start = ws.take((size_t)(n_rooms + 1) * 4);
+    L->gt_start = ws.take((size_t)(n_rooms + 1) * 4);
+    L->ncl = ws.take((size_t)n_rooms * 4);
+    L->col_start = ws.take((size_t)(n_rooms + 1) * 4);
+    L->cell_start = ws.take((size_t)(n_rooms + 1) * 4);
+    L->chunk_base = ws.take((size_t)(n_rooms + 1) * 4);
+    L->status = ws.take((size_t)n_rooms * 4);
+    L->cont = ws.take((size_t)cells * 4);
+    L->cchunk = ws.take((size_t)cells * 4);
+    L->a = ws.take((size_t)g * 4);
+    L->b = ws.take((size_t)cols * 4);
+    L->map = ws.take((size_t)cols * 4);
+    L->T = ws.take((size_t)(max_n + 1) * 8);
+    L->partial = ws.take((size_t)chunks * 8);
+    L->total = ws.total;
     return 0;
-}
-
-// the last r in [lo, hi] with start[r] <= i
-__device__ __forceinline__ int mt_find(const int32_t *start, int lo, int hi, int i) {
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (start[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
 }
 
 // fixed-order sum of one value per thread (MT_THREADS threads); the result is returned to every thread
@@ -153,7 +143,7 @@ __global__ __launch_bounds__(MT_THREADS) void mt_cont_kernel(MtArgs a) {
     const long first = (long)blockIdx.x * MT_TILE;
     if (first >= a.n) return;
     const int lo = (int)first, hi = (int)(first + MT_TILE < (long)a.n ? first + MT_TILE : (long)a.n);
-    const int r0 = mt_find(a.room_start, 0, a.n_rooms - 1, lo), r1 = mt_find(a.room_start, r0, a.n_rooms - 1, hi - 1);
+    const int r0 = lrg_last_start(a.room_start, 0, a.n_rooms - 1, lo), r1 = lrg_last_start(a.room_start, r0, a.n_rooms - 1, hi - 1);
     const int g0 = a.gt_start[r0 + 1] - a.gt_start[r0], w0 = a.ncl[r0] + 1;
     const bool lds = r0 == r1 && (long)g0 * w0 <= MT_LDS_CELLS;
     if (lds) {
@@ -173,7 +163,7 @@ __global__ __launch_bounds__(MT_THREADS) void mt_cont_kernel(MtArgs a) {
         }
     } else {
         for (int i = lo + (int)threadIdx.x; i < hi; i += MT_THREADS) {
-            const int r = mt_find(a.room_start, r0, r1, i);
+            const int r = lrg_last_start(a.room_start, r0, r1, i);
             const int G = a.gt_start[r + 1] - a.gt_start[r], W = a.ncl[r] + 1;
             const int lab = a.labels[i], g = a.gt_row[i];
             if ((unsigned)lab >= (unsigned)W || (unsigned)g >= (unsigned)G) { atomicOr(&a.status[r], 1); continue; }
@@ -188,14 +178,14 @@ __global__ __launch_bounds__(MT_THREADS) void mt_sums_kernel(MtArgs a) {
     const long first = (long)blockIdx.x * MT_THREADS;
     if (first >= a.cells) return;
     const long last = first + MT_THREADS - 1 < a.cells - 1 ? first + MT_THREADS - 1 : a.cells - 1;
-    const int r0 = mt_find(a.cell_start, 0, a.n_rooms - 1, (int)first), r1 = mt_find(a.cell_start, r0, a.n_rooms - 1, (int)last);
+    const int r0 = lrg_last_start(a.cell_start, 0, a.n_rooms - 1, (int)first), r1 = lrg_last_start(a.cell_start, r0, a.n_rooms - 1, (int)last);
     const long c = first + threadIdx.x;
     long long sq = 0;
     int r = r0;
     if (c < a.cells) {
         const int v = a.cont[c];
         if (v) {
-            r = mt_find(a.cell_start, r0, r1, (int)c);
+            r = lrg_last_start(a.cell_start, r0, r1, (int)c);
             const int W = a.ncl[r] + 1, rel = (int)(c - a.cell_start[r]);
             atomicAdd(&a.a[a.gt_start[r] + rel / W], v);
             atomicAdd(&a.b[a.col_start[r] + rel % W], v);
@@ -295,14 +285,14 @@ __global__ __launch_bounds__(MT_THREADS) void mt_room_kernel(MtArgs a) {
 __global__ __launch_bounds__(MT_THREADS) void mt_emi_kernel(MtArgs a) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= a.chunks) return;
-    const int r = mt_find(a.chunk_base, 0, a.n_rooms - 1, (int)t);
+    const int r = lrg_last_start(a.chunk_base, 0, a.n_rooms - 1, (int)t);
     const int q = (int)(t - a.chunk_base[r]);
     const long long *is = a.isums + (long)r * MT_ISUMS;
     const long room_bound = (long)a.chunk_base[r + 1] - a.chunk_base[r];
     if (q >= is[7] || q >= room_bound) return;
     const int G = a.gt_start[r + 1] - a.gt_start[r], W = a.ncl[r] + 1, N = (int)is[3];
     const int32_t *cchunk = a.cchunk + a.cell_start[r];
-    const int c = mt_find(cchunk, 0, G * W - 1, q);
+    const int c = lrg_last_start(cchunk, 0, G * W - 1, q);
     const int ai = a.a[a.gt_start[r] + c / W], bj = a.b[a.col_start[r] + c % W];
     int start;
     const int len = mt_pair_len(ai, bj, N, &start);
@@ -393,7 +383,7 @@ __global__ __launch_bounds__(MT_THREADS) void mt_relabel_kernel(MtArgs a) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= a.n) return;
     const int i = (int)t;
-    const int r = mt_find(a.room_start, 0, a.n_rooms - 1, i);
+    const int r = lrg_last_start(a.room_start, 0, a.n_rooms - 1, i);
     const int lab = a.labels[i];
     a.label2[i] = (unsigned)lab <= (unsigned)a.ncl[r] ? a.map[a.col_start[r] + lab] : 0;
 }

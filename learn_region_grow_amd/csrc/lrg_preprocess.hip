@@ -13,9 +13,9 @@
 // with one room.
 #include "lrg_common.h"
 #include "lrg_eig3.h"
+#include "lrg_room_hash.h"
 
 #define PREP_THREADS 256
-#define PREP_SCAN_ITEMS 8                      // per thread: 2048 elements per block
 
 // ---- order-preserving integer images of floats / doubles (for atomicMin / atomicMax) ----
 __device__ __forceinline__ int prep_ord(float f) { int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
@@ -24,74 +24,6 @@ __device__ __forceinline__ float prep_unord(int i) { return __int_as_float(i >= 
 __global__ void prep_flag_kernel(const int32_t *slot_of, const int32_t *first, int M, int32_t *flag) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < M) flag[i] = (slot_of[i] >= 0 && first[slot_of[i]] == i) ? 1 : 0;
-}
-
-// ---- exclusive scan of an int32 array (three launches; block = 2048 elements) ----
-__device__ __forceinline__ int prep_block_exscan(int v, int *sh, int *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int k = 0; k < PREP_THREADS / 64; ++k) {
-        if (k < w) base += sh[k];
-        tot += sh[k];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(PREP_THREADS) void prep_scan_sums_kernel(const int32_t *x, long n, int32_t *bsum) {
-    __shared__ int sh[PREP_THREADS / 64];
-    const long base = ((long)blockIdx.x * PREP_THREADS + threadIdx.x) * PREP_SCAN_ITEMS;
-    int s = 0;
-    for (int k = 0; k < PREP_SCAN_ITEMS; ++k) s += base + k < n ? x[base + k] : 0;
-    int tot;
-    prep_block_exscan(s, sh, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(PREP_THREADS) void prep_scan_top_kernel(int32_t *bsum, int nb) {   // one block; bsum[nb] = total
-    __shared__ int sh[PREP_THREADS / 64];
-    int carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += PREP_THREADS) {
-        const int i = b0 + threadIdx.x;
-        const int v = i < nb ? bsum[i] : 0;
-        int tot;
-        const int ex = prep_block_exscan(v, sh, &tot);
-        if (i < nb) bsum[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) bsum[nb] = carry;
-}
-
-__global__ __launch_bounds__(PREP_THREADS) void prep_scan_apply_kernel(const int32_t *x, long n, const int32_t *bsum, int32_t *out) {
-    __shared__ int sh[PREP_THREADS / 64];
-    const long base = ((long)blockIdx.x * PREP_THREADS + threadIdx.x) * PREP_SCAN_ITEMS;
-    int v[PREP_SCAN_ITEMS], s = 0;
-    for (int k = 0; k < PREP_SCAN_ITEMS; ++k) { v[k] = base + k < n ? x[base + k] : 0; s += v[k]; }
-    int tot;
-    int run = bsum[blockIdx.x] + prep_block_exscan(s, sh, &tot);
-    for (int k = 0; k < PREP_SCAN_ITEMS; ++k) {
-        if (base + k < n) out[base + k] = run;
-        run += v[k];
-    }
-}
-
-static int prep_exscan(const int32_t *x, long n, int32_t *bsum, int32_t *out, hipStream_t st) {
-    const long per_block = PREP_THREADS * PREP_SCAN_ITEMS;
-    const int nb = (int)((n + per_block - 1) / per_block);
-    hipLaunchKernelGGL(prep_scan_sums_kernel, dim3(nb), dim3(PREP_THREADS), 0, st, x, n, bsum);
-    hipLaunchKernelGGL(prep_scan_top_kernel, dim3(1), dim3(PREP_THREADS), 0, st, bsum, nb);
-    hipLaunchKernelGGL(prep_scan_apply_kernel, dim3(nb), dim3(PREP_THREADS), 0, st, x, n, bsum, out);
-    LRG_LAUNCH_CHECK();
-    return 0;
 }
 
 // raw points of a voxel in file order (normal_grid[k].append(i), :131-133)
@@ -119,16 +51,7 @@ __device__ __forceinline__ void prep_cov_point(const float *raw, int ld, float r
     for (int dx = -1; dx <= 1; ++dx)
         for (int dy = -1; dy <= 1; ++dy)
             for (int dz = -1; dz <= 1; ++dz) {                                 // itertools.product order (:147)
-                const uint64_t key = lrg_pack_voxel(vx + dx, vy + dy, vz + dz);
-                if (key == LRG_HASH_EMPTY) continue;
-                unsigned h = (unsigned)lrg_fmix64(key) & (unsigned)mask;
-                int slot = -1;
-                while (true) {
-                    const uint64_t k = keys[h];
-                    if (k == key) { slot = (int)h; break; }
-                    if (k == LRG_HASH_EMPTY) break;
-                    h = (h + 1) & (unsigned)mask;
-                }
+                const int slot = lrg_room_find(keys, mask, lrg_pack_voxel(vx + dx, vy + dy, vz + dz));
                 if (slot < 0) continue;
                 const int o = hash_off[slot], c = count[slot];
                 for (int t = 0; t < c; ++t) {
@@ -207,9 +130,8 @@ __device__ __forceinline__ void prep_feature_row(const float *p, const int32_t *
 // ---------------------------------------------------------------------------------------------------------------------------------
 // All rooms of a file in one pass.  The rooms' raw rows lie one after the other ([sum M, ld], room r =
 // rows raw_start[r] .. raw_start[r + 1]); every kernel runs over the whole array (or over all hash slots), so the launch count does
-// not depend on the number of rooms.  Room r owns the hash segment at slot 4 raw_start[r] + 64 r, capacity the
-// smallest power of two >= max(64, 2 M_r) (which is < 4 M_r + 64): equal voxel coordinates in two rooms are keys in two tables and
-// never meet.  first / list / hash_off hold file-wide raw indices; ONE scan of the first-point flags ranks the equalised points of
+// not depend on the number of rooms.  Room r owns a hash segment (lrg_room_hash.h): equal voxel coordinates in two rooms are keys in
+// two tables and never meet.  first / list / hash_off hold file-wide raw indices; ONE scan of the first-point flags ranks the equalised points of
 // all rooms back to back in room order, eq_start[r] = its value at raw_start[r]; equalized_idx / unequalized_idx are written
 // room-relative.  Every room has its own status word and its own 16-word scalar block: [0] N, [1] error, [2..7] xyz min/max (ordered
 // ints), [8,9] max curvature (u64), [10] any-NaN, [14,15] eq_start of a one-room call.
@@ -244,49 +166,35 @@ static int pb_layout(const int32_t *raw_start, int n_rooms, PbLayout *L) {
     const long n = raw_start[n_rooms];
     if (n >= (1L << 30)) return LRG_EINVAL - 63;
     // the segments' space (an upper bound of the summed capacities): slot numbers and list offsets stay in int32
-    const long hslots = 4L * n + 64L * n_rooms;
+    const long hslots = lrg_room_hash_slots(n, n_rooms);
     if (hslots >= (1L << 31)) return LRG_EINVAL - 64;
     L->hslots = hslots;
     L->n = (int)n;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = lrg_align_up(o + bytes, 256); return at; };
-    L->keys = take((size_t)hslots * 8);
-    L->first = take((size_t)hslots * 4);
-    L->count = take((size_t)hslots * 4);
-    L->off = take((size_t)hslots * 4);
-    L->rank = take((size_t)hslots * 4);
-    L->cursor = take((size_t)hslots * 4);
-    L->slot = take((size_t)n * 4);
-    L->flag = take((size_t)n * 4);
-    L->list = take((size_t)n * 4);
-    L->room_of = take((size_t)n * 4);
-    L->eglob = take((size_t)n * 4);
-    L->rooms = take((size_t)(n_rooms + 1) * 4);
-    L->status = take((size_t)n_rooms * 4);
-    const long per_block = PREP_THREADS * PREP_SCAN_ITEMS;
-    L->bsum = take((size_t)((hslots + per_block - 1) / per_block + 1) * 4);
-    L->scal = take((size_t)n_rooms * PB_SCAL * 4);
-    L->normal = take((size_t)n * 3 * 8);
-    L->curv = take((size_t)n * 8);
-    L->total = o;
+    LrgArena ws;
+    L->keys = ws.take((size_t)hslots * 8);
+    L->first = ws.take((size_t)hslots * 4);
+    L->count = ws.take((size_t)hslots * 4);
+    L->off = ws.take((size_t)hslots * 4);
+    L->rank = ws.take((size_t)hslots * 4);
+    L->cursor = ws.take((size_t)hslots * 4);
+    L->slot = ws.take((size_t)n * 4);
+    L->flag = ws.take((size_t)n * 4);
+    L->list = ws.take((size_t)n * 4);
+    L->room_of = ws.take((size_t)n * 4);
+    L->eglob = ws.take((size_t)n * 4);
+    L->rooms = ws.take((size_t)(n_rooms + 1) * 4);
+    L->status = ws.take((size_t)n_rooms * 4);
+    L->bsum = ws.take((size_t)(lrg_scan_blocks(hslots) + 1) * 4);
+    L->scal = ws.take((size_t)n_rooms * PB_SCAL * 4);
+    L->normal = ws.take((size_t)n * 3 * 8);
+    L->curv = ws.take((size_t)n * 8);
+    L->total = ws.total;
     return 0;
 }
 
-// Bounds of room r (raw_start was checked on the host: this only keeps a bad word from turning into an address)
+// Bounds of room r; an r out of range and an empty room are refused too
 __device__ __forceinline__ bool pb_room(const PbArgs &a, int r, int *s, int *e) {
-    if (r < 0 || r >= a.n_rooms) return false;
-    const int s0 = a.raw_start[r], e0 = a.raw_start[r + 1];
-    if (s0 < 0 || e0 <= s0 || e0 > a.n) return false;
-    *s = s0; *e = e0;
-    return true;
-}
-
-// the room's hash segment: first slot and mask
-__device__ __forceinline__ void pb_segment(int r, int s, int e, long *off, int *mask) {
-    int cap = 64;
-    while (cap < 2 * (e - s)) cap <<= 1;
-    *off = 4L * s + 64L * r;
-    *mask = cap - 1;
+    return r >= 0 && r < a.n_rooms && lrg_room_bounds(a.raw_start, a.n, r, s, e) && *e > *s;
 }
 
 // single_n > 0: the call is one room of single_n rows, and this kernel writes its bounds to a.raw_start itself -- no copy from the
@@ -300,14 +208,7 @@ __global__ __launch_bounds__(PREP_THREADS) void pb_init_kernel(PbArgs a, int sin
         a.scal[t] = (k >= 2 && k <= 4) ? INT_MAX : (k >= 5 && k <= 7) ? INT_MIN : 0;
     }
     if (t < a.n_rooms) a.status[t] = 0;
-    if (t >= a.n) return;
-    const int i = (int)t;
-    int lo = 0, hi = a.n_rooms - 1;                // the last r with raw_start[r] <= i
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.raw_start[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    a.room_of[i] = lo;
+    if (t < a.n) a.room_of[t] = lrg_room_of(a.raw_start, a.n_rooms, (int)t);
 }
 
 // voxel -> slot of the room's own segment (insert), first raw index and population of every voxel          (:125-133)
@@ -322,20 +223,12 @@ __global__ __launch_bounds__(PREP_THREADS) void pb_insert_kernel(PbArgs a) {
     const uint64_t key = lrg_pack_voxel(lrg_voxel_of(p[0], a.res), lrg_voxel_of(p[1], a.res), lrg_voxel_of(p[2], a.res));
     if (key == LRG_HASH_EMPTY) { a.scal[r * PB_SCAL + 1] = 1; a.status[r] = 1; return; }     // outside the 21-bit voxel window
     long off; int mask;
-    pb_segment(r, s, e, &off, &mask);
-    uint64_t *keys = a.keys + off;
-    unsigned h = (unsigned)lrg_fmix64(key) & (unsigned)mask;
-    for (int probe = 0; probe <= mask; ++probe) {      // (capacity >= 2 M_r: a free slot exists)
-        unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&keys[h]), (unsigned long long)LRG_HASH_EMPTY,
-                                            (unsigned long long)key);
-        if (prev == LRG_HASH_EMPTY || prev == key) {
-            atomicMin(&a.first[off + h], i);
-            atomicAdd(&a.count[off + h], 1);
-            a.slot[i] = (int)(off + h);
-            return;
-        }
-        h = (h + 1) & (unsigned)mask;
-    }
+    lrg_room_segment(r, s, e, &off, &mask);
+    const int h = lrg_room_claim(a.keys + off, mask, key);
+    if (h < 0) return;
+    atomicMin(&a.first[off + h], i);
+    atomicAdd(&a.count[off + h], 1);
+    a.slot[i] = (int)(off + h);
 }
 
 // equalised order = raw order of the first point of each voxel, rooms back to back (:127-129,:134); eq_start and the rooms' N
@@ -378,7 +271,7 @@ __global__ __launch_bounds__(PREP_THREADS) void pb_cov_kernel(PbArgs a) {
     int s, e;
     if (!pb_room(a, r, &s, &e)) return;
     long off; int mask;
-    pb_segment(r, s, e, &off, &mask);
+    lrg_room_segment(r, s, e, &off, &mask);
     const float *pe = a.raw + (long)i * a.ld;
     double C[9];
     prep_cov_point(a.raw, a.ld, a.res, pe, a.keys + off, a.off + off, a.count + off, mask, a.list, C);
@@ -444,14 +337,10 @@ static int pb_run(const PbLayout &L, const PbArgs &a, int single_n, hipStream_t 
     hipLaunchKernelGGL(pb_init_kernel, dim3(gi), dim3(PREP_THREADS), 0, st, a, single_n);
     hipLaunchKernelGGL(pb_insert_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
     hipLaunchKernelGGL(prep_flag_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a.slot, a.first, n, a.flag);
-    LRG_LAUNCH_CHECK();
     // file-wide rank of every first point (scanned into `list`, which is filled only afterwards)
-    if ((rc = prep_exscan(a.flag, n, a.bsum, a.list, st))) return rc;
-    const long per_block = PREP_THREADS * PREP_SCAN_ITEMS;
-    const int nb_m = (int)((n + per_block - 1) / per_block);
-    hipLaunchKernelGGL(pb_equalize_kernel, dim3(ge), dim3(PREP_THREADS), 0, st, a, a.list, a.bsum + nb_m);
-    LRG_LAUNCH_CHECK();
-    if ((rc = prep_exscan(a.count, L.hslots, a.bsum, a.off, st))) return rc;
+    if ((rc = lrg_exscan_i32(a.flag, n, a.bsum, a.list, st))) return rc;
+    hipLaunchKernelGGL(pb_equalize_kernel, dim3(ge), dim3(PREP_THREADS), 0, st, a, a.list, a.bsum + lrg_scan_blocks(n));
+    if ((rc = lrg_exscan_i32(a.count, L.hslots, a.bsum, a.off, st))) return rc;
     hipLaunchKernelGGL(pb_fill_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
     hipLaunchKernelGGL(prep_sort_lists_kernel, dim3(gh), dim3(PREP_THREADS), 0, st, a.off, a.count, (int)L.hslots, a.list);
     hipLaunchKernelGGL(pb_cov_kernel, dim3(gm), dim3(PREP_THREADS), 0, st, a);
