@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 23
+#define LRG_ABI_VERSION 24
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -995,6 +995,12 @@ int lrg_gemm_f32_planes(int M, int N, int K, const float *A, int lda, int transA
  * of a call is summed in a fixed order: the same inputs add the same bits. */
 int lrg_ce_grad(const float *logits, const int32_t *labels, long rows, float w_pos, float w_neg, float *dlogits, double *stats,
                 void *stream);
+/* lrg_ce_grad with the remove head's class weights (learn_region_grow_util.py:166-172) taken on the device (ABI 24): n_pos = the sum of
+ * positives [n_counts] (int32, e.g. lrg_train_assemble's per-instance sums), w_pos = n_pos ? (float)(1.0 / (double)n_pos) : 0,
+ * w_neg the same with rows - n_pos -- the values train.py hands lrg_ce_grad from the host, so dlogits and stats have the same bits and
+ * the step reads nothing back.  LRG_EINVAL - 1: a NULL pointer or rows <= 0; - 2: n_counts < 1. */
+int lrg_ce_grad_counted(const float *logits, const int32_t *labels, long rows, const int32_t *positives, int n_counts, float *dlogits,
+                        double *stats, void *stream);
 /* Gradient of the column max over each instance's rows (:122-123) followed by the pooled layer's ReLU: y [B,rows,C] is that
  * layer's output, dpool [B, dpool_stride] the gradient of its column maxima; dy [B,rows,C] gets dpool / (number of rows that tie
  * for the maximum) on those rows -- tf.reduce_max's rule -- and 0 elsewhere (and 0 everywhere when the maximum is 0). */
@@ -1246,6 +1252,25 @@ int lrg_kitti_first_in_voxel(const double *xyz, int n, double resolution, uint64
 /* stage_semantic_kitti.py:167-183 */
 int lrg_kitti_components(const double *xyz, const int32_t *obj, const int32_t *cls, int n, double resolution, uint64_t *keys, int32_t *vals,
                          int slots, int32_t *root, int32_t *size, int32_t *first_src, uint8_t *emits, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 24.  Training batches for LrgNet assembled on the device (train_region_grow.py:156-175: every tuple of a batch padded /
+ * subsampled to the network's point counts; the losses that consume them are learn_region_grow_util.py:165-186; DESIGN 3.20;
+ * csrc/lrg_assemble.hip).  One side of one batch per call: rows [*, row_stride] float32 and labels [*] int32 are a side's flat buffers
+ * (lrg_stage_tuples' points / remove or neighbor_points / add, or a staged file uploaded as it is), row_start [T] int64 and
+ * row_count [T] int32 the first row and the number of rows of every kept tuple, order [B] the tuple ids of the batch.  Slot j < k of
+ * instance b, with t = order[b] and N = row_count[t], is row row_start[t] + lrg_sample_position(j, N, k, purpose, 0, pass, epoch,
+ * rng_seed, t) of csrc/lrg_rng.h (purposes TRAIN_INLIER 11, TRAIN_NEIGHBOR 12; pass 0 training, 1 validation): N >= k a subset without
+ * replacement, N < k the N rows followed by draws with replacement, as the reference pads -- under the counter stream, a build
+ * extension (the reference draws from one legacy stream), so a tuple's draws depend on (rng_seed, t, epoch, pass) alone.
+ * Writes out_rows [B, k, F] (the F leading columns), out_labels [B, k] and positives [B] (the sum of the instance's gathered labels;
+ * no atomics: the same bytes every time).  N >= 1 and t < T are the caller's contract.  Refused before any launch: LRG_EINVAL - 120 a
+ * NULL pointer, - 121 B < 1, - 122 k outside 1 .. LRG_ASSEMBLE_MAX_POINTS, - 123 F < 1 (or above 65536), - 124 F > row_stride,
+ * - 125 epoch, pass or purpose outside the counter's fields. */
+#define LRG_ASSEMBLE_MAX_POINTS 4096
+int lrg_train_assemble(const float *rows, int row_stride, const int32_t *labels, const int64_t *row_start, const int32_t *row_count,
+                       const int32_t *order, int B, int k, int F, uint32_t rng_seed, int epoch, int pass, int purpose, float *out_rows,
+                       int32_t *out_labels, int32_t *positives, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,9 +12,9 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
            'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip', 'lrg_pointnet_train.hip',
-           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip', 'lrg_mcpnet_train.hip', 'lrg_stage.hip', 'lrg_kitti.hip', 'lrg_scan.hip']
+           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip', 'lrg_mcpnet_train.hip', 'lrg_stage.hip', 'lrg_kitti.hip', 'lrg_scan.hip', 'lrg_assemble.hip']
 
-LRG_ABI_VERSION = 23      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 24      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -135,6 +135,8 @@ LRG_DONE_RING = 1020
 LRG_STATS_WORDS = 4 + LRG_DONE_RING
 LRG_STAGE_MAX_POINTS = 1024
 LRG_STAGE_OK, LRG_STAGE_OVERFLOW, LRG_STAGE_ITER_CAP = range(3)      # lrg_stage_teacher: a room's status word
+LRG_ASSEMBLE_MAX_POINTS = 4096
+LRG_PURPOSE_TRAIN_INLIER, LRG_PURPOSE_TRAIN_NEIGHBOR = 11, 12      # csrc/lrg_rng.h: the draws of lrg_train_assemble's two sides
 LRG_KITTI_MAX_POINTS = 1 << 28
 LRG_KITTI_ST_NONFINITE, LRG_KITTI_ST_WINDOW, LRG_KITTI_ST_SCAN, LRG_KITTI_ST_TABLE = 1, 2, 4, 8      # lrg_kitti_*: bits of the status word
 LRG_FPFH_LISTS = 1                     # lrg_fpfh flags: the pair pass stores the neighbour lists for the gather pass
@@ -339,6 +341,7 @@ _SIGS = {
     'lrg_gemm_f32_planes': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int,
                                            _fp, ctypes.c_int, _fp]),
     'lrg_ce_grad': (ctypes.c_int, [_fp, _fp, ctypes.c_long, ctypes.c_float, ctypes.c_float, _fp, _fp, _fp]),
+    'lrg_ce_grad_counted': (ctypes.c_int, [_fp, _fp, ctypes.c_long, _fp, ctypes.c_int, _fp, _fp, _fp]),
     'lrg_pool_backward': (ctypes.c_int, [_fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp]),
     'lrg_segment_colsum': (ctypes.c_int, [_fp, ctypes.c_long, ctypes.c_int, ctypes.c_int, _fp, _fp]),
     'lrg_adam_step': (ctypes.c_int, [_fp, _fp, _fp, _fp, ctypes.c_long, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _fp]),
@@ -357,6 +360,7 @@ _SIGS = {
     'lrg_metrics_batch_status': (ctypes.c_int, [_fp] + [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _fp]),
     'lrg_stage_teacher': (ctypes.c_int, [_fp, _fp, ctypes.c_int] + [_fp] * 8 + [ctypes.c_uint32] + [ctypes.c_int] * 4 + [_fp]),
     'lrg_stage_tuples': (ctypes.c_int, [_fp] * 3 + [ctypes.c_int] * 2 + [_fp] * 5),
+    'lrg_train_assemble': (ctypes.c_int, [_fp, ctypes.c_int] + [_fp] * 4 + [ctypes.c_int] * 3 + [ctypes.c_uint32] + [ctypes.c_int] * 3 + [_fp] * 4),
     'lrg_kitti_table_slots': (ctypes.c_int, [ctypes.c_int]),
     'lrg_kitti_project': (ctypes.c_int, [_fp, ctypes.c_int, _fp, _fp, ctypes.c_int, ctypes.c_int] + [_fp] * 7 + [ctypes.c_double, _fp, _fp, ctypes.c_int] +
                           [_fp] * 6),

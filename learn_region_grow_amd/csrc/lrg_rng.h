@@ -18,6 +18,9 @@
 #define LRG_PURPOSE_STAGE_RMV 8u
 #define LRG_PURPOSE_STAGE_INLIER 9u      // Feistel keys of an emitted side's subset
 #define LRG_PURPOSE_STAGE_NEIGHBOR 10u
+// training batches (lrg_assemble.hip): key (rng_seed, tuple id), seed_point = 0, restart = the pass (0 training, 1 validation), step = the epoch
+#define LRG_PURPOSE_TRAIN_INLIER 11u
+#define LRG_PURPOSE_TRAIN_NEIGHBOR 12u
 #define LRG_PURPOSE_PERMKEY 0x80u
 
 struct lrg_u32x4 { uint32_t x, y, z, w; };

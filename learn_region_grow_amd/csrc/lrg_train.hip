@@ -111,9 +111,31 @@ __global__ __launch_bounds__(256) void lrg_gemm_f32_kernel(LrgGemmArgs a) {
 
 // stats[0] += sum over the rows of the weighted ce: ONE workgroup; thread t sums rows t, t + 1024, ... in that order, the
 // 1024 partial sums meet in a fixed tree.  (51 200 rows of the real step: 50 rows a thread.)
+// COUNTED (lrg_ce_grad_counted): the class weights are not the arguments but 1 / #positive and 1 / #negative slots, the positives being
+// the sum of positives[0 .. n_counts) -- the division the host does for lrg_ce_grad (in double, rounded to float once), done by every
+// workgroup for itself, so that nothing is read back.
+__device__ __forceinline__ void lrg_ce_counted_weights(const int32_t *positives, int n_counts, long rows, float *sw, float &w_pos, float &w_neg) {
+    if (threadIdx.x < 64) {
+        long long s = 0;
+        for (int i = threadIdx.x; i < n_counts; i += 64) s += positives[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if (threadIdx.x == 0) {
+            const long long n_pos = s, n_neg = (long long)rows - s;
+            sw[0] = n_pos ? (float)(1.0 / (double)n_pos) : 0.0f;
+            sw[1] = n_neg ? (float)(1.0 / (double)n_neg) : 0.0f;
+        }
+    }
+    __syncthreads();
+    w_pos = sw[0]; w_neg = sw[1];
+}
+
+template <bool COUNTED>
 __global__ __launch_bounds__(1024) void lrg_ce_loss_kernel(const float *logits, const int32_t *labels, long rows, float w_pos, float w_neg,
-                                                            double *stats) {
+                                                            const int32_t *positives, int n_counts, double *stats) {
     __shared__ double sh[1024];
+    __shared__ float sw[2];
+    if (COUNTED) lrg_ce_counted_weights(positives, n_counts, rows, sw, w_pos, w_neg);
     double ce = 0.0;
     for (long r = threadIdx.x; r < rows; r += 1024) {
         const float l0 = logits[2 * r], l1 = logits[2 * r + 1];
@@ -131,10 +153,13 @@ __global__ __launch_bounds__(1024) void lrg_ce_loss_kernel(const float *logits, 
     if (threadIdx.x == 0) atomicAdd(&stats[0], sh[0]);
 }
 
+template <bool COUNTED>
 __global__ __launch_bounds__(256) void lrg_ce_grad_kernel(const float *logits, const int32_t *labels, long rows, float w_pos, float w_neg,
-                                                           float *dlogits, double *stats) {
+                                                           const int32_t *positives, int n_counts, float *dlogits, double *stats) {
     __shared__ double sh[6];
+    __shared__ float sw[2];
     if (threadIdx.x < 6) sh[threadIdx.x] = 0.0;
+    if (COUNTED) lrg_ce_counted_weights(positives, n_counts, rows, sw, w_pos, w_neg);
     __syncthreads();
     int ok = 0, tp = 0, pp = 0, lp = 0, nr = 0;
     for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (long)gridDim.x * blockDim.x) {
@@ -244,10 +269,25 @@ int lrg_ce_grad(const float *logits, const int32_t *labels, long rows, float w_p
                 void *stream) {
     if (!logits || !labels || !dlogits || !stats || rows <= 0) return LRG_EINVAL - 1;
     const long blocks = (rows + 255) / 256;
-    hipLaunchKernelGGL(lrg_ce_grad_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)stream, logits, labels,
-                       rows, w_pos, w_neg, dlogits, stats);
+    hipLaunchKernelGGL(lrg_ce_grad_kernel<false>, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)stream, logits, labels,
+                       rows, w_pos, w_neg, (const int32_t *)nullptr, 0, dlogits, stats);
     LRG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(lrg_ce_loss_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, logits, labels, rows, w_pos, w_neg, stats);
+    hipLaunchKernelGGL(lrg_ce_loss_kernel<false>, dim3(1), dim3(1024), 0, (hipStream_t)stream, logits, labels, rows, w_pos, w_neg,
+                       (const int32_t *)nullptr, 0, stats);
+    LRG_LAUNCH_CHECK();
+    return 0;
+}
+
+int lrg_ce_grad_counted(const float *logits, const int32_t *labels, long rows, const int32_t *positives, int n_counts, float *dlogits,
+                        double *stats, void *stream) {
+    if (!logits || !labels || !positives || !dlogits || !stats || rows <= 0) return LRG_EINVAL - 1;
+    if (n_counts < 1) return LRG_EINVAL - 2;
+    const long blocks = (rows + 255) / 256;
+    hipLaunchKernelGGL(lrg_ce_grad_kernel<true>, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)stream, logits, labels,
+                       rows, 0.f, 0.f, positives, n_counts, dlogits, stats);
+    LRG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lrg_ce_loss_kernel<true>, dim3(1), dim3(1024), 0, (hipStream_t)stream, logits, labels, rows, 0.f, 0.f, positives, n_counts,
+                       stats);
     LRG_LAUNCH_CHECK();
     return 0;
 }

@@ -197,14 +197,18 @@ STAGE_ARENA_LAUNCH = 1 << 30        # list entries of one teacher launch (the tu
 
 
 def stage_rooms_gpu(rooms, seed=0, resolution=0.1, max_points=1024, device='cuda:0', cluster_threshold=10, max_steps=500, max_iters=None,
-                    arena_entries=None, info=None):
+                    arena_entries=None, info=None, download=True):
     """The device teacher (csrc/lrg_stage.hip) under the counter stream keyed by (seed, room_id): lrg_stage_teacher over all rooms in one
     launch, then lrg_stage_tuples over all their tuples.  rooms: dicts with points [n,F] float32, obj_id [n] and optionally room_id (default:
     the position in the list).  Returns the dict `merge` returns, rows already centred (stage_data.py:233-240); `save_staged` takes it as it is.
     arena_entries: first arena of every room in list entries (default STAGE_ARENA_PER_POINT per point); a room whose tuples overrun its arena
     is run again with twice as much -- the draws are pure functions, the repeat gives the same tuples.
     info (a dict) collects 'launches', 'overflowed' (room positions), 'bytes_downloaded', 'teacher_ms' / 'tuples_ms' (device time by events),
-    'tuples' and 'objects' (per room the int32 rows steps, seed, points, IoU bits of its stored objects)."""
+    'tuples' and 'objects' (per room the int32 rows steps, seed, points, IoU bits of its stored objects).
+    download=False leaves the rows where lrg_stage_tuples wrote them: the per-tuple lists stay empty and the result has 'device' = dict of the
+    flat device buffers points [rows,F] / remove [rows] / neighbor_points [rows,F] / add [rows] and the host tables row_in / row_nb [T+1] int64
+    (tuple t's rows are row_in[t] .. row_in[t+1]); train_data.TupleStore.from_device takes it.  steps, complete and info as before;
+    bytes_downloaded then counts status, headers and objects only."""
     import ctypes
     import torch
     from . import _lib
@@ -217,7 +221,17 @@ def stage_rooms_gpu(rooms, seed=0, resolution=0.1, max_points=1024, device='cuda
         info = {}
     info.update(launches=0, overflowed=[], bytes_downloaded=0, teacher_ms=0.0, tuples_ms=0.0, tuples=0, objects=[])
     out = dict(points=[], remove=[], neighbor_points=[], add=[], steps=[], complete=[])
+
+    def left_on_device(d_p, d_r, d_q, d_a, row_in, row_nb):
+        return dict(points=d_p, remove=d_r, neighbor_points=d_q, add=d_a, row_in=np.asarray(row_in, dtype=np.int64), row_nb=np.asarray(row_nb, dtype=np.int64))
+
+    def nothing_on_device(F):
+        d = torch.device(device)
+        return left_on_device(torch.empty((0, F), dtype=torch.float32, device=d), torch.empty(0, dtype=torch.int32, device=d),
+                              torch.empty((0, F), dtype=torch.float32, device=d), torch.empty(0, dtype=torch.int32, device=d), [0], [0])
     if not rooms:
+        if not download:
+            out['device'] = nothing_on_device(13)
         return out
     if max_iters is None:
         max_iters = 2 * max_steps + 64
@@ -330,6 +344,8 @@ def stage_rooms_gpu(rooms, seed=0, resolution=0.1, max_points=1024, device='cuda
     T = len(hdr_all)
     info['tuples'] = T
     if T == 0:
+        if not download:
+            out['device'] = nothing_on_device(F)
         return out
     cnt_in, cnt_nb = hdr_all[:, 0].astype(np.int64), hdr_all[:, 1].astype(np.int64)
     row_in = np.concatenate([[0], np.cumsum(cnt_in)])
@@ -365,11 +381,14 @@ def stage_rooms_gpu(rooms, seed=0, resolution=0.1, max_points=1024, device='cuda
         ev[1].record()
         ev[1].synchronize()
         info['tuples_ms'] += ev[0].elapsed_time(ev[1])
+    out['complete'] = list(hdr_all[:, 4].copy().view(np.float32))
+    if not download:
+        out['device'] = left_on_device(d_p, d_r, d_q, d_a, row_in, row_nb)
+        return out
     h_p, h_r, h_q, h_a = d_p.cpu().numpy(), d_r.cpu().numpy(), d_q.cpu().numpy(), d_a.cpu().numpy()
     info['bytes_downloaded'] += h_p.nbytes + h_r.nbytes + h_q.nbytes + h_a.nbytes
     out['points'] = np.split(h_p, row_in[1:-1])
     out['remove'] = np.split(h_r, row_in[1:-1])
     out['neighbor_points'] = np.split(h_q, row_nb[1:-1])
     out['add'] = np.split(h_a, row_nb[1:-1])
-    out['complete'] = list(hdr_all[:, 4].copy().view(np.float32))
     return out
