@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 24
+#define LRG_ABI_VERSION 25
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -1271,6 +1271,50 @@ int lrg_kitti_components(const double *xyz, const int32_t *obj, const int32_t *c
 int lrg_train_assemble(const float *rows, int row_stride, const int32_t *labels, const int64_t *row_start, const int32_t *row_count,
                        const int32_t *order, int B, int k, int F, uint32_t rng_seed, int epoch, int pass, int purpose, float *out_rows,
                        int32_t *out_labels, int32_t *positives, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 25.  Growth trace and frames of animate_region_growing.py (csrc/lrg_trace.hip).  All three calls read the
+ * grower's buffers and write the caller's; none changes a grow kernel's state.
+ *
+ * lrg_trace_snapshot: one snapshot of slot `slot` growing room `room` (greedy growing under the counter stream), enqueued behind
+ * each lrg_grow_step_packed.  After a packed iteration an ACTIVE slot stands between evaluation and mask update, so a snapshot
+ * starts the frame of the step just evaluated -- header (8 words: slot.seed, slot.step + 1 as animate_region_growing.py:374 counts,
+ * room.next_cluster_id, then the counts of :398-401 over the raw points: inlier, neighbour, add, remove; word 7 becomes 1 once the
+ * frame is complete) and a code byte per equalised point, bit 0 = previousMask (:365), bit 1 = the neighbour mask (:318-320) -- and
+ * completes the frame before it: bit 2 = currentMask after the update (:366-373), which is the slot's mask while the slot is on the
+ * same seed one step on, else the points visited since the frame began less the seeds of the zero-step 'noneighbor' regions logged
+ * behind the finished one.  paint [stride] restates instance_color[currentMask] = instance_color_id[cluster_id] (:403) as
+ * paint[after] = (next_cluster_id - 1) % 19 + 1 (the reference's 20-row table would raise at cluster 20; the wrap is ours); the frame's
+ * copy goes to paints.  Frames live in rings of cap_frames rows: headers [cap_frames, 8], codes / paints [cap_frames, stride];
+ * frame f is row f % cap_frames and `consumed` is the number of frames the host has taken.  state [8] (zeroed by the caller once):
+ * [0] frames begun, [1] 1 while the last one awaits its `after`, [2] room.n_regions when it began, [3] error bits (1 a step without a
+ * successor, 2 a list entry outside the room, 4 the ring is full, 8 not the room the buffers were sized for), [4] frames completed.
+ * plan [8] and mark [stride] are scratch (zeroed once), vis_prev [stride] a copy of the visited flags, mult [stride] int32 the number of
+ * raw points per equalised point (:123's unequalized_idx counted).  n = the room's points, stride >= n a multiple of 16; the byte
+ * arrays and mult 16-byte aligned.  Every list entry is checked against n before it is used as an address. */
+int lrg_trace_snapshot(const LrgSlot *slots, const LrgRoom *rooms, int slot, int room, int n, int stride, int cap_frames, int consumed,
+                       int32_t *state, int32_t *plan, int32_t *headers, uint8_t *codes, uint8_t *paints, uint8_t *paint,
+                       uint8_t *vis_prev, uint8_t *mark, const int32_t *mult, void *stream);
+
+/* displayFun of animate_region_growing.py:165-182 (glPointSize squares of GL_POINTS under GL_DEPTH_TEST) once per camera instead of
+ * once per frame: vis [H * W] receives per pixel the smallest key (bits(depth) << 32) | raw index of the points covering it, all ones
+ * where there is none.  xyz [M, 3] float32 raw points; matrix_host: HOST pointer to the 16 floats, row-major, of projection x view
+ * (gluPerspective x gluLookAt, :169,:255).  Per point in float32 without fused multiply-adds: clip_r = ((m[4r] x + m[4r+1] y) + m[4r+2] z)
+ * + m[4r+3]; kept if w > 0 and -w <= x, y, z <= w; ndc = clip / w; xw = (ndc.x * 0.5 + 0.5) * W, yw likewise with H; depth = ndc.z * 0.5
+ * + 0.5; the pixels [floor(xw) - h, floor(xw) + h] x [floor(yw) - h, floor(yw) + h], h = (point_size - 1) / 2, clipped to the window, image
+ * row H - 1 - y (:394).  The result does not depend on the order of execution.  LRG_EINVAL - 1: point_size even or outside 1 .. 63. */
+int lrg_render_visibility(const float *xyz, int M, const float *matrix_host, int W, int H, int point_size, unsigned long long *vis,
+                          void *stream);
+
+/* T palette-index frames out [T, H, W] uint8 through one visibility buffer (:387,:404 result_points[:,3:6] = colour[unequalized_idx]):
+ * pixel = luts[frame_lut[t]][index[t * index_stride + unequalized_idx[vis & 0xffffffff]]], 0 where vis is all ones.  luts [n_luts, 256].
+ * text (nullable) [T, 5, text_len] bytes: the five lines of :397-401 per frame (0 = nothing), drawn with value `white` from font
+ * [font_count, 7] (glyphs of 5 x 7 bits for the characters font_first ..., bit 4 = leftmost) in cells of 6 x 8 font pixels, each
+ * max(1, 40 H / 8000) screen pixels, at x = 10 H / 1000, y = (10 + 50 k) H / 1000 (integer division). */
+int lrg_render_shade(const unsigned long long *vis, const int32_t *unequalized_idx, int M, int n, int W, int H, int T,
+                     const uint8_t *index, long index_stride, const uint8_t *luts, int n_luts, const int32_t *frame_lut,
+                     const uint8_t *text, int text_len, const uint8_t *font, int font_first, int font_count, int white, uint8_t *out,
+                     void *stream);
 
 #ifdef __cplusplus
 }

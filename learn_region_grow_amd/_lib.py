@@ -12,9 +12,9 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
            'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip', 'lrg_pointnet_train.hip',
-           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip', 'lrg_mcpnet_train.hip', 'lrg_stage.hip', 'lrg_kitti.hip', 'lrg_scan.hip', 'lrg_assemble.hip']
+           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip', 'lrg_mcpnet_train.hip', 'lrg_stage.hip', 'lrg_kitti.hip', 'lrg_scan.hip', 'lrg_assemble.hip', 'lrg_trace.hip']
 
-LRG_ABI_VERSION = 24      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 25      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -366,6 +366,10 @@ _SIGS = {
                           [_fp] * 6),
     'lrg_kitti_first_in_voxel': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.c_double, _fp, _fp, ctypes.c_int, _fp, _fp, _fp]),
     'lrg_kitti_components': (ctypes.c_int, [_fp, _fp, _fp, ctypes.c_int, ctypes.c_double, _fp, _fp, ctypes.c_int] + [_fp] * 6),
+    'lrg_trace_snapshot': (ctypes.c_int, [_fp, _fp] + [ctypes.c_int] * 6 + [_fp] * 10),
+    'lrg_render_visibility': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp]),
+    'lrg_render_shade': (ctypes.c_int, [_fp, _fp] + [ctypes.c_int] * 5 + [_fp, ctypes.c_long, _fp, ctypes.c_int, _fp, _fp, ctypes.c_int, _fp,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp]),
 }
 
 EXPORTS = sorted(_SIGS)

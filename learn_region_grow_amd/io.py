@@ -6,6 +6,7 @@
 ``savePCD``     learn_region_grow_util.py:33-55   ASCII PCD v0.7 with packed rgb
 ``label_colors`` test_region_grow.py:368-371      the colour table of the result clouds
 ``read_png``    stage_semantic_kitti.py:103       what imageio.imread gives for the camera images, from zlib and NumPy alone
+``write_png``   animate_region_growing.py:402,409 image.save(..., 'PNG') of a frame, as a palette image
 
 HDF5 goes through ``h5lite`` (h5py is not installed here); weights through ``checkpoint``.
 """
@@ -98,12 +99,13 @@ def _png_unfilter(raw, height, stride, bpp):
 
 
 def read_png(filename):
-    """An 8-bit, non-interlaced grey, RGB or RGBA PNG as uint8 [H, W, 3] (grey repeated, alpha dropped).  Any other PNG is an error."""
+    """An 8-bit, non-interlaced grey, RGB, RGBA or palette PNG as uint8 [H, W, 3] (grey repeated, alpha dropped, palette entries looked up).
+    Any other PNG is an error."""
     with open(filename, 'rb') as f:
         data = f.read()
     if data[:8] != b'\x89PNG\r\n\x1a\n':
         raise ValueError('%s is not a PNG file' % filename)
-    pos, header, idat, ended = 8, None, [], False
+    pos, header, idat, ended, plte = 8, None, [], False, None
     while pos + 8 <= len(data) and not ended:
         length, tag = struct.unpack('>I4s', data[pos:pos + 8])
         body = data[pos + 8:pos + 8 + length]
@@ -113,6 +115,8 @@ def read_png(filename):
             raise ValueError('%s: bad CRC in %s chunk' % (filename, tag.decode('latin-1')))
         if tag == b'IHDR':
             header = struct.unpack('>IIBBBBB', body)
+        elif tag == b'PLTE':
+            plte = body
         elif tag == b'IDAT':
             idat.append(body)
         elif tag == b'IEND':
@@ -121,13 +125,45 @@ def read_png(filename):
     if header is None or not idat or not ended:
         raise ValueError('%s: IHDR, IDAT or IEND missing' % filename)
     width, height, depth, colour, compression, filtering, interlace = header
-    if depth != 8 or colour not in (0, 2, 6) or compression != 0 or filtering != 0 or interlace != 0 or width < 1 or height < 1:
-        raise ValueError('%s: only 8-bit non-interlaced grey / RGB / RGBA PNGs are read (bit depth %d, colour type %d, interlace %d)' %
+    if depth != 8 or colour not in (0, 2, 3, 6) or compression != 0 or filtering != 0 or interlace != 0 or width < 1 or height < 1:
+        raise ValueError('%s: only 8-bit non-interlaced grey / RGB / RGBA / palette PNGs are read (bit depth %d, colour type %d, interlace %d)' %
                          (filename, depth, colour, interlace))
-    bpp = {0: 1, 2: 3, 6: 4}[colour]
+    bpp = {0: 1, 2: 3, 3: 1, 6: 4}[colour]
+    if colour == 3 and (plte is None or len(plte) % 3 or not 3 <= len(plte) <= 768):
+        raise ValueError('%s: a palette image without a valid PLTE chunk' % filename)
     try:
         raw = zlib.decompress(b''.join(idat))
     except zlib.error as e:
         raise ValueError('%s: %s' % (filename, e))
     px = _png_unfilter(raw, height, width * bpp, bpp).reshape(height, width, bpp)
+    if colour == 3:
+        table = np.frombuffer(plte, dtype=np.uint8).reshape(-1, 3)
+        if int(px.max()) >= len(table):
+            raise ValueError('%s: pixel value %d outside the palette of %d entries' % (filename, int(px.max()), len(table)))
+        return np.ascontiguousarray(table[px[:, :, 0]])
     return np.ascontiguousarray(np.repeat(px, 3, axis=2) if bpp == 1 else px[:, :, :3])
+
+
+def _png_chunk(tag, body):
+    return struct.pack('>I', len(body)) + tag + body + struct.pack('>I', zlib.crc32(tag + body) & 0xFFFFFFFF)
+
+
+def encode_png(index, palette, level=1):
+    """The bytes of a palette PNG (colour type 3, 8 bits, every row under filter 0, one IDAT): index [H, W] uint8, palette [P <= 256, 3]."""
+    index, palette = np.ascontiguousarray(index, dtype=np.uint8), np.ascontiguousarray(palette, dtype=np.uint8)
+    if index.ndim != 2 or index.size == 0 or palette.ndim != 2 or palette.shape[1] != 3 or not 1 <= len(palette) <= 256:
+        raise ValueError('write_png: index [H, W] and palette [P <= 256, 3] expected, got %s and %s' % (index.shape, palette.shape))
+    height, width = index.shape
+    rows = np.zeros((height, width + 1), dtype=np.uint8)          # column 0: filter type 0
+    rows[:, 1:] = index
+    return (b'\x89PNG\r\n\x1a\n' + _png_chunk(b'IHDR', struct.pack('>IIBBBBB', width, height, 8, 3, 0, 0, 0)) + _png_chunk(b'PLTE', palette.tobytes()) +
+            _png_chunk(b'IDAT', zlib.compress(rows.tobytes(), level)) + _png_chunk(b'IEND', b''))
+
+
+def write_png(filename, index, palette, level=1):
+    """A frame as a palette PNG: what read_png (or any viewer) turns back into palette[index].  A pixel value outside the palette is an error."""
+    index = np.asarray(index)
+    if index.size and int(index.max()) >= len(palette):
+        raise ValueError('write_png: pixel value %d outside the palette of %d entries' % (int(index.max()), len(palette)))
+    with open(filename, 'wb') as f:
+        f.write(encode_png(index, palette, level))
