@@ -47,6 +47,9 @@ def parse(argv=None):
     ap.add_argument('--metrics', default='host', choices=('host', 'device'),
                     help="the per-room evaluation: 'host' = metrics.room_metrics room by room; 'device' = all rooms of a segmentation call in one "
                          'pass on the GPU (metrics_gpu.room_metrics_batch)')
+    ap.add_argument('--ply-encoder', default='host', choices=('host', 'device'),
+                    help="--save: 'host' = io.savePLY, one vertex line per Python iteration; 'device' = the lines encoded on the GPU "
+                         '(io.savePLY_device: the same files and printed lines)')
     return ap.parse_args(argv)
 
 
@@ -79,7 +82,8 @@ def report_room(args, mode, area, r, names, raw_points, seconds, m, unequalized_
     pts = np.array(raw_points[:, :6], dtype=np.float64)
     colors = io.label_colors(int(m['cluster_label2'].max()) + 1)
     pts[:, 3:6] = colors[m['cluster_label2'], :][unequalized_idx]
-    io.savePLY(os.path.join(out_dir, ('scannet%d.ply' if area == 'scannet' else '%d.ply') % save_id), pts)
+    save = io.savePLY_device if getattr(args, 'ply_encoder', 'host') == 'device' else io.savePLY
+    save(os.path.join(out_dir, ('scannet%d.ply' if area == 'scannet' else '%d.ply') % save_id), pts)
     return save_id + 1
 
 

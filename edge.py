@@ -39,6 +39,9 @@ def parse(argv=None):
     ap.add_argument('--metrics', default='host', choices=('host', 'device'),
                     help="the per-room evaluation: 'host' = metrics.room_metrics room by room; 'device' = all rooms of a batch in one pass on "
                          'the GPU (metrics_gpu.room_metrics_batch)')
+    ap.add_argument('--ply-encoder', default='host', choices=('host', 'device'),
+                    help="--save: 'host' = io.savePLY, one vertex line per Python iteration; 'device' = the lines encoded on the GPU "
+                         '(io.savePLY_device: the same files and printed lines)')
     return ap.parse_args(argv)
 
 

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LRG_ABI_VERSION 25
+#define LRG_ABI_VERSION 26
 #define LRG_EINVAL (-1000)
 #define LRG_ERESIDENCY (-1100)  /* lrg_grow_async: the launch's workgroups cannot all be resident at once on this stream / device (see there) */
 
@@ -1315,6 +1315,31 @@ int lrg_render_shade(const unsigned long long *vis, const int32_t *unequalized_i
                      const uint8_t *index, long index_stride, const uint8_t *luts, int n_luts, const int32_t *frame_lut,
                      const uint8_t *text, int text_len, const uint8_t *font, int font_first, int font_count, int white, uint8_t *out,
                      void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 26.  The ASCII vertex lines of savePLY / savePCD (learn_region_grow_util.py:33-73) encoded on the device, byte for byte what
+ * Python's '%' operator gives (csrc/lrg_text.hip).  lrg_text_encode: n rows -- all rooms of a call back to back -- of
+ * xyz [n, ld] float32 (x, y, z in the first three columns, ld >= 3) and rgb [n, 3] int32 become
+ *   LRG_TEXT_PLY  "%f %f %f %d %d %d\n"
+ *   LRG_TEXT_PCD  "%f %f %f %d\n" with (r << 16) | (g << 8) | b
+ * in text, line i at byte line_off[i]; line_off [n + 1] int32, line_off[n] the total, so the body of the rows [a, b) is
+ * text[line_off[a] : line_off[b]].  '%f' of a float32 is exact integer arithmetic: x 10^6 = (m 15625) 2^(e + 6) with m < 2^24, one
+ * round-half-even on the bits shifted out, the sign printed for -0.0 and for negatives that round to zero.  A row is REFUSED -- a line
+ * of zero bytes, counted in *status (int32 on the device, set by this call) -- if a coordinate is not finite or |x| >= 2^40, and
+ * under LRG_TEXT_PCD if a colour is outside 0 .. 255; the caller writes such a room on the host.  With |x| < 2^40 a '%f' field has at
+ * most 21 bytes and a '%d' field 11, so no line is longer than LRG_TEXT_MAX_LINE; the caller sizes text from that bound:
+ * text_bytes >= n * LRG_TEXT_MAX_LINE, text 16-byte aligned (nothing is read back to size it: one synchronisation, the caller's, before
+ * the download of line_off[n] bytes).  Stream-ordered: length pass, the exclusive scan of lrg_scan.hip over the lengths (int32, hence
+ * n * LRG_TEXT_MAX_LINE < 2^31 per call), write pass; nothing is allocated and nothing synchronised.  workspace:
+ * lrg_text_workspace_bytes(n) bytes, 16-byte aligned.  Refused before any launch: LRG_EINVAL - 130 a NULL pointer or a misaligned
+ * text / workspace, - 131 n < 0 or n * LRG_TEXT_MAX_LINE >= 2^31, - 132 ld < 3, - 133 an unknown format, - 134 workspace_bytes or
+ * text_bytes too small.  n == 0 sets line_off[0] = 0 and *status = 0. */
+#define LRG_TEXT_MAX_LINE 102
+#define LRG_TEXT_PLY 0
+#define LRG_TEXT_PCD 1
+size_t lrg_text_workspace_bytes(int n);
+int lrg_text_encode(const float *xyz, int ld, const int32_t *rgb, int n, int format, void *workspace, size_t workspace_bytes,
+                    int32_t *line_off, uint8_t *text, size_t text_bytes, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,9 +12,9 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'liblrg_hip.so')
 SOURCES = ['lrg_net.hip', 'lrg_fused.hip', 'lrg_grow.hip', 'lrg_grouping.hip', 'lrg_preprocess.hip', 'lrg_train.hip', 'lrg_sampling.hip',
            'lrg_baselines.hip', 'lrg_mcpnet.hip', 'lrg_metrics.hip', 'lrg_pointnet2.hip', 'lrg_pointnet.hip', 'lrg_pointnet_train.hip',
-           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip', 'lrg_mcpnet_train.hip', 'lrg_stage.hip', 'lrg_kitti.hip', 'lrg_scan.hip', 'lrg_assemble.hip', 'lrg_trace.hip']
+           'lrg_pointnet2_train.hip', 'lrg_fpfh.hip', 'lrg_edge.hip', 'lrg_mcpnet_train.hip', 'lrg_stage.hip', 'lrg_kitti.hip', 'lrg_scan.hip', 'lrg_assemble.hip', 'lrg_trace.hip', 'lrg_text.hip']
 
-LRG_ABI_VERSION = 25      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
+LRG_ABI_VERSION = 26      # what this binding was written against (include/lrg_hip.h: LRG_ABI_VERSION; tests/test_capi.py compares them and INTEGRATION.md)
 LRG_EINVAL = -1000
 LRG_ERESIDENCY = -1100     # lrg_grow_async: its workgroups cannot all be resident at once on this stream / device
 LRG_MAX_CONV = 5
@@ -140,6 +140,8 @@ LRG_PURPOSE_TRAIN_INLIER, LRG_PURPOSE_TRAIN_NEIGHBOR = 11, 12      # csrc/lrg_rn
 LRG_KITTI_MAX_POINTS = 1 << 28
 LRG_KITTI_ST_NONFINITE, LRG_KITTI_ST_WINDOW, LRG_KITTI_ST_SCAN, LRG_KITTI_ST_TABLE = 1, 2, 4, 8      # lrg_kitti_*: bits of the status word
 LRG_FPFH_LISTS = 1                     # lrg_fpfh flags: the pair pass stores the neighbour lists for the gather pass
+LRG_TEXT_MAX_LINE = 102                # lrg_text_encode: no line is longer; the caller sizes `text` as n * LRG_TEXT_MAX_LINE
+LRG_TEXT_PLY, LRG_TEXT_PCD = 0, 1
 
 
 class LrgHipError(RuntimeError):
@@ -370,6 +372,8 @@ _SIGS = {
     'lrg_render_visibility': (ctypes.c_int, [_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp]),
     'lrg_render_shade': (ctypes.c_int, [_fp, _fp] + [ctypes.c_int] * 5 + [_fp, ctypes.c_long, _fp, ctypes.c_int, _fp, _fp, ctypes.c_int, _fp,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp]),
+    'lrg_text_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int]),
+    'lrg_text_encode': (ctypes.c_int, [_fp, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_size_t, _fp, _fp, ctypes.c_size_t, _fp, _fp]),
 }
 
 EXPORTS = sorted(_SIGS)

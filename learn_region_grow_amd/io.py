@@ -167,3 +167,187 @@ def write_png(filename, index, palette, level=1):
         raise ValueError('write_png: pixel value %d outside the palette of %d entries' % (int(index.max()), len(palette)))
     with open(filename, 'wb') as f:
         f.write(encode_png(index, palette, level))
+
+
+# ---- vertex lines encoded on the device (lrg_text_encode, csrc/lrg_text.hip) ----------------------------------------
+# The host functions above stay the authority: what follows writes the same bytes and prints the same lines, and hands every room the
+# device refuses (a non-finite coordinate, |x| >= 2^40, a PCD colour outside 0 .. 255), and every array that is not float32 / integral,
+# back to them.
+
+TEXT_FORMATS = {'ply': 0, 'pcd': 1}
+
+
+def _ply_header(n):
+    return ("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % n)
+
+
+def _pcd_header(n):
+    return ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F I\n"
+            "COUNT 1 1 1 1\nWIDTH %d\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %d\nDATA ascii\n" % (n, n))
+
+
+def text_rows_per_call():
+    """The most rows one lrg_text_encode call takes: the byte offsets are int32 and the text is sized from the bound rows * LRG_TEXT_MAX_LINE."""
+    from . import _lib
+    return ((1 << 31) - 1) // _lib.LRG_TEXT_MAX_LINE
+
+
+def text_encode_device(xyz, rgb, format='ply'):
+    """The lines of xyz [n, >= 3] float32 (rows may be strided) and rgb [n, 3] int32, device tensors, enqueued on the current stream of their
+    device: (line_off [n + 1] int32, text uint8, status [1] int32) on the device, nothing synchronised.  Line i is
+    text[line_off[i]:line_off[i + 1]], empty for a refused row; status counts the refused rows."""
+    import torch
+    from . import _lib
+    from .lrgnet import _ptr, _stream_ptr
+    if format not in TEXT_FORMATS:
+        raise ValueError("format must be 'ply' or 'pcd', not %r" % (format,))
+    n = int(xyz.shape[0])
+    if not (xyz.is_cuda and rgb.is_cuda and xyz.dtype == torch.float32 and rgb.dtype == torch.int32 and xyz.dim() == 2 and xyz.shape[1] >= 3 and
+            tuple(rgb.shape) == (n, 3)):
+        raise ValueError('text_encode_device: xyz [n, >= 3] float32 and rgb [n, 3] int32 on the device expected')
+    if n > text_rows_per_call():
+        raise ValueError('text_encode_device: %d rows in one call, at most %d (split the batch at room boundaries)' % (n, text_rows_per_call()))
+    if n and (xyz.stride(1) != 1 or xyz.stride(0) < 3):
+        xyz = xyz[:, :3].contiguous()
+    rgb = rgb.contiguous()
+    lib, dev = _lib.load(), xyz.device
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.lrg_text_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        line_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        text = torch.empty(max(16, n * _lib.LRG_TEXT_MAX_LINE), dtype=torch.uint8, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.lrg_text_encode(_ptr(xyz), int(xyz.stride(0)) if n else 3, _ptr(rgb), n, TEXT_FORMATS[format], _ptr(ws), ws.numel(),
+                                       _ptr(line_off), _ptr(text), text.numel(), _ptr(status), _stream_ptr(dev)), 'lrg_text_encode')
+    return line_off, text, status
+
+
+def _encode_call(xyz, rgb, starts, format):
+    """One launch over the rooms starts[0] .. starts[-1] of device tensors: their bodies as memoryviews into one pinned download, None for a
+    room with a refused row.  One synchronisation before the download."""
+    import torch
+    dev = xyz.device
+    a, b = int(starts[0]), int(starts[-1])
+    line_off, text, status = text_encode_device(xyz[a:b], rgb[a:b], format)
+    with torch.cuda.device(dev):
+        at = torch.as_tensor(np.asarray(starts, dtype=np.int64) - a, device=dev)
+        head = torch.cat([line_off.index_select(0, at), status]).to('cpu', non_blocking=False).numpy()      # the offsets and the status together
+        offs, refused = head[:-1], int(head[-1])
+        total = int(offs[-1])
+        host = torch.empty(max(total, 1), dtype=torch.uint8).pin_memory()
+        host[:total].copy_(text[:total], non_blocking=True)
+        bad = None
+        if refused:
+            gone = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), (line_off[1:] == line_off[:-1]).cumsum(0)])
+            bad = gone.index_select(0, at).cpu().numpy()
+        torch.cuda.current_stream(dev).synchronize()
+    view = memoryview(host.numpy())
+    out = []
+    for r in range(len(starts) - 1):
+        if bad is not None and bad[r + 1] > bad[r]:
+            out.append(None)
+        else:
+            out.append(view[int(offs[r]):int(offs[r + 1])])
+    return out
+
+
+def encode_points_device(xyz, rgb, raw_start, format='ply', device=None):
+    """The file bodies of the rooms raw_start[r] .. raw_start[r + 1] of xyz [n, >= 3] float32 and rgb [n, 3] int32 (NumPy arrays or device
+    tensors): one memoryview per room into a pinned download, or None for a room the device refused (a row with a non-finite coordinate,
+    |x| >= 2^40 or, for 'pcd', a colour outside 0 .. 255) or that is too large for one call: such a room is the host function's.  All rooms
+    go through one launch (more only where rows * LRG_TEXT_MAX_LINE would pass 2^31), split at room boundaries."""
+    import torch
+    raw_start = [int(v) for v in raw_start]
+    if len(raw_start) < 1 or raw_start[0] != 0 or any(b < a for a, b in zip(raw_start, raw_start[1:])) or raw_start[-1] != len(xyz):
+        raise ValueError('encode_points_device: raw_start must rise from 0 to the number of rows')
+    if not torch.is_tensor(xyz):
+        dev = torch.device(device if device is not None else 'cuda')
+        xyz = torch.from_numpy(np.ascontiguousarray(xyz, dtype=np.float32)).to(dev)
+    dev = xyz.device
+    if not torch.is_tensor(rgb):
+        rgb = torch.from_numpy(np.ascontiguousarray(rgb, dtype=np.int32))
+    rgb = rgb.to(dev)
+    cap, out, r, R = text_rows_per_call(), [], 0, len(raw_start) - 1
+    while r < R:
+        if raw_start[r + 1] - raw_start[r] > cap:
+            out.append(None)
+            r += 1
+            continue
+        e = r + 1
+        while e < R and raw_start[e + 1] - raw_start[r] <= cap:
+            e += 1
+        out.extend(_encode_call(xyz, rgb, raw_start[r:e + 1], format))
+        r = e
+    return out
+
+
+def _save_rooms_device(filenames, xyz_rooms, rgb_rooms, format, device=None):
+    import torch
+    if not (len(filenames) == len(xyz_rooms) == len(rgb_rooms)):
+        raise ValueError('one file name, one xyz array and one rgb array per room expected')
+    if not filenames:
+        return []
+    start = np.concatenate([[0], np.cumsum([len(x) for x in xyz_rooms])])
+    if torch.is_tensor(xyz_rooms[0]):
+        xyz = torch.cat([x[:, :3] for x in xyz_rooms]) if len(xyz_rooms) > 1 else xyz_rooms[0]
+        rgb = torch.cat(list(rgb_rooms)) if len(rgb_rooms) > 1 else rgb_rooms[0]
+    else:
+        xyz = np.concatenate([np.asarray(x, dtype=np.float32)[:, :3] for x in xyz_rooms])
+        rgb = np.concatenate([np.asarray(c, dtype=np.int32) for c in rgb_rooms])
+    bodies = encode_points_device(xyz, rgb, start, format, device)
+    routes = []
+    for name, body, x, c in zip(filenames, bodies, xyz_rooms, rgb_rooms):
+        n = len(x)
+        if body is None:
+            x, c = (x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x)), (c.cpu().numpy() if torch.is_tensor(c) else np.asarray(c))
+            (savePLY if format == 'ply' else savePCD)(name, np.hstack([x[:, :3].astype(np.float64), c.astype(np.float64)]))
+            routes.append('host')
+            continue
+        routes.append('device')
+        if format == 'pcd' and n == 0:
+            continue
+        with open(name, 'wb') as f:
+            f.write((_ply_header(n) if format == 'ply' else _pcd_header(n)).encode('ascii'))
+            f.write(body)
+        print('Saved to %s: (%d points)' % (name, n) if format == 'ply' else 'Saved %d points to %s' % (n, name))
+    return routes
+
+
+def save_rooms_ply_device(filenames, xyz_rooms, rgb_rooms, device=None):
+    """savePLY of several rooms through one launch: xyz_rooms[r] [n_r, >= 3] float32 and rgb_rooms[r] [n_r, 3] int32, NumPy arrays or device
+    tensors.  The same files and the same printed lines as savePLY; returns 'device' or 'host' per room, the route it took (a room with a
+    refused row is written by savePLY itself)."""
+    return _save_rooms_device(filenames, xyz_rooms, rgb_rooms, 'ply', device)
+
+
+def _device_rows(points):
+    """xyz float32 and rgb int32 of a points array, or None where the device would not print what the host prints: a coordinate that is
+    not a float32 value, a colour that is not an int32 value (the host's %d truncates, its %f prints the double)."""
+    points = np.asarray(points)
+    if points.ndim != 2 or points.shape[1] < 6 or points.dtype.kind not in 'fiu':
+        return None
+    a = points[:, :6].astype(np.float64)
+    with np.errstate(invalid='ignore', over='ignore'):
+        xyz, rgb = a[:, :3].astype(np.float32), a[:, 3:6].astype(np.int32)
+        same = np.array_equal(np.hstack([xyz, rgb]), a)           # one comparison; a NaN differs from itself and goes to the host too
+    return (xyz, rgb) if same else None
+
+
+def savePLY_device(filename, points, device=None):
+    """savePLY with the vertex lines encoded on the device: the same file, the same printed line.  Returns the route taken."""
+    rows = _device_rows(points) if len(points) else None
+    if rows is None:
+        savePLY(filename, points)
+        return 'host'
+    return _save_rooms_device([filename], [rows[0]], [rows[1]], 'ply', device)[0]
+
+
+def savePCD_device(filename, points, device=None):
+    """savePCD with the vertex lines encoded on the device: the same file, the same printed line, nothing written for zero points."""
+    if len(points) == 0:
+        return 'host'
+    rows = _device_rows(points)
+    if rows is None:
+        savePCD(filename, points)
+        return 'host'
+    return _save_rooms_device([filename], [rows[0]], [rows[1]], 'pcd', device)[0]

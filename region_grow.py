@@ -96,6 +96,9 @@ def parse(argv=None):
                     help="the per-room evaluation (test_region_grow.py:319-355): 'host' = metrics.room_metrics, NumPy and sklearn room by room; "
                          "'device' = all rooms of the rank in one pass on the GPU (metrics_gpu.room_metrics_batch: same matching outputs bit "
                          "for bit, ARS equal, NMI / AMI to ~1e-10)")
+    ap.add_argument('--ply-encoder', default='host', choices=('host', 'device'),
+                    help="--save: 'host' = io.savePLY, one vertex line per Python iteration; 'device' = the lines encoded on the GPU "
+                         '(io.savePLY_device: the same files and printed lines)')
     args = ap.parse_args(argv)
     if args.beam > 0:
         bad = [o for o, on in (('--rng legacy', args.rng != 'counter'), ('--restarts', args.restarts > 1), ('--lanes', args.lanes > 1),
@@ -311,7 +314,7 @@ def main(argv=None):
                 colors = lio.label_colors(int(m['cluster_label2'].max()) + 1)              # test_region_grow.py:368-371
                 cloud[:, 3:6] = colors[m['cluster_label2'], :][pre[k]['unequalized_idx']]
                 name = ('scannet%d.ply' if area == 'scannet' else '%d.ply') % (save_id + room_ids.index(r))
-                lio.savePLY(os.path.join(args.save, name), cloud)
+                (lio.savePLY_device if args.ply_encoder == 'device' else lio.savePLY)(os.path.join(args.save, name), cloud)
         save_id += len(room_ids)
         if world > 1:
             # the final gather (the only collective): every room's labels to every rank over RCCL, the small per-room records as objects
